@@ -8,10 +8,11 @@ evp_prep1/2 + ndte x (fused stress+stepu kernel, velocity halo / tripole fold) +
 already in HBM.  N > 1 shards the SAME grid into x-slabs (one ice_blocks block column of 450x2700 per eighth of the
 grid), i.e. strong scaling, with the halo exchange between the ranks' libevpk contexts.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports them; --full adds the CPU baseline,
+the bit check of the result (N = 1: against the oracle; N > 1: against a one-rank device run) and the informational variants.
 """
 import argparse
 import hashlib
@@ -29,6 +30,8 @@ import numpy as np  # noqa: E402
 ALG_BYTES_STRESS = 360      # 24 reads + 21 writes, fp64 -- the reference's UNFUSED per-subcycle traffic
 ALG_BYTES_STEPU = 232       # 23 reads + 6 writes
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s is what a streaming copy reaches)
+DUMP_CELLS = 1 << 17        # --dump-outputs: grids with more cells are sampled (38 arrays x 2^17 cells x 8 B = 40 MB)
+DUMP_SEED = 20261016
 
 
 def parse():
@@ -48,13 +51,18 @@ def parse():
                          "do not divide leave the last ranks short or idle (the reference's 40x30 blocks = 90 columns on 8 ranks: "
                          "12, ..., 12, 6 -- legal, 2x imbalanced)")
     ap.add_argument("--yblocks", type=int, default=10, help="blocks across y")
-    ap.add_argument("--cpu-subcycles", type=int, default=120, help="subcycles of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline, the bit check of the result and the informational extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write every array the last step returns to a caller as DIR/<name>.npy (float64, "
+                         "physical cells of the global grid in (j, i) order; above %d cells a fixed seeded sample of them)" % DUMP_CELLS)
+    ap.add_argument("--cpu-subcycles", type=int, default=120, help="subcycles of the CPU baseline sample of --full (0 = skip)")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "shm", "ipc"],
                     help="rccl: ncclSend/ncclRecv over xGMI (the measurement); ipc: peer-mapped buffers; shm: host-staged "
                          "shared-memory relay (functional check of the multi-rank path on one GPU, never a measurement)")
     ap.add_argument("--calib", type=int, default=0, help="untimed calibration copies for rocprofv3 --pmc runs")
     ap.add_argument("--no-variants", action="store_true",
-                    help="skip the informational extras (same grid with ns_boundary_type='open', PCIe-inclusive evp; N = 1 only)")
+                    help="with --full: skip the informational extras (same grid with ns_boundary_type='open', PCIe-inclusive evp; N = 1 only)")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc pass (profiles/)")
     return ap.parse_args()
@@ -218,6 +226,8 @@ def main():
     t_setup = time.perf_counter() - t_start
     r = timed_steps(ctx, a.ndte, a.steps, a.warmup, fence)
     st = r["stats"]
+    if a.dump_outputs:
+        dump_outputs(ctx, d, f, a.dump_outputs, rank, world, dist)
 
     vals = torch.tensor([r["wall_s"], r["loop_ms"], float(st.icellt), float(st.icellu)], dtype=torch.float64)
     devs = [(int(st.device), int(st.device_pci))]
@@ -286,7 +296,7 @@ def main():
 
     exit_code = 0
     t_cpu = time.perf_counter()
-    if rank == 0 and world == 1 and a.cpu_subcycles > 0:
+    if rank == 0 and world == 1 and a.full and a.cpu_subcycles > 0:
         # verify: the benched context itself against the oracle on the box the number comes from -- state back at rest, the same
         # `cpu_subcycles` subcycles (default: all ndte) + stress folds + evp_finish on the device (untimed) and, as the cpu_baseline
         # leg below, in the oracle, over the same blocks; the prognostic state compared bit for bit on every cell the reference
@@ -302,27 +312,28 @@ def main():
         out["cpu_baseline"] = cpu_baseline(d, f, a, xmin)       # (runs the oracle in place on f: nv subcycles from the same state)
         out["verify"] = verify(d, got, f, names, nv, vst, out["cpu_baseline"])
         del got
-    elif world > 1 and a.cpu_subcycles > 0:
+    elif world > 1 and a.full and a.cpu_subcycles > 0:
         # verify, N > 1: every rank puts its slab back at rest and runs one untimed evp; rank 0 runs the WHOLE grid as ONE rank on its
         # own GPU (the path the N = 1 line verifies against the oracle) and compares every rank's blocks with it, bit for bit
         v = verify_multirank(a, case, d, f, solver, xmin, local_rank, rank, world, dist)
         if rank == 0:
             out["verify"] = v
     # what the line claims about its ranks is part of the exit code: one RCCL rank and one physical GPU per process (EVPK_FORCE_DEVICE
-    # puts all ranks on one GPU on purpose: tests), and a result that equals the one-rank run
+    # puts all ranks on one GPU on purpose: tests), and with --full a result that equals the one-rank run
     if rank == 0 and world > 1:
         want_dev = 1 if os.environ.get("EVPK_FORCE_DEVICE") is not None else world
         checks = {"devices": out["config"]["devices"] == want_dev,
-                  "rccl_ranks": (out["config"]["rccl_ranks"] == world) if a.transport == "rccl" else True,
-                  "bit_identical": out.get("verify", {}).get("bit_identical") is not False}
+                  "rccl_ranks": (out["config"]["rccl_ranks"] == world) if a.transport == "rccl" else True}
+        if "verify" in out:
+            checks["bit_identical"] = out["verify"].get("bit_identical") is not False
         out["checks"] = checks
         if not all(checks.values()):
             out["failed"] = "checks"
             exit_code = 4
     t_cpu = time.perf_counter() - t_cpu
     t_extra = time.perf_counter()
-    # (profiling runs pass --cpu-subcycles 0 and skip the extras, so that their traces hold the timed workload only)
-    if world == 1 and a.cpu_subcycles > 0 and not a.no_variants:
+    # (only with --full: a plain run, and so a profiling run, holds the timed workload only)
+    if world == 1 and a.full and a.cpu_subcycles > 0 and not a.no_variants:
         # informational, never part of `value`: the same grid closed at the north (ns_boundary_type = 'open': no fold, so
         # no band launches), timed the same way -- HIP events on the library's stream, same roofline accounting
         solver.close()
@@ -448,6 +459,43 @@ def verify_multirank(a, case, d, f, solver, xmin, device, rank, world, dist):
             "what": f"every rank: state at rest -> {a.ndte} subcycles + stress folds + evp_finish on its slab (untimed, after the timed steps); "
                     f"rank 0: the same on the whole grid in ONE context on its own GPU (the configuration the N = 1 line verifies against the "
                     f"oracle); (u, v) on all cells of every block, sigma on physical + N/E ghost T cells, the ocean stresses on physical cells"}
+
+
+def dump_outputs(ctx, d, f, out_dir, rank, world, dist):
+    """--dump-outputs: what the last timed step left for a caller -- every array evpk_download returns (the prognostic state,
+    the outputs of evp, iceumask / icetmask, the halo-updated strength) -- on physical cells of the global grid in (j, i) order:
+    all of them as (ny, nx) when the grid has at most DUMP_CELLS cells, else the same seeded sample of DUMP_CELLS cells (1-D,
+    ascending cell index) for every array, whatever the decomposition.  Rank 0 writes DIR/<name>.npy in float64."""
+    from cice5_amd import synth
+    names = synth.STATE_FIELDS + synth.OUTPUT_FIELDS + ["iceumask", "icetmask", "strength"]
+    ncell = d.nx_global * d.ny_global
+    cells = np.arange(ncell) if ncell <= DUMP_CELLS else \
+        np.sort(np.random.default_rng(DUMP_SEED).choice(ncell, DUMP_CELLS, replace=False))
+    jg, ig = np.divmod(cells, d.nx_global)
+    pos, src = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]      # sampled cells this rank owns -> flat index into its block arrays
+    for n, b in enumerate(d.local_blocks):
+        j0, i0 = b.jglob_lo - 1, b.iglob_lo - 1
+        k = np.nonzero((jg >= j0) & (jg <= j0 + b.jhi - b.jlo) & (ig >= i0) & (ig <= i0 + b.ihi - b.ilo))[0]
+        pos.append(k)
+        src.append(np.ravel_multi_index((np.full(k.size, n), jg[k] - j0 + b.jlo - 1, ig[k] - i0 + b.ilo - 1), f["uvel"].shape))
+    pos, src = np.concatenate(pos), np.concatenate(src)
+    mine = {}
+    for name in names:                  # one array at a time: the whole set at 3600x2700 would be 3 GB of host memory
+        a = np.zeros_like(f[name])
+        ctx.download({name: a})
+        mine[name] = a.ravel()[src].astype(np.float64)
+    parts = [(pos, mine)]
+    if world > 1:
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object((pos, mine), parts, dst=0)
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for name in names:
+        v = np.zeros(cells.size)        # (cells of land blocks no rank holds stay 0)
+        for p, m in parts:
+            v[p] = m[name]
+        np.save(os.path.join(out_dir, name + ".npy"), v.reshape(d.ny_global, d.nx_global) if cells.size == ncell else v)
 
 
 def timed_steps(ctx, ndte, steps, warmup, fence):

@@ -12,7 +12,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 COMMON="--steps 4 --warmup 1 --cpu-subcycles 0"
 # 1. the bench line as the driver runs it (CPU baseline and extras included)
-python3 bench.py > "$out/bench_n1.json" 2> "$out/bench_n1.err"
+python3 bench.py --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"
 # 2. per workload: kernel trace, then FETCH_SIZE / WRITE_SIZE passes (they do not fit in one) with calibration copies
 profile() {   # name, bench flags
   local name=$1; shift

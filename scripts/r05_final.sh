@@ -20,7 +20,7 @@ cat "$out/fuzz.txt"
 # the self-verifying multi-rank bench line at FULL size: 2 and 4 rank processes sharing the one GPU over the peer-mapped transport (a functional
 # check, not a scaling number): every rank's blocks against the one-rank device run of the whole grid, bit for bit
 for n in 2 4; do
-  EVPK_FORCE_DEVICE=0 timeout 900 python3 bench.py --gpus $n --steps 2 --warmup 1 --transport ipc 2>/dev/null | grep '^{' | tail -1 > "$out/bench_n${n}_shared_gpu_ipc.json"
+  EVPK_FORCE_DEVICE=0 timeout 900 python3 bench.py --full --gpus $n --steps 2 --warmup 1 --transport ipc 2>/dev/null | grep '^{' | tail -1 > "$out/bench_n${n}_shared_gpu_ipc.json"
   python3 -c "
 import json,sys
 o=json.load(open('$out/bench_n${n}_shared_gpu_ipc.json')); v=o.get('verify',{})

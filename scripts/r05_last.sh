@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.." || exit 1
 tag=${1:-r05_last}; out=gpurun_out/$tag; mkdir -p "$out"
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -i "smoke" | tee "$out/smoke.txt"
-python3 bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"
+python3 bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
 python3 -c "
 import json
 o=json.loads([l for l in open('$out/bench_default.json') if l.startswith('{')][-1]); r=o['roofline']

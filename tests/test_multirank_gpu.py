@@ -466,7 +466,7 @@ def test_random_unequal_slabs_on_a_tripole_grid(seed):
 
 @pytest.mark.parametrize("ns,world", [("tripole", 2), ("open", 3)])
 def test_bench_line_of_a_multirank_run_verifies_itself(ns, world):
-    """`python bench.py --gpus N`: after the timed steps every rank runs one untimed evp from rest and rank 0 compares all of it,
+    """`python bench.py --full --gpus N`: after the timed steps every rank runs one untimed evp from rest and rank 0 compares all of it,
     bit for bit, with a ONE-rank device run of the whole grid on its own GPU (`verify.against = "1-rank device run"`); what the
     line says about its ranks (`devices`, `rccl_ranks`) and the comparison are part of the exit code.  Here: the ranks share the
     box's GPU(s) as the other cases of this file do, over the peer-mapped transport."""
@@ -476,7 +476,7 @@ def test_bench_line_of_a_multirank_run_verifies_itself(ns, world):
     shared = not _per_rank(world)
     if shared:
         env["EVPK_FORCE_DEVICE"] = "0"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--transport", "ipc",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--transport", "ipc",
                         "--grid", "720x400", "--xblocks", "6", "--yblocks", "2", "--ndte", "24", "--ns", ns, "--dt", "1800"],
                        capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
