@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/evpk.h"
@@ -1199,6 +1200,20 @@ static int halo_stress12(evpk_ctx *c, int f0) {
     return 0;
 }
 
+// ---- run-time flags -> template arguments ------------------------------------------------------------------
+// with_bool(flag, f) calls f(std::true_type{}) or f(std::false_type{}): inside f, decltype(B)::value is a constant expression.
+// Every kernel family below maps its flags to template arguments in ONE place; only combinations that are written out there are
+// instantiated (evpk_kernels.hip instantiates exactly those explicitly).
+template <class F> static inline void with_bool(bool flag, F &&f) {
+    if (flag) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F> static inline void with_bool(bool flag1, bool flag2, F &&f) {
+    with_bool(flag1, [&](auto B1) { with_bool(flag2, [&](auto B2) { f(B1, B2); }); });
+}
+
+// workgroups of a launch (or of one part of it: strips, band, mirror slab) rounded up to a multiple of 8: XCD remap in the kernels
+static inline int xcd_round(int nwg) { return (nwg + 7) & ~7; }
+
 // ---- launch of the two-subcycle kernel (plain or LDS-prefetch variant) ------------------------------------
 static void launch_sub2(evpk_ctx *c, const SubArgs &a_in, hipStream_t st, bool revp, bool last2) {
     // The tripole band (and mirror-slab) workgroups as the LAST of the grid (round 5) -- in the marching kernel only.  There the
@@ -1208,60 +1223,62 @@ static void launch_sub2(evpk_ctx *c, const SubArgs &a_in, hipStream_t st, bool r
     // started last, the band is all that is left running (1440x1080 tripole 2.90 -> 3.40 ms per evp): there it stays first.
     SubArgs a = a_in;
     a.band_last = (c->band_last && !c->tile_mode) ? 1 : 0;
-    const int nband8 = (a.nband + 7) & ~7;      // the tripole top band as workgroups of the pair's own launch (band_pair)
     const bool xm = a.nmir > 0 && !last2 && a.xm && (c->tile_mode || c->prefetch);      // ... then the strips of the mirror slab (x-slab ranks, XM kernels)
-    if (c->tile_mode && c->tile_roll) {      // ... rolling north through a strip of R rows: min(R + 3, ROLL_NW) waves per workgroup
-        const int nw = std::min(a.R + 3, ROLL_NW);
-        const dim3 gt(((a.nstrips + 7) / 8) * 8 + nband8 + (xm ? (a.nmir + 7) & ~7 : 0)), bt(nw * 64);
-        const size_t lds = std::max((size_t)nw * ROLL_LDS_PER_WAVE, a.nband ? sizeof(double) * BAND_LDS_DOUBLES : (size_t)0);
-        if (xm)         { if (revp) hipLaunchKernelGGL((k_subcycle2r<true, false, true>), gt, bt, lds, st, a); else hipLaunchKernelGGL((k_subcycle2r<false, false, true>), gt, bt, lds, st, a); }
-        else if (last2) { if (revp) hipLaunchKernelGGL((k_subcycle2r<true, true>), gt, bt, lds, st, a); else hipLaunchKernelGGL((k_subcycle2r<false, true>), gt, bt, lds, st, a); }
-        else            { if (revp) hipLaunchKernelGGL((k_subcycle2r<true, false>), gt, bt, lds, st, a); else hipLaunchKernelGGL((k_subcycle2r<false, false>), gt, bt, lds, st, a); }
-        return;
-    }
-    if (c->tile_mode) {      // small-slab variant: one workgroup of R + 3 waves per strip, one row per wave
-        const dim3 gt(((a.nstrips + 7) / 8) * 8 + nband8 + (xm ? (a.nmir + 7) & ~7 : 0)), bt((a.R + 3) * 64);
-        const size_t lds = std::max((size_t)(a.R + 3) * (4096 + 5 * 1024), a.nband ? sizeof(double) * BAND_LDS_DOUBLES : (size_t)0);
-        if (xm)         { if (revp) hipLaunchKernelGGL((k_subcycle2t<true, false, true>), gt, bt, lds, st, a); else hipLaunchKernelGGL((k_subcycle2t<false, false, true>), gt, bt, lds, st, a); }
-        else if (last2 && a.R + 3 <= 8) { if (revp) hipLaunchKernelGGL(k_subcycle2t8<true>, gt, bt, lds, st, a); else hipLaunchKernelGGL(k_subcycle2t8<false>, gt, bt, lds, st, a); }      // (no scratch)
-        else if (last2) { if (revp) hipLaunchKernelGGL((k_subcycle2t<true, true>), gt, bt, lds, st, a); else hipLaunchKernelGGL((k_subcycle2t<false, true>), gt, bt, lds, st, a); }
-        else            { if (revp) hipLaunchKernelGGL((k_subcycle2t<true, false>), gt, bt, lds, st, a); else hipLaunchKernelGGL((k_subcycle2t<false, false>), gt, bt, lds, st, a); }
-        return;
-    }
-    const dim3 g((((a.nstrips + 3) / 4 + 7) / 8) * 8 + nband8 + (xm ? (((a.nmir + 3) / 4) + 7) & ~7 : 0)), b(256);     // multiples of 8: XCD remap in the kernel
-    if (c->prefetch) {
-#define EVPK_L2P(RV, L2, CMX) hipLaunchKernelGGL((k_subcycle2p<RV, L2, CMX>), g, b, 0, st, a)
-#define EVPK_L2X(RV, CMX) hipLaunchKernelGGL((k_subcycle2p<RV, false, CMX, true>), g, b, 0, st, a)
-        if (xm) {
-            if (c->compact) { if (revp) EVPK_L2X(true, true); else EVPK_L2X(false, true); }
-            else            { if (revp) EVPK_L2X(true, false); else EVPK_L2X(false, false); }
-        } else if (c->compact) {
-            if (last2) { if (revp) EVPK_L2P(true, true, true); else EVPK_L2P(false, true, true); }
-            else       { if (revp) EVPK_L2P(true, false, true); else EVPK_L2P(false, false, true); }
-        } else {
-            if (last2) { if (revp) EVPK_L2P(true, true, false); else EVPK_L2P(false, true, false); }
-            else       { if (revp) EVPK_L2P(true, false, false); else EVPK_L2P(false, false, false); }
+    // the strips (tile kernels: one per workgroup, marching kernels: four), then the tripole top band as workgroups of the pair's
+    // own launch (band_pair), then the strips of the mirror slab
+    const int per_wg = c->tile_mode ? 1 : 4;
+    const dim3 g(xcd_round((a.nstrips + per_wg - 1) / per_wg) + xcd_round(a.nband) + (xm ? xcd_round((a.nmir + per_wg - 1) / per_wg) : 0));
+    const size_t band_lds = a.nband ? sizeof(double) * BAND_LDS_DOUBLES : (size_t)0;
+    // XM excludes LAST2 (the mirror slab is only advanced when another pair follows): <*, true, *, true> is never named
+    with_bool(revp, [&](auto RV) {
+        constexpr bool rv = decltype(RV)::value;
+        if (c->tile_mode && c->tile_roll) {      // ... rolling north through a strip of R rows: min(R + 3, ROLL_NW) waves per workgroup
+            const int nw = std::min(a.R + 3, ROLL_NW);
+            const dim3 b(nw * 64);
+            const size_t lds = std::max((size_t)nw * ROLL_LDS_PER_WAVE, band_lds);
+            if (xm) hipLaunchKernelGGL((k_subcycle2r<rv, false, true>), g, b, lds, st, a);
+            else with_bool(last2, [&](auto L2) { hipLaunchKernelGGL((k_subcycle2r<rv, decltype(L2)::value>), g, b, lds, st, a); });
+        } else if (c->tile_mode) {               // small-slab variant: one workgroup of R + 3 waves per strip, one row per wave
+            const dim3 b((a.R + 3) * 64);
+            const size_t lds = std::max((size_t)(a.R + 3) * (4096 + 5 * 1024), band_lds);
+            if (xm) hipLaunchKernelGGL((k_subcycle2t<rv, false, true>), g, b, lds, st, a);
+            else if (last2 && a.R + 3 <= 8) hipLaunchKernelGGL(k_subcycle2t8<rv>, g, b, lds, st, a);      // (no scratch)
+            else with_bool(last2, [&](auto L2) { hipLaunchKernelGGL((k_subcycle2t<rv, decltype(L2)::value>), g, b, lds, st, a); });
+        } else if (c->prefetch) {
+            const dim3 b(256);
+            if (xm) with_bool(c->compact, [&](auto CMX) { hipLaunchKernelGGL((k_subcycle2p<rv, false, decltype(CMX)::value, true>), g, b, 0, st, a); });
+            else with_bool(last2, c->compact, [&](auto L2, auto CMX) { hipLaunchKernelGGL((k_subcycle2p<rv, decltype(L2)::value, decltype(CMX)::value>), g, b, 0, st, a); });
         }
-#undef EVPK_L2P
-#undef EVPK_L2X
-    }
 #ifdef EVPK_EXPERIMENTAL
-    else {
-        if (last2) { if (revp) hipLaunchKernelGGL((k_subcycle2<true, true>), g, b, 0, st, a); else hipLaunchKernelGGL((k_subcycle2<false, true>), g, b, 0, st, a); }
-        else       { if (revp) hipLaunchKernelGGL((k_subcycle2<true, false>), g, b, 0, st, a); else hipLaunchKernelGGL((k_subcycle2<false, false>), g, b, 0, st, a); }
-    }
+        else with_bool(last2, [&](auto L2) { hipLaunchKernelGGL((k_subcycle2<rv, decltype(L2)::value>), g, dim3(256), 0, st, a); });
 #endif
+    });
 }
 
 // three subcycles in one launch: one workgroup of three waves per strip (k_subcycle3w)
 static void launch_sub3(evpk_ctx *c, const SubArgs &a, hipStream_t st, bool revp) {
 #ifdef EVPK_EXPERIMENTAL
-    const dim3 g(((a.nstrips + 7) / 8) * 8), b(192);            // multiple of 8: XCD remap in the kernel
-    if (c->compact) { if (revp) hipLaunchKernelGGL((k_subcycle3w<true, true>), g, b, 0, st, a); else hipLaunchKernelGGL((k_subcycle3w<false, true>), g, b, 0, st, a); }
-    else            { if (revp) hipLaunchKernelGGL((k_subcycle3w<true, false>), g, b, 0, st, a); else hipLaunchKernelGGL((k_subcycle3w<false, false>), g, b, 0, st, a); }
+    with_bool(revp, c->compact, [&](auto RV, auto CMX) {
+        hipLaunchKernelGGL((k_subcycle3w<decltype(RV)::value, decltype(CMX)::value>), dim3(xcd_round(a.nstrips)), dim3(192), 0, st, a);
+    });
 #else
     (void)c; (void)a; (void)st; (void)revp;      // (never reached: evpk_create refuses EVPK_TRIPLE=1 without the kernel)
 #endif
+}
+
+// one subcycle, one row per wave (k_subcycle_t): the band launches of a tripole pair -- their sequence is on the critical path of
+// every pair -- and the one-subcycle launch of a small slab
+static void launch_sub1t(const SubArgs &a, hipStream_t st, bool revp, bool last) {
+    with_bool(last, revp, [&](auto LAST, auto RV) {
+        hipLaunchKernelGGL((k_subcycle_t<decltype(LAST)::value, decltype(RV)::value>), dim3(a.nstrips), dim3((a.R + 1) * 64), (size_t)(a.R + 1) * 2048, st, a);
+    });
+}
+
+// one subcycle, marching: four strips per workgroup (k_subcycle)
+static void launch_sub1(const SubArgs &a, hipStream_t st, bool revp, bool last) {
+    with_bool(last, revp, [&](auto LAST, auto RV) {
+        hipLaunchKernelGGL((k_subcycle<decltype(LAST)::value, decltype(RV)::value>), dim3(xcd_round((a.nstrips + 3) / 4)), dim3(256), 0, st, a);
+    });
 }
 
 // ---- ghost zones (zW columns per side) of a list of pair planes: x-slab neighbours ------------------------
@@ -2481,23 +2498,30 @@ extern "C" int evpk_eap_download(evpk_ctx *c, evpk_eap_state *st) {
     return 0;
 }
 
+// the per-call counters of evpk_get_stats: zero at the start of every subcycle call, whichever loop runs it
+static void reset_call_counters(evpk_ctx *c) {
+    c->kernel_ms = c->kernel2_ms = c->kernel3_ms = 0.f;
+    c->kernel_launches = c->double_launches = c->triple_launches = 0;
+    c->kernel_timed = c->kernel2_timed = c->kernel3_timed = 0;
+    c->bound_updates = 0; c->bound_timed = 0; c->bound_ms = 0.f;
+    c->xb_swaps = 0; c->zone_exchanges = 0; c->zone_bytes = 0;
+}
+
 // the subcycle loop of eap(dt) (ice_dyn_eap.F90:345-447): stress_eap, stepu, [stepa], velocity halo -- in place in the current buffer
 static int eap_subcycle(evpk_ctx *c, int32_t nsub) {
     Slab &s = c->s;
     const int SB = c->cur ? F_STATE1 : F_STATE0;
     const dim3 gT((s.nxl + 1 + 63) / 64, (s.nyl + 1 + 3) / 4), gU((s.nxl + 63) / 64, (s.nyl + 3) / 4);
     const double dte = c->p.dt / (double)c->p.ndte, dtei = 1.0 / dte;        // ice_dyn_shared.F90:209-210
-    c->kernel_ms = c->kernel2_ms = 0.f;
-    c->kernel_launches = c->double_launches = c->triple_launches = 0;
-    c->kernel_timed = c->kernel2_timed = c->kernel3_timed = 0;
-    c->bound_updates = 0; c->bound_timed = 0; c->bound_ms = 0.f;
+    reset_call_counters(c);
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (c->ksub == 0) hipLaunchKernelGGL(k_eap_reset, grid2d(s, B2D), B2D, 0, c->stream, s, c->E);
     for (int n = 0; n < nsub; n++) {
         const int ksub = c->ksub + 1;
         const int hist = (ksub == c->p.ndte || n == nsub - 1) ? 1 : 0;      // the history fields of the call's last subcycle are the ones that can be seen
-        if (ksub == c->p.ndte) hipLaunchKernelGGL(k_eap_stress<true>, gT, B2D, 0, c->stream, s, c->E, SB, c->p.arlx1i, c->p.denom1, hist);
-        else hipLaunchKernelGGL(k_eap_stress<false>, gT, B2D, 0, c->stream, s, c->E, SB, c->p.arlx1i, c->p.denom1, hist);
+        with_bool(ksub == c->p.ndte, [&](auto LAST) {
+            hipLaunchKernelGGL(k_eap_stress<decltype(LAST)::value>, gT, B2D, 0, c->stream, s, c->E, SB, c->p.arlx1i, c->p.denom1, hist);
+        });
         hipLaunchKernelGGL(k_eap_stepu, gU, B2D, 0, c->stream, s, c->E, c->p, SB);
         if (ksub % 10 == 1) hipLaunchKernelGGL(k_eap_stepa, gT, B2D, 0, c->stream, s, c->E, SB, dtei);     // :411-426
         if (halo(c, SB + S_U, 2, true, true, 0.0)) return 1;                                               // :431-439
@@ -2523,98 +2547,116 @@ static void take_counts(evpk_ctx *c) {
     c->counts_pending = false;
 }
 
-static int subcycle_impl(evpk_ctx *c, int32_t nsub) {
-    if (!c->prepped) FAIL(c, "evpk_prep has not been called");
-    if (nsub < 0) FAIL(c, "nsub < 0");
-    Slab &s = c->s;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->eap) {       // EVPK_EAP_FUSED=0: stress_eap and stepu as two launches with str(8) through memory, in place
-        const char *e = getenv("EVPK_EAP_FUSED");
-        if (e && atoi(e) == 0) return eap_subcycle(c, nsub);
-    }
-    const bool wrap = (c->nranks == 1 && c->ew == EVPK_BND_CYCLIC && !c->force_exchange);
-    const bool need_halo = (c->nranks > 1) || (c->ns == EVPK_BND_TRIPOLE) || c->force_exchange;
-    c->kernel_ms = 0.f;
-    c->kernel2_ms = 0.f;
-    c->kernel3_ms = 0.f;
-    c->kernel_launches = 0;
-    c->kernel_timed = c->kernel2_timed = c->kernel3_timed = 0;
-    if (c->time_kernels) {
-        while ((int)c->kev.size() < 2 * nsub + 2) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->kev.push_back(e); }
-    }
-    c->kev_kind.clear(); c->kev_count.clear();
-    c->nkev = 0;
-    // Kernel timing by HIP events on the stream the launches go to, in SPANS: one event in front of a run of consecutive
-    // launches of one kind (1, 2 or 3 subcycles per launch) and one behind it, launches 3..8 of every 20 by default
-    // (EVPK_TIME_KERNELS=2: every launch a span of its own, 0: none).  A span's time / its launches is the per-launch time as the
-    // stream's timeline has it (launch gaps included, the ~4-8 us an event pair costs spread over six launches), so that
-    // launches x average never exceeds the loop time.  A span ends early when the kind or the stream changes and in front of any
-    // halo / fold / exchange work.
-    bool span_open = false;
-    int span_kind = 0, span_n = 0;
+// ---- the timers of the subcycle loop (events owned by the context: kev, bev) --------------------------------------------------
+// Kernel timing by HIP events on the stream the launches go to, in SPANS: one event in front of a run of consecutive
+// launches of one kind (1, 2 or 3 subcycles per launch) and one behind it, launches 3..8 of every 20 by default
+// (EVPK_TIME_KERNELS=2: every launch a span of its own, 0: none).  A span's time / its launches is the per-launch time as the
+// stream's timeline has it (launch gaps included, the ~4-8 us an event pair costs spread over six launches), so that
+// launches x average never exceeds the loop time.  A span ends early when the kind or the stream changes and in front of any
+// halo / fold / exchange work.
+struct LoopTimer {
+    evpk_ctx *c;
+    bool span_open = false, bound_open = false;
+    int span_kind = 0, span_n = 0, span_len = 6;
     hipStream_t span_stream = nullptr;
-    const int span_len = c->time_kernels == 2 ? 1 : 6;
-    auto span_close = [&]() -> int {
+    int start(int nsub) {       // before the loop: an event pair for every launch of the call, no span recorded yet
+        while (c->time_kernels && (int)c->kev.size() < 2 * nsub + 2) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->kev.push_back(e); }
+        c->kev_kind.clear(); c->kev_count.clear();
+        c->nkev = 0;
+        span_len = c->time_kernels == 2 ? 1 : 6;
+        return 0;
+    }
+    int close() {       // end the open span, if any
         if (!span_open) return 0;
         span_open = false;
         const int rc = hipEventRecord(c->kev[2 * c->nkev + 1], span_stream) != hipSuccess;
         c->kev_kind.push_back(span_kind); c->kev_count.push_back(span_n);
         c->nkev++;
-        return rc;
-    };
-    auto ev_begin = [&](hipStream_t st, int kind) -> int {
-        if (span_open && (kind != span_kind || st != span_stream) && span_close()) return 1;
+        if (rc) FAIL(c, "hipEventRecord failed");
+        return 0;
+    }
+    int begin(hipStream_t st, int kind) {       // in front of a launch of `kind` subcycles on `st`
+        if (span_open && (kind != span_kind || st != span_stream) && close()) return 1;
         if (span_open || !c->time_kernels) return 0;
         if (c->time_kernels == 1 && c->kernel_launches % 20 != 3) return 0;      // (an event pair stalls the queue for a few microseconds)
         if (2 * c->nkev + 2 > (int)c->kev.size()) return 0;
         span_open = true; span_kind = kind; span_n = 0; span_stream = st;
-        return hipEventRecord(c->kev[2 * c->nkev], st) != hipSuccess;
-    };
-    auto ev_end = [&](hipStream_t) -> int {
+        if (hipEventRecord(c->kev[2 * c->nkev], st) != hipSuccess) FAIL(c, "hipEventRecord failed");
+        return 0;
+    }
+    int end() {         // behind that launch
         if (!span_open) return 0;
-        return (++span_n >= span_len) ? span_close() : 0;
-    };
+        return (++span_n >= span_len) ? close() : 0;
+    }
     // the same sampling for the halo / fold / ghost-zone updates (what the reference books under timer_bound): an event pair
     // on the stream the update runs on, every 5th update by default
-    c->bound_updates = 0; c->bound_timed = 0; c->bound_ms = 0.f;
-    bool bound_open = false;
-    auto bound_begin = [&](hipStream_t st) {
-        (void)span_close();
+    void bound_begin(hipStream_t st) {
+        (void)close();
         bound_open = c->time_kernels == 2 || (c->time_kernels == 1 && c->bound_updates % 5 == 2);
         c->bound_updates++;
         if (!bound_open) return;
         while ((int)c->bev.size() < 2 * c->bound_timed + 2) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { bound_open = false; return; } c->bev.push_back(e); }
         (void)hipEventRecord(c->bev[2 * c->bound_timed], st);
-    };
-    auto bound_end = [&](hipStream_t st) {
+    }
+    void bound_end(hipStream_t st) {
         if (!bound_open) return;
         (void)hipEventRecord(c->bev[2 * c->bound_timed + 1], st);
         c->bound_timed++;
         bound_open = false;
-    };
-    const bool ov_trying = c->zone_mode && !c->band_mode && !c->ov_fixed && c->ksub == 0 && nsub == c->p.ndte;
-    if (ov_trying) c->overlap = (c->ov_trial != 2);
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (c->eap && c->ksub == 0) hipLaunchKernelGGL(k_eap_reset, grid2d(s, B2D), B2D, 0, c->stream, s, c->E);   // ice_dyn_eap.F90:171-180, :284-298
-    c->double_launches = 0;
-    c->triple_launches = 0;
-    c->xb_swaps = 0;
-    c->zone_exchanges = 0;
-    c->zone_bytes = 0;
+    }
+    // after the loop's last event has completed: the sampled times scaled to all updates / all launches of a kind
+    int reduce() {
+        if (c->bound_timed) {
+            double sum = 0.0;
+            for (int k = 0; k < c->bound_timed; k++) {
+                float ms = 0.f;
+                HIPCHK(c, hipEventElapsedTime(&ms, c->bev[2 * k], c->bev[2 * k + 1]));
+                sum += ms;
+            }
+            c->bound_ms = (float)(sum / c->bound_timed * c->bound_updates);
+        }
+        if (c->time_kernels) {
+            // per kind: time of its spans / launches inside them, scaled to all launches of that kind
+            double sum[4] = {0, 0, 0, 0};
+            int cnt[4] = {0, 0, 0, 0};
+            for (int k = 0; k < c->nkev; k++) {
+                float ms = 0.f;
+                HIPCHK(c, hipEventElapsedTime(&ms, c->kev[2 * k], c->kev[2 * k + 1]));
+                sum[c->kev_kind[k]] += ms; cnt[c->kev_kind[k]] += c->kev_count[k];
+            }
+            const int n1 = c->kernel_launches - c->double_launches - c->triple_launches;
+            if (cnt[1]) c->kernel_ms = (float)(sum[1] / cnt[1] * n1);
+            if (cnt[2]) c->kernel2_ms = (float)(sum[2] / cnt[2] * c->double_launches);
+            if (cnt[3]) c->kernel3_ms = (float)(sum[3] / cnt[3] * c->triple_launches);
+            c->kernel_timed = cnt[1]; c->kernel2_timed = cnt[2]; c->kernel3_timed = cnt[3];
+        }
+        return 0;
+    }
+};
+
+// ---- the subcycle loop: what its steps share during one call -------------------------------------------------------------------
+struct SubLoop {
+    evpk_ctx *c;
+    LoopTimer t;
+    int nsub, n = 0;            // subcycles of this call, of which done
+    bool wrap, need_halo, revp;
+    int G;                      // ghost-zone columns beyond the halo column the pair kernels compute (x-slabs)
     bool pendingI = false;      // an interior launch on stream2 that `stream` has not waited for yet
     bool evE_valid = false;     // evE marks the latest kernel launch on `stream`
-    const int G = c->zone_mode ? c->zW - 2 : 0;
-    auto join = [&]() -> int {  // `stream` continues after the interior strips on stream2
+
+    int join() {                // `stream` continues after the interior strips on stream2
         if (!pendingI) return 0;
         pendingI = false;
-        return hipStreamWaitEvent(c->stream, c->evI, 0) != hipSuccess;
-    };
+        if (hipStreamWaitEvent(c->stream, c->evI, 0) != hipSuccess) FAIL(c, "hipStreamWaitEvent failed");
+        return 0;
+    }
     // refresh the ghost zones of state buffer `SBUF` from the neighbours (it must hold the current state)
     // with_mirror (x-slab ranks on a tripole grid, another pair follows): the refresh of the mirror slab travels in the same round --
     // both exchanges are posted before either is waited for (peer-mapped: the mirror messages on the second channel, whose pages and
     // counters the zone messages do not touch; RCCL: one group), so that a pair of ranks meets once per refresh instead of twice
-    auto zone_exchange = [&](int SBUF, bool with_mirror = false) -> int {
-        bound_begin(c->stream);
+    int zone_exchange(int SBUF, bool with_mirror = false) {
+        Slab &s = c->s;
+        t.bound_begin(c->stream);
         if (with_mirror && c->xband && c->xb_merge && !c->relay) {
             XbXchg X;
             ColsXchg Q;
@@ -2633,7 +2675,7 @@ static int subcycle_impl(evpk_ctx *c, int32_t nsub) {
             if (exchange_cols(c, state_pairs(SBUF), c->zcompact)) return 1;
             with_mirror = false;
         }
-        bound_end(c->stream);
+        t.bound_end(c->stream);
         c->zone_exchanges++;
         c->zone_bytes += (long long)(NSTATE / 2) * c->zW * 16 *
                          ((c->west >= 0 ? (c->zcompact ? c->zn[0] : s.nyl + 2) : 0) + (c->east >= 0 ? (c->zcompact ? c->zn[1] : s.nyl + 2) : 0));
@@ -2641,266 +2683,313 @@ static int subcycle_impl(evpk_ctx *c, int32_t nsub) {
         c->inner_ok = true;
         c->m_need = with_mirror ? 0 : 1;              // (x-slab tripole: the mirror slab is due as well)
         return 0;
-    };
-    for (int n = 0; n < nsub;) {
+    }
+};
+
+// EVPK_DEBUG_CLOCKS=<file>: the timeline of the loop's sixth launch (per strip: start / end clock of its wave, where it ran)
+static int dbg_clocks_arm(evpk_ctx *c, SubArgs &a) {
+    if (!(c->dbg_file && c->kernel_launches == 5 && c->evp_count == 3)) return 0;
+    if (!c->d_dbg) { HIPCHK(c, hipMalloc(&c->d_dbg, sizeof(unsigned long long) * 4 * 65536)); }
+    HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, sizeof(unsigned long long) * 4 * 65536, c->stream));
+    hipLaunchKernelGGL(k_dbg_clock, dim3(1), dim3(64), 0, c->stream, c->d_dbg + 4 * 65535);      // the stream's clock just before the launch
+    a.dbg = c->d_dbg;
+    return 0;
+}
+
+static int dbg_clocks_dump(evpk_ctx *c) {
+    if (!(c->dbg_file && c->d_dbg && c->evp_count == 3)) return 0;
+    std::vector<unsigned long long> h((size_t)4 * 65536);
+    hipLaunchKernelGGL(k_dbg_clock, dim3(1), dim3(64), 0, c->stream, c->d_dbg + 4 * 65535 + 1);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    if (FILE *fp = fopen(c->dbg_file, "w")) {
+        fprintf(fp, "# t0 %llu\n", h[(size_t)4 * 65535]);
+        for (int k = 0; k < 65535; k++) if (h[(size_t)4 * k]) fprintf(fp, "%d %llu %llu %llx\n", k, h[(size_t)4 * k], h[(size_t)4 * k + 1], h[(size_t)4 * k + 2]);
+        fclose(fp);
+    }
+    return 0;
+}
+
+// three subcycles in one launch (k_subcycle3w)
+static int step_triple(SubLoop &L, SubArgs &a) {
+    evpk_ctx *c = L.c;
+    a.strips = c->d_strips3; a.nstrips = c->ns_tot3_cur; a.nsdev = c->d_ns3; a.ncx = c->ncx3; a.R = c->R3; a.G = 0;
+    a.wrap = (c->ew == EVPK_BND_CYCLIC) ? 1 : 0;
+    if (L.join()) return 1;
+    if (L.t.begin(c->stream, 3)) return 1;
+    launch_sub3(c, a, c->stream, L.revp);
+    if (L.t.end()) return 1;
+    c->kernel_launches++;
+    c->triple_launches++;
+    L.evE_valid = false;
+    c->ksub += 3;
+    L.n += 3;
+    c->cur ^= 1;
+    return 0;
+}
+
+// ---- the tripole band of a pair: rows next to the fold are redone one subcycle at a time with the fold in between ------------------
+//   band 1: T rows nyl-2..nyl+1, U rows nyl-2..nyl   state `sr` -> scratch;  fold(scratch)
+//   band 2: T rows nyl-1..nyl+1, U rows nyl-1..nyl   scratch -> state `sw`;  fold(sw)
+// The main launch leaves rows >= nyl-1 to the bands (jmax).  Three ways, each fills in its part of the main launch's arguments:
+
+// tripole on ONE rank: the top band of a pair runs as extra workgroups of the pair's own launch (band_pair: a strip
+// and its mirror image in one workgroup, the fold between the subcycles in its LDS) -- no band launches, no second
+// stream, no hand-overs; EVPK_BAND_FUSED=0 brings the launches on stream2 back
+static void band_fused(const SubLoop &L, SubArgs &a) {
+    const Slab &s = L.c->s;
+    a.nband = (s.nxl / 2 + 1 + 60) / 61;          // strips A cover columns 0 .. nx/2, their mirror images the rest
+    a.jmax = s.nyl - 2;
+}
+
+// x-slab ranks: strip A of every band workgroup is mine, strip B the mirror rank's, read from the mirror slab M.
+// M comes whole after a ghost-zone exchange or a one-subcycle launch (one message, m_need); between two such
+// refreshes its rows below the band are advanced HERE by the pair kernel over M's own strips (two rows of
+// validity less per pair, see evpk_connect) and the band rows by band_pair, on both ranks alike
+static int band_xslab(SubLoop &L, SubArgs &a, bool pair_ends_evp) {
+    evpk_ctx *c = L.c;
+    Slab &s = c->s;
+    if (L.join()) return 1;
+    if (c->m_need) {
+        L.t.bound_begin(c->stream);
+        if (xband_state(c, a.sr, c->stream)) return 1;
+        L.t.bound_end(c->stream);
+        c->xb_swaps++;
+        c->m_need = 0;
+    }
+    // (cells no lane stores are alike in both state buffers: M's write buffer starts from its read buffer)
+    hipLaunchKernelGGL(k_xband_rows_copy, dim3((s.nxl + 2 * ZW_MAX + 127) / 128, c->m.nyl + 2), dim3(128), 0, c->stream, c->m, a.sr, a.sw,
+                       (int)NSTATE, 0, c->m.nyl + 1);
+    if (c->zone_left > 1 && !pair_ends_evp) {      // another pair follows before the next refresh
+        if (c->ms_R != c->R2 || c->ms_ncx != c->ncx2) {
+            const int nry = (c->m.nyl + c->R2 - 1) / c->R2;
+            std::vector<int> ms((size_t)c->ncx2 * nry);
+            for (int k = 0; k < (int)ms.size(); k++) ms[k] = k;
+            if (c->d_mstrips) (void)hipFree(c->d_mstrips);
+            c->d_mstrips = nullptr;
+            HIPCHK(c, hipMalloc(&c->d_mstrips, sizeof(int) * ms.size()));
+            HIPCHK(c, hipMemcpy(c->d_mstrips, ms.data(), sizeof(int) * ms.size(), hipMemcpyHostToDevice));
+            c->ms_R = c->R2; c->ms_ncx = c->ncx2; c->ms_n = (int)ms.size();
+        }
+        SubArgs bm = a;
+        bm.s = c->m; bm.strips = c->d_mstrips; bm.nstrips = c->ms_n; bm.nsdev = nullptr; bm.jmax = c->m.nyl - 2;
+        // M's advance writes M's rows below the band, the band workgroups of the main launch the rows above, both read
+        // the other state buffer: the advance runs as workgroups OF the main launch (SubArgs::nmir) -- a launch of its
+        // own, seven to nine rows of dependent marching, took as long as the main launch of a narrow slab and sat in
+        // front of every pair (round 4, xp_compare: 52 us per pair; on stream2 beside the main launch the two event
+        // hand-overs cost more than that: 29.5 against 24.4 ms per evp, rejected).  EVPK_XB_FUSE=0: the launch of its own
+        if (c->xb_fuse) { a.nmir = c->ms_n; a.mjmax = c->m.nyl - 2; }
+        else launch_sub2(c, bm, c->stream, L.revp, false);
+    }
+    a.xm = c->d_mslab;
+    a.nband = (s.nxl + 2 * L.G + 60) / 61;
+    a.jmax = s.nyl - 2;
+    return 0;
+}
+
+// band launches (k_subcycle_t) on stream2, beside the main launch: nothing the band sequence -- band 1, fold, band 2,
+// fold -- reads or writes is touched by it (single rank: the main launch writes its own E-W ghost images;
+// x-slabs: those come with the ghost-zone exchange after both).  `stream` takes over again after the main launch (step_pair).
+static int band_stream2(SubLoop &L, SubArgs &a, bool pair_ends_evp) {
+    evpk_ctx *c = L.c;
+    Slab &s = c->s;
+    SubArgs b1 = a;
+    b1.strips = c->d_band; b1.nstrips = c->ncx; b1.ncx = c->ncx; b1.wrap = L.wrap ? 1 : 0; b1.G = 0;
+    b1.R = 4; b1.jb0 = s.nyl - 2; b1.sw = F_STATE2;
+    SubArgs b2 = b1;
+    b2.R = 3; b2.jb0 = s.nyl - 1; b2.sr = F_STATE2; b2.sw = a.sw;
+    if (c->handover_value) {
+        c->sig_seq++;
+        HIPCHK(c, hipStreamWriteValue32(c->stream, c->sigB, c->sig_seq, 0));
+        HIPCHK(c, hipStreamWaitValue32(c->stream2, c->sigB, c->sig_seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    } else {
+        HIPCHK(c, hipEventRecord(c->evB0, c->stream));          // the previous pair (and its exchange) is complete
+        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evB0, 0));
+    }
+    launch_sub1t(b1, c->stream2, L.revp, false);
+    L.t.bound_begin(c->stream2);
+    if (halo(c, F_STATE2 + S_U, 2, true, true, 0.0, -1, c->stream2, false, a.sr + S_U)) return 1;
+    L.t.bound_end(c->stream2);
+    launch_sub1t(b2, c->stream2, L.revp, pair_ends_evp);
+    L.t.bound_begin(c->stream2);
+    // (x-slabs: the ghost-zone exchange after the pair delivers the E-W ghost columns of the new state, all rows)
+    if (halo(c, a.sw + S_U, 2, true, true, 0.0, -1, c->stream2, c->zone_mode, F_STATE2 + S_U, s.nyl - 1)) return 1;
+    L.t.bound_end(c->stream2);
+    if (c->handover_value) HIPCHK(c, hipStreamWriteValue32(c->stream2, c->sigB1, c->sig_seq, 0));
+    else HIPCHK(c, hipEventRecord(c->evB1, c->stream2));
+    a.jmax = s.nyl - 2;
+    return 0;
+}
+
+// the main launch of a pair.  split (x-slabs): the launch that uses up the zones runs its edge strips first on `stream`, followed by
+// the exchange of the edge columns there, while the interior strips run on `stream2`
+static int pair_launch(SubLoop &L, SubArgs &a, bool split, bool pair_ends_evp) {
+    evpk_ctx *c = L.c;
+    if (L.join()) return 1;
+    if (!split) {
+        if (c->nstrips2 > 0) {
+            if (L.t.begin(c->stream, 2)) return 1;
+            launch_sub2(c, a, c->stream, L.revp, pair_ends_evp);
+            if (L.t.end()) return 1;
+            c->kernel_launches++;
+            c->double_launches++;
+        }
+        L.evE_valid = false;
+        return 0;
+    }
+    // edge(k) reads everything round k-1 wrote near the edges: interior(k-1) on stream2 (joined above), the exchange on stream
+    if (!L.evE_valid) HIPCHK(c, hipEventRecord(c->evE, c->stream));      // round k-1 was a plain launch on `stream`
+    a.strips = c->d_strips2e; a.nstrips = c->nstrips2e;
+    launch_sub2(c, a, c->stream, L.revp, false);
+    // interior(k) needs round k-1's kernels, not its exchange: it reads no ghost zone
+    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evE, 0));
+    a.strips = c->d_strips2i; a.nstrips = c->nstrips2i;
+    if (L.t.begin(c->stream2, 2)) return 1;
+    launch_sub2(c, a, c->stream2, L.revp, false);
+    if (L.t.end()) return 1;
+    if (L.t.close()) return 1;      // (the other stream's work follows)
+    c->kernel_launches++;
+    c->double_launches++;
+    HIPCHK(c, hipEventRecord(c->evI, c->stream2));
+    L.pendingI = true;
+    HIPCHK(c, hipEventRecord(c->evE, c->stream));
+    L.evE_valid = true;
+    return 0;
+}
+
+// two subcycles in one launch; pair_ends_evp: the second is the last of this evp (else another subcycle follows it: "pair_inside")
+static int step_pair(SubLoop &L, SubArgs &a, bool fused_band, bool xb, bool pair_ends_evp) {
+    evpk_ctx *c = L.c;
+    a.strips = c->d_strips2; a.nstrips = c->dev_strips ? c->ns_tot2_cur : c->nstrips2; a.ncx = c->ncx2; a.R = c->R2; a.G = L.G;
+    a.nsdev = c->dev_strips ? c->d_ns2 : nullptr;
+    a.wrap = (c->ew == EVPK_BND_CYCLIC && !c->zone_mode) ? 1 : 0;      // in-kernel cyclic wrap, or ghost-zone mode
+    if (c->zone_mode && c->zone_left < 1) {         // (a one-subcycle launch or a partial call came before)
+        if (L.join()) return 1;
+        if (L.zone_exchange(a.sr)) return 1;
+    }
+    const bool band2 = c->band_mode && !fused_band && !xb;
+    if (fused_band) band_fused(L, a);
+    else if (xb) { if (band_xslab(L, a, pair_ends_evp)) return 1; }
+    else if (band2) { if (band_stream2(L, a, pair_ends_evp)) return 1; }
+    const bool split = c->zone_mode && c->overlap && !c->band_mode && !pair_ends_evp && c->zone_left == 1 &&
+                       c->nstrips2e > 0 && c->nstrips2i > 0;
+    if (pair_launch(L, a, split, pair_ends_evp)) return 1;
+    if (band2 && c->handover_value) HIPCHK(c, hipStreamWaitValue32(c->stream, c->sigB1, c->sig_seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    else if (band2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evB1, 0));
+    c->ksub += 2;
+    L.n += 2;
+    c->cur ^= 1;
+    if (c->zone_mode) {
+        c->zone_left--;
+        c->inner_ok = c->zone_left >= 1;
+        // the zones are used up (in a split round this overlaps the interior strips), or the evp is complete
+        if (c->zone_left < 1 || pair_ends_evp) {
+            if (!split && L.join()) return 1;
+            if (L.zone_exchange(c->cur ? F_STATE1 : F_STATE0, !pair_ends_evp && L.nsub - L.n >= 2 && c->p.ndte - c->ksub >= 2)) return 1;
+        }
+    }
+    return 0;
+}
+
+// one subcycle: eap (stress_eap + stepu in one launch), one row per wave on a small slab, else marching; then the velocity halo
+static int step_single(SubLoop &L, SubArgs &a) {
+    evpk_ctx *c = L.c;
+    Slab &s = c->s;
+    if (L.join()) return 1;
+    if (c->zone_mode && !c->inner_ok && L.zone_exchange(a.sr)) return 1;
+    if (strips1(c)) return 1;
+    c->ksub++;
+    L.n++;
+    a.strips = c->d_strips; a.nstrips = c->nstrips; a.ncx = c->ncx; a.wrap = L.wrap ? 1 : 0;
+    a.R = c->R;                     // (strips1 may have re-tuned it: tune_R1)
+    const bool last = (c->ksub == c->p.ndte);
+    if (c->nstrips > 0) {
+        // small slab: one row per wave (k_subcycle_t) instead of R + 1 march steps per wave
+        const bool t1 = c->R <= 7 && (long long)c->nstrips * (c->R + 1) <= 8LL * c->nsimd && c->tile_force != 0;
+        if (L.t.begin(c->stream, 1)) return 1;
+        if (c->eap) {       // eap(dt): stress_eap + stepu in one launch (k_eap_sub), stepa every tenth subcycle (ice_dyn_eap.F90:345-447)
+            EapSubArgs x{c->E, (last || L.n == L.nsub) ? 1 : 0};
+            with_bool(last, [&](auto LAST) {
+                hipLaunchKernelGGL(k_eap_sub<decltype(LAST)::value>, dim3(xcd_round((c->nstrips + 3) / 4)), dim3(256), 0, c->stream, a, x);
+            });
+            // (round 5: stepa INSIDE this launch -- the angle planes double buffered, the twelve stepa subcycles as a kernel of their own
+            //  at three waves per SIMD -- was built, is bit-exact and measured SLOWER: 42.1-43.0 ms per eap against 41.2-41.3,
+            //  profiles/r05_v1/eap_stepa_ab.txt; the launch of its own stays)
+            if (c->ksub % 10 == 1) {                                                    // :411-426
+                const double dtei = 1.0 / (c->p.dt / (double)c->p.ndte);              // ice_dyn_shared.F90:209-210
+                hipLaunchKernelGGL(k_eap_stepa, dim3((s.nxl + 1 + 63) / 64, (s.nyl + 1 + 3) / 4), B2D, 0, c->stream, s, c->E, a.sw, dtei);
+            }
+        }
+        else if (t1) launch_sub1t(a, c->stream, L.revp, last);
+        else launch_sub1(a, c->stream, L.revp, last);
+        if (L.t.end()) return 1;
+        c->kernel_launches++;
+    }
+    L.evE_valid = false;
+    c->cur ^= 1;
+    if (L.need_halo) {                                                          // ice_dyn_evp.F90:392-400
+        L.t.bound_begin(c->stream);
+        if (halo(c, (c->cur ? F_STATE1 : F_STATE0) + S_U, 2, true, true, 0.0, -1, nullptr, false, a.sr + S_U)) return 1;
+        L.t.bound_end(c->stream);
+    }
+    if (c->zone_mode) { c->zone_left = 0; c->inner_ok = true; }     // one ghost column is current, the deeper zone is not
+    c->m_need = 1;
+    return 0;
+}
+
+static int subcycle_impl(evpk_ctx *c, int32_t nsub) {
+    if (!c->prepped) FAIL(c, "evpk_prep has not been called");
+    if (nsub < 0) FAIL(c, "nsub < 0");
+    Slab &s = c->s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->eap) {       // EVPK_EAP_FUSED=0: stress_eap and stepu as two launches with str(8) through memory, in place
+        const char *e = getenv("EVPK_EAP_FUSED");
+        if (e && atoi(e) == 0) return eap_subcycle(c, nsub);
+    }
+    SubLoop L{c, LoopTimer{c}, nsub};
+    L.wrap = (c->nranks == 1 && c->ew == EVPK_BND_CYCLIC && !c->force_exchange);
+    L.need_halo = (c->nranks > 1) || (c->ns == EVPK_BND_TRIPOLE) || c->force_exchange;
+    L.revp = (c->p.revp == 1.0);
+    L.G = c->zone_mode ? c->zW - 2 : 0;
+    reset_call_counters(c);
+    if (L.t.start(nsub)) return 1;
+    const bool ov_trying = c->zone_mode && !c->band_mode && !c->ov_fixed && c->ksub == 0 && nsub == c->p.ndte;
+    if (ov_trying) c->overlap = (c->ov_trial != 2);
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (c->eap && c->ksub == 0) hipLaunchKernelGGL(k_eap_reset, grid2d(s, B2D), B2D, 0, c->stream, s, c->E);   // ice_dyn_eap.F90:171-180, :284-298
+    while (L.n < nsub) {
         SubArgs a;
         a.s = s; a.ecci = c->p.ecci; a.arlx1i = c->p.arlx1i; a.denom1 = c->p.denom1; a.brlx = c->p.brlx;
         a.revp = c->p.revp; a.cosw = c->p.cosw; a.sinw = c->p.sinw;
-        a.R = c->R; a.jb0 = 0; a.G = 0; a.jmax = 1 << 30; a.nband = 0; a.nmir = 0; a.mjmax = 0; a.nsdev = nullptr; a.xm = nullptr; a.dbg = nullptr; a.prio = c->prio; a.band_last = c->band_last;      // (band_last: switched off below for the tile kernels)
+        a.R = c->R; a.jb0 = 0; a.G = 0; a.jmax = 1 << 30; a.nband = 0; a.nmir = 0; a.mjmax = 0; a.nsdev = nullptr; a.xm = nullptr; a.dbg = nullptr; a.prio = c->prio; a.band_last = c->band_last;      // (band_last: switched off in launch_sub2 for the tile kernels)
         a.sr = c->cur ? F_STATE1 : F_STATE0; a.sw = c->cur ? F_STATE0 : F_STATE1;
-        const bool revp = (c->p.revp == 1.0);
+        const int left = nsub - L.n;
         // two subcycles in one launch when neither of them is the last one of this evp (ksub == ndte writes diagnostics) ...
         // (a small slab on a one-rank tripole grid: the band sequence of a pair -- two band launches, two folds, two hand-overs
         // between the streams, ~35 us -- costs more than two one-row-per-wave launches with their folds on one stream: 2.4 ms
         // against 1.9 per evp at 360x300, even at 720x540, measured again with the stream-memory hand-overs)
-        // tripole on ONE rank: the top band of a pair runs as extra workgroups of the pair's own launch (band_pair: a strip
-        // and its mirror image in one workgroup, the fold between the subcycles in its LDS) -- no band launches, no second
-        // stream, no hand-overs; EVPK_BAND_FUSED=0 brings the launches on stream2 back
-        const bool fused_band = c->band_mode && c->band_fused && wrap && (c->prefetch || c->tile_mode) && s.nyl >= 4;
+        const bool fused_band = c->band_mode && c->band_fused && L.wrap && (c->prefetch || c->tile_mode) && s.nyl >= 4;      // see band_fused
         const bool xb = c->xband && !fused_band;
         const bool pairs = c->use_double && !c->eap && (fused_band || !(c->band_mode && c->tile_mode && c->nranks == 1 && !c->force_exchange));
-        const bool pair_inside = pairs && nsub - n >= 2 && c->ksub + 2 < c->p.ndte;
+        const bool pair_inside = pairs && left >= 2 && c->ksub + 2 < c->p.ndte;
         // ... or when the second of them is the last one (k_subcycle2<.., LAST2>; tripole: the second band launch is then
         // the LAST variant of k_subcycle)
-        const bool pair_ends_evp = pairs && nsub - n >= 2 && (c->ksub + 2 == c->p.ndte);
-        // EVPK_DEBUG_CLOCKS=<file>: the timeline of the loop's sixth launch (per strip: start / end clock of its wave, where it ran)
-        const bool dbg_now = c->dbg_file && c->kernel_launches == 5 && c->evp_count == 3;
-        if (dbg_now) {
-            if (!c->d_dbg) { HIPCHK(c, hipMalloc(&c->d_dbg, sizeof(unsigned long long) * 4 * 65536)); }
-            HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, sizeof(unsigned long long) * 4 * 65536, c->stream));
-            hipLaunchKernelGGL(k_dbg_clock, dim3(1), dim3(64), 0, c->stream, c->d_dbg + 4 * 65535);      // the stream's clock just before the launch
-            a.dbg = c->d_dbg;
-        }
+        const bool pair_ends_evp = pairs && left >= 2 && (c->ksub + 2 == c->p.ndte);
+        if (dbg_clocks_arm(c, a)) return 1;
         // three subcycles in one launch (k_subcycle3w) while at least one more follows in this evp: the evp then ends with the pair /
         // single launches below, which write the diagnostics of the last subcycle
-        if (c->use_triple && nsub - n >= 3 && c->ksub + 3 < c->p.ndte) {
-            a.strips = c->d_strips3; a.nstrips = c->ns_tot3_cur; a.nsdev = c->d_ns3; a.ncx = c->ncx3; a.R = c->R3; a.G = 0;
-            a.wrap = (c->ew == EVPK_BND_CYCLIC) ? 1 : 0;
-            if (join()) FAIL(c, "hipStreamWaitEvent failed");
-            if (ev_begin(c->stream, 3)) FAIL(c, "hipEventRecord failed");
-            launch_sub3(c, a, c->stream, revp);
-            if (ev_end(c->stream)) FAIL(c, "hipEventRecord failed");
-            c->kernel_launches++;
-            c->triple_launches++;
-            evE_valid = false;
-            c->ksub += 3;
-            n += 3;
-            c->cur ^= 1;
-            continue;
-        }
-        if (pair_inside || pair_ends_evp) {
-            a.strips = c->d_strips2; a.nstrips = c->dev_strips ? c->ns_tot2_cur : c->nstrips2; a.ncx = c->ncx2; a.R = c->R2; a.G = G;
-            a.nsdev = c->dev_strips ? c->d_ns2 : nullptr;
-            a.wrap = (c->ew == EVPK_BND_CYCLIC && !c->zone_mode) ? 1 : 0;      // in-kernel cyclic wrap, or ghost-zone mode
-            // tripole: rows next to the fold are redone one subcycle at a time with the fold in between
-            //   band 1: T rows nyl-2..nyl+1, U rows nyl-2..nyl   state `sr` -> scratch;  fold(scratch)
-            //   band 2: T rows nyl-1..nyl+1, U rows nyl-1..nyl   scratch -> state `sw`;  fold(sw)
-            // The main launch leaves rows >= nyl-1 to the bands (jmax), and nothing the band sequence -- band 1, fold, band 2,
-            // fold -- reads or writes is touched by it (single rank: the main launch writes its own E-W ghost images;
-            // x-slabs: those come with the ghost-zone exchange after both), so the sequence runs beside it on stream2.
-            if (c->zone_mode && c->zone_left < 1) {         // (a one-subcycle launch or a partial call came before)
-                if (join()) FAIL(c, "hipStreamWaitEvent failed");
-                if (zone_exchange(a.sr)) return 1;
-            }
-            SubArgs b1 = a, b2 = a;
-            // (band launches: k_subcycle_t, one row per wave -- the band sequence is on the critical path of every pair)
-            auto launch_band = [&](const SubArgs &bb, hipStream_t st, bool last = false) {
-                const dim3 g(bb.nstrips), b((bb.R + 1) * 64);
-                const size_t lds = (size_t)(bb.R + 1) * 2048;
-                if (last && revp) hipLaunchKernelGGL((k_subcycle_t<true, true>), g, b, lds, st, bb);
-                else if (last) hipLaunchKernelGGL((k_subcycle_t<true, false>), g, b, lds, st, bb);
-                else if (revp) hipLaunchKernelGGL((k_subcycle_t<false, true>), g, b, lds, st, bb);
-                else hipLaunchKernelGGL((k_subcycle_t<false, false>), g, b, lds, st, bb);
-            };
-            if (fused_band) {
-                a.nband = (s.nxl / 2 + 1 + 60) / 61;          // strips A cover columns 0 .. nx/2, their mirror images the rest
-                a.jmax = s.nyl - 2;
-            } else if (xb) {
-                // x-slab ranks: strip A of every band workgroup is mine, strip B the mirror rank's, read from the mirror slab M.
-                // M comes whole after a ghost-zone exchange or a one-subcycle launch (one message, m_need); between two such
-                // refreshes its rows below the band are advanced HERE by the pair kernel over M's own strips (two rows of
-                // validity less per pair, see evpk_connect) and the band rows by band_pair, on both ranks alike
-                if (join()) FAIL(c, "hipStreamWaitEvent failed");
-                if (c->m_need) {
-                    bound_begin(c->stream);
-                    if (xband_state(c, a.sr, c->stream)) return 1;
-                    bound_end(c->stream);
-                    c->xb_swaps++;
-                    c->m_need = 0;
-                }
-                // (cells no lane stores are alike in both state buffers: M's write buffer starts from its read buffer)
-                hipLaunchKernelGGL(k_xband_rows_copy, dim3((s.nxl + 2 * ZW_MAX + 127) / 128, c->m.nyl + 2), dim3(128), 0, c->stream, c->m, a.sr, a.sw,
-                                   (int)NSTATE, 0, c->m.nyl + 1);
-                if (c->zone_left > 1 && !pair_ends_evp) {      // another pair follows before the next refresh
-                    if (c->ms_R != c->R2 || c->ms_ncx != c->ncx2) {
-                        const int nry = (c->m.nyl + c->R2 - 1) / c->R2;
-                        std::vector<int> ms((size_t)c->ncx2 * nry);
-                        for (int k = 0; k < (int)ms.size(); k++) ms[k] = k;
-                        if (c->d_mstrips) (void)hipFree(c->d_mstrips);
-                        c->d_mstrips = nullptr;
-                        HIPCHK(c, hipMalloc(&c->d_mstrips, sizeof(int) * ms.size()));
-                        HIPCHK(c, hipMemcpy(c->d_mstrips, ms.data(), sizeof(int) * ms.size(), hipMemcpyHostToDevice));
-                        c->ms_R = c->R2; c->ms_ncx = c->ncx2; c->ms_n = (int)ms.size();
-                    }
-                    SubArgs bm = a;
-                    bm.s = c->m; bm.strips = c->d_mstrips; bm.nstrips = c->ms_n; bm.nsdev = nullptr; bm.jmax = c->m.nyl - 2;
-                    // M's advance writes M's rows below the band, the band workgroups of the main launch the rows above, both read
-                    // the other state buffer: the advance runs as workgroups OF the main launch (SubArgs::nmir) -- a launch of its
-                    // own, seven to nine rows of dependent marching, took as long as the main launch of a narrow slab and sat in
-                    // front of every pair (round 4, xp_compare: 52 us per pair; on stream2 beside the main launch the two event
-                    // hand-overs cost more than that: 29.5 against 24.4 ms per evp, rejected).  EVPK_XB_FUSE=0: the launch of its own
-                    if (c->xb_fuse) { a.nmir = c->ms_n; a.mjmax = c->m.nyl - 2; }
-                    else launch_sub2(c, bm, c->stream, revp, false);
-                }
-                a.xm = c->d_mslab;
-                a.nband = (s.nxl + 2 * G + 60) / 61;
-                a.jmax = s.nyl - 2;
-            } else if (c->band_mode) {
-                b1.strips = c->d_band; b1.nstrips = c->ncx; b1.ncx = c->ncx; b1.wrap = wrap ? 1 : 0; b1.G = 0;
-                b1.R = 4; b1.jb0 = s.nyl - 2; b1.sw = F_STATE2;
-                b2 = b1;
-                b2.R = 3; b2.jb0 = s.nyl - 1; b2.sr = F_STATE2; b2.sw = a.sw;
-                if (c->handover_value) {
-                    c->sig_seq++;
-                    HIPCHK(c, hipStreamWriteValue32(c->stream, c->sigB, c->sig_seq, 0));
-                    HIPCHK(c, hipStreamWaitValue32(c->stream2, c->sigB, c->sig_seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
-                } else {
-                HIPCHK(c, hipEventRecord(c->evB0, c->stream));          // the previous pair (and its exchange) is complete
-                HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evB0, 0));
-                }
-                launch_band(b1, c->stream2);
-                bound_begin(c->stream2);
-                if (halo(c, F_STATE2 + S_U, 2, true, true, 0.0, -1, c->stream2, false, a.sr + S_U)) return 1;
-                bound_end(c->stream2);
-                launch_band(b2, c->stream2, pair_ends_evp);
-                bound_begin(c->stream2);
-                // (x-slabs: the ghost-zone exchange after the pair delivers the E-W ghost columns of the new state, all rows)
-                if (halo(c, a.sw + S_U, 2, true, true, 0.0, -1, c->stream2, c->zone_mode, F_STATE2 + S_U, s.nyl - 1)) return 1;
-                bound_end(c->stream2);
-                if (c->handover_value) HIPCHK(c, hipStreamWriteValue32(c->stream2, c->sigB1, c->sig_seq, 0));
-                else HIPCHK(c, hipEventRecord(c->evB1, c->stream2));
-                a.jmax = s.nyl - 2;
-            }
-            // x-slabs: the launch that uses up the zones runs its edge strips first on `stream`, followed by the exchange
-            // of the edge columns there, while the interior strips run on `stream2`
-            const bool split = c->zone_mode && c->overlap && !c->band_mode && pair_inside && c->zone_left == 1 &&
-                               c->nstrips2e > 0 && c->nstrips2i > 0;
-            if (!split) {
-                if (join()) FAIL(c, "hipStreamWaitEvent failed");
-                if (c->nstrips2 > 0) {
-                    if (ev_begin(c->stream, 2)) FAIL(c, "hipEventRecord failed");
-                    launch_sub2(c, a, c->stream, revp, pair_ends_evp);
-                    if (ev_end(c->stream)) FAIL(c, "hipEventRecord failed");
-                    c->kernel_launches++;
-                    c->double_launches++;
-                }
-                evE_valid = false;
-            } else {
-                // edge(k) reads everything round k-1 wrote near the edges: interior(k-1) on stream2, the exchange on stream
-                if (join()) FAIL(c, "hipStreamWaitEvent failed");
-                if (!evE_valid) HIPCHK(c, hipEventRecord(c->evE, c->stream));      // round k-1 was a plain launch on `stream`
-                a.strips = c->d_strips2e; a.nstrips = c->nstrips2e;
-                launch_sub2(c, a, c->stream, revp, false);
-                // interior(k) needs round k-1's kernels, not its exchange: it reads no ghost zone
-                HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evE, 0));
-                a.strips = c->d_strips2i; a.nstrips = c->nstrips2i;
-                if (ev_begin(c->stream2, 2)) FAIL(c, "hipEventRecord failed");
-                launch_sub2(c, a, c->stream2, revp, false);
-                if (ev_end(c->stream2)) FAIL(c, "hipEventRecord failed");
-                if (span_close()) FAIL(c, "hipEventRecord failed");      // (the other stream's work follows)
-                c->kernel_launches++;
-                c->double_launches++;
-                HIPCHK(c, hipEventRecord(c->evI, c->stream2));
-                pendingI = true;
-                HIPCHK(c, hipEventRecord(c->evE, c->stream));
-                evE_valid = true;
-            }
-            if (c->band_mode && !fused_band && !xb) {
-                if (c->handover_value) HIPCHK(c, hipStreamWaitValue32(c->stream, c->sigB1, c->sig_seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
-                else HIPCHK(c, hipStreamWaitEvent(c->stream, c->evB1, 0));
-            }
-            c->ksub += 2;
-            n += 2;
-            c->cur ^= 1;
-            if (c->zone_mode) {
-                c->zone_left--;
-                c->inner_ok = c->zone_left >= 1;
-                // the zones are used up (in a split round this overlaps the interior strips), or the evp is complete
-                if (c->zone_left < 1 || pair_ends_evp) {
-                    if (!split && join()) FAIL(c, "hipStreamWaitEvent failed");
-                    if (zone_exchange(c->cur ? F_STATE1 : F_STATE0, !pair_ends_evp && nsub - n >= 2 && c->p.ndte - c->ksub >= 2)) return 1;
-                }
-            }
-            continue;
-        }
-        if (join()) FAIL(c, "hipStreamWaitEvent failed");
-        if (c->zone_mode && !c->inner_ok && zone_exchange(a.sr)) return 1;
-        if (strips1(c)) return 1;
-        c->ksub++;
-        n++;
-        a.strips = c->d_strips; a.nstrips = c->nstrips; a.ncx = c->ncx; a.wrap = wrap ? 1 : 0;
-        a.R = c->R;                     // (strips1 may have re-tuned it: tune_R1)
-        const bool last = (c->ksub == c->p.ndte);
-        if (c->nstrips > 0) {
-            const dim3 g((((c->nstrips + 3) / 4 + 7) / 8) * 8), b(256);   // multiple of 8: see the XCD remap in k_subcycle
-            // small slab: one row per wave (k_subcycle_t) instead of R + 1 march steps per wave
-            const bool t1 = c->R <= 7 && (long long)c->nstrips * (c->R + 1) <= 8LL * c->nsimd && c->tile_force != 0;
-            const dim3 gt(c->nstrips), bt((c->R + 1) * 64);
-            const size_t lds = (size_t)(c->R + 1) * 2048;
-            if (ev_begin(c->stream, 1)) FAIL(c, "hipEventRecord failed");
-            if (c->eap) {       // eap(dt): stress_eap + stepu in one launch (k_eap_sub), stepa every tenth subcycle (ice_dyn_eap.F90:345-447)
-                EapSubArgs x{c->E, (last || n == nsub) ? 1 : 0};
-                if (last) hipLaunchKernelGGL(k_eap_sub<true>, g, b, 0, c->stream, a, x);
-                else hipLaunchKernelGGL(k_eap_sub<false>, g, b, 0, c->stream, a, x);
-                // (round 5: stepa INSIDE this launch -- the angle planes double buffered, the twelve stepa subcycles as a kernel of their own
-                //  at three waves per SIMD -- was built, is bit-exact and measured SLOWER: 42.1-43.0 ms per eap against 41.2-41.3,
-                //  profiles/r05_v1/eap_stepa_ab.txt; the launch of its own stays)
-                if (c->ksub % 10 == 1) {                                                    // :411-426
-                    const double dtei = 1.0 / (c->p.dt / (double)c->p.ndte);              // ice_dyn_shared.F90:209-210
-                    hipLaunchKernelGGL(k_eap_stepa, dim3((s.nxl + 1 + 63) / 64, (s.nyl + 1 + 3) / 4), B2D, 0, c->stream, s, c->E, a.sw, dtei);
-                }
-            }
-            else if (t1) {
-                if (last && revp) hipLaunchKernelGGL((k_subcycle_t<true, true>), gt, bt, lds, c->stream, a);
-                else if (last) hipLaunchKernelGGL((k_subcycle_t<true, false>), gt, bt, lds, c->stream, a);
-                else if (revp) hipLaunchKernelGGL((k_subcycle_t<false, true>), gt, bt, lds, c->stream, a);
-                else hipLaunchKernelGGL((k_subcycle_t<false, false>), gt, bt, lds, c->stream, a);
-            }
-            else if (last && revp) hipLaunchKernelGGL((k_subcycle<true, true>), g, b, 0, c->stream, a);
-            else if (last) hipLaunchKernelGGL((k_subcycle<true, false>), g, b, 0, c->stream, a);
-            else if (revp) hipLaunchKernelGGL((k_subcycle<false, true>), g, b, 0, c->stream, a);
-            else hipLaunchKernelGGL((k_subcycle<false, false>), g, b, 0, c->stream, a);
-            if (ev_end(c->stream)) FAIL(c, "hipEventRecord failed");
-            c->kernel_launches++;
-        }
-        evE_valid = false;
-        c->cur ^= 1;
-        if (need_halo) {                                                          // ice_dyn_evp.F90:392-400
-            bound_begin(c->stream);
-            if (halo(c, (c->cur ? F_STATE1 : F_STATE0) + S_U, 2, true, true, 0.0, -1, nullptr, false, a.sr + S_U)) return 1;
-            bound_end(c->stream);
-        }
-        if (c->zone_mode) { c->zone_left = 0; c->inner_ok = true; }     // one ghost column is current, the deeper zone is not
-        c->m_need = 1;
+        if (c->use_triple && left >= 3 && c->ksub + 3 < c->p.ndte) { if (step_triple(L, a)) return 1; }
+        else if (pair_inside || pair_ends_evp) { if (step_pair(L, a, fused_band, xb, pair_ends_evp)) return 1; }
+        else if (step_single(L, a)) return 1;
     }
-    if (span_close()) FAIL(c, "hipEventRecord failed");
-    if (join()) FAIL(c, "hipStreamWaitEvent failed");
+    if (L.t.close()) return 1;
+    if (L.join()) return 1;
     // leave the ghost columns 0 / nxl+1 of the state current (download, finish, a later one-subcycle launch)
-    if (c->zone_mode && !c->inner_ok && zone_exchange(c->cur ? F_STATE1 : F_STATE0)) return 1;
+    if (c->zone_mode && !c->inner_ok && L.zone_exchange(c->cur ? F_STATE1 : F_STATE0)) return 1;
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventSynchronize(c->ev1));
     HIPCHK(c, hipEventElapsedTime(&c->loop_ms, c->ev0, c->ev1));
-    if (c->dbg_file && c->d_dbg && c->evp_count == 3) {
-        std::vector<unsigned long long> h((size_t)4 * 65536);
-        hipLaunchKernelGGL(k_dbg_clock, dim3(1), dim3(64), 0, c->stream, c->d_dbg + 4 * 65535 + 1);
-        HIPCHK(c, hipMemcpy(h.data(), c->d_dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-        if (FILE *fp = fopen(c->dbg_file, "w")) {
-            fprintf(fp, "# t0 %llu\n", h[(size_t)4 * 65535]);
-            for (int k = 0; k < 65535; k++) if (h[(size_t)4 * k]) fprintf(fp, "%d %llu %llu %llx\n", k, h[(size_t)4 * k], h[(size_t)4 * k + 1], h[(size_t)4 * k + 2]);
-            fclose(fp);
-        }
-    }
+    if (dbg_clocks_dump(c)) return 1;
     if (c->dev_strips) take_counts(c);   // what evpk_prep left in flight has arrived with the loop's last event
     if (c->use_triple) c->nstrips3 = (int)(c->h_counts[3] & 0xffffffffull);
     if (xp_check(c)) return 1;
@@ -2908,31 +2997,7 @@ static int subcycle_impl(evpk_ctx *c, int32_t nsub) {
         if (c->ov_trial >= 1) c->ov_ms[c->ov_trial - 1] = c->loop_ms;
         if (++c->ov_trial == 3) { c->overlap = (c->ov_ms[0] <= c->ov_ms[1]); c->ov_fixed = true; }
     }
-    if (c->bound_timed) {
-        double sum = 0.0;
-        for (int k = 0; k < c->bound_timed; k++) {
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->bev[2 * k], c->bev[2 * k + 1]));
-            sum += ms;
-        }
-        c->bound_ms = (float)(sum / c->bound_timed * c->bound_updates);
-    }
-    if (c->time_kernels) {
-        // per kind: time of its spans / launches inside them, scaled to all launches of that kind
-        double sum[4] = {0, 0, 0, 0};
-        int cnt[4] = {0, 0, 0, 0};
-        for (int k = 0; k < c->nkev; k++) {
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->kev[2 * k], c->kev[2 * k + 1]));
-            sum[c->kev_kind[k]] += ms; cnt[c->kev_kind[k]] += c->kev_count[k];
-        }
-        const int n1 = c->kernel_launches - c->double_launches - c->triple_launches;
-        if (cnt[1]) c->kernel_ms = (float)(sum[1] / cnt[1] * n1);
-        if (cnt[2]) c->kernel2_ms = (float)(sum[2] / cnt[2] * c->double_launches);
-        if (cnt[3]) c->kernel3_ms = (float)(sum[3] / cnt[3] * c->triple_launches);
-        c->kernel_timed = cnt[1]; c->kernel2_timed = cnt[2]; c->kernel3_timed = cnt[3];
-    }
-    return 0;
+    return L.t.reduce();
 }
 
 extern "C" int evpk_subcycle(evpk_ctx *c, int32_t nsub) {
