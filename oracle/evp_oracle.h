@@ -7,10 +7,12 @@
  *
  * PARITY: pinned by the reference's OWN output for the halo updates (orc_halo_r8 / i4 / stress), ice_strength and the
  * block / distribution arithmetic -- those reference routines compile here unmodified (oracle/ref/Makefile) and their
- * outputs are the fixtures tests/golden/ref_*.npz (tests/test_ref_pins.py).  PARITY UNPINNED for stress, stepu, evp_prep1/2,
- * evp_finish, to_ugrid / to_tgrid, horizontal_remap and eap: their Fortran modules `use ice_grid`, which needs the netCDF
- * Fortran module (source/ice_grid.F90:144), absent from the image, and the reference ships no tests or golden vectors
- * (SURVEY.md S4).  For those this restatement is checked by decomposition invariance and analytic properties
+ * outputs are the fixtures tests/golden/ref_*.npz (tests/test_ref_pins.py).  Pinned the same way, by a slice of ice_dyn_shared /
+ * ice_dyn_evp cut out at build time (oracle/ref/Makefile `kernels`, tests/golden/ref_dyn_*.npz): orc_evp_prep1, orc_evp_prep2,
+ * orc_stress, orc_stepu, orc_evp_finish, orc_principal_stress, each alone and as the chain orc_evp runs.  PARITY UNPINNED for
+ * the call order inside evp() (written from it; the routine itself reaches ice_grid), to_ugrid / to_tgrid, horizontal_remap and
+ * eap: ice_grid needs the netCDF Fortran module (source/ice_grid.F90:144), absent from the image; the remap and EAP routines
+ * could be sliced like the dynamics and are not yet; the reference ships no tests or golden vectors.  For those this restatement is checked by decomposition invariance and analytic properties
  * (tests/test_oracle.py), and tests/golden/evp_*.npz hold ITS OWN outputs (regression pins, not reference vectors).
  *
  * Array convention: every field is a Fortran-ordered block array

@@ -2,7 +2,8 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py -- never by the cice5_amd product path.
-Parity: halo updates / ice_strength pinned by reference output (tests/golden/ref_*.npz), the rest UNPINNED (oracle/evp_oracle.h).
+Parity: halo updates, ice_strength, evp_prep1/2, stress, stepu, evp_finish pinned by reference output (tests/golden/ref_*.npz);
+to_ugrid / to_tgrid, remap and eap UNPINNED (oracle/evp_oracle.h).
 """
 from __future__ import annotations
 

@@ -193,6 +193,8 @@ def main():
         path = os.path.join(HERE, f"ref_{cfg}.npz")
         np.savez_compressed(path, **allout)
         print(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
+    from tests.golden import make_ref_kernels          # the slice fixtures ref_dyn_*.npz (evp_prep1 .. stress)
+    make_ref_kernels.main()
 
 
 if __name__ == "__main__":

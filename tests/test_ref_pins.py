@@ -248,3 +248,248 @@ def test_compute_tracers_equals_reference():
                               orc._p64(atr), orc._p64(a), orc._p64(v), orc._p64(sn), orc._p64(got))
         assert np.array_equal(got, want), (tag, np.argwhere(got != want)[:5])
         assert (want[0] == rv.TOCNFRZ).any() and np.abs(want).max() > 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The slice fixtures tests/golden/ref_dyn_*.npz (tests/golden/make_ref_kernels.py): the reference's own evp_prep1, evp_prep2,
+# stress, stepu, evp_finish and principal_stress, cut out of ice_dyn_shared / ice_dyn_evp at build time (oracle/ref/Makefile,
+# target `kernels`; driver oracle/ref/ref_kernels.F90).  Single-routine records pin each routine on one block; chain records
+# pin the whole call order of evp() on the whole grid with the reference's own halo updates in between.
+# NOT pinned: the T<->U averages to_ugrid / t2ugrid_vector / u2tgrid_vector (ice_grid cannot be built): aiu, umass, the U-grid
+# wind stress handed to the chain and the last average of strocnxT / strocnyT come from the restatement itself.
+import ctypes as ct
+
+SN = rv.STRESS_NAMES
+P_ = orc._p64
+
+
+class _Merged(dict):
+    files = property(lambda self: list(self))
+
+
+def load_dyn(cfg, case=None):
+    """the chain records of `case`, or (case None) the single-routine records of every variant"""
+    g = os.path.join(HERE, "golden")
+    if case is not None:
+        return np.load(os.path.join(g, f"ref_dyn_{cfg}.{case}.npz"))
+    out = _Merged()
+    for var in rv.BLOCK_VARIANTS:
+        with np.load(os.path.join(g, f"ref_dyn_{cfg}.{var}.npz")) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
+def _between(a, lo, hi):
+    return int(((a > lo) & (a < hi)).sum())
+
+
+def assert_block_coverage(cfg, z):
+    """the branches the single-routine records must reach, counted on the reference's outputs (and the inputs they belong to)"""
+    big = cfg == "g72x20_b72x20"
+    n10, n3 = (10, 3) if big else (2, 1)
+    for var in rv.BLOCK_VARIANTS:
+        q = rv.block_inputs(cfg, "full", var)
+        ilo, ihi, jlo, jhi = rv.BLOCK_RECORDS[cfg]["full"]
+        ph = np.zeros(q["aice"].shape, dtype=bool); ph[jlo - 1:jhi, ilo - 1:ihi] = True
+        pre = f"full/{var}"
+        tm, itm = z[f"{pre}/evp_prep1/tmass"], z[f"{pre}/evp_prep1/icetmask"]
+        assert (q["tmask"][ph] == 0).sum() >= n10 and (tm[q["tmask"] == 0] == 0).all()
+        assert (itm[ph] == 1).sum() >= n10 and (itm[ph] == 0).sum() >= n10
+        assert _between(tm, rv.M_MIN * (1 - 1e-8), rv.M_MIN) >= n3 and _between(tm, rv.M_MIN, rv.M_MIN * (1 + 1e-8)) >= n3
+        assert _between(q["aice"], rv.A_MIN * (1 - 1e-8), rv.A_MIN) >= n3 and _between(q["aice"], rv.A_MIN, rv.A_MIN * (1 + 1e-8)) >= n3
+        new, old = z[f"{pre}/evp_prep2/iceumask"] != 0, q["iceumask"] != 0
+        assert (new & ~old & ph).sum() >= n10 and (old & ~new & ph).sum() >= n10, (cfg, var)
+        for a, t in ((q["aiu"], rv.A_MIN), (q["umass"], rv.M_MIN)):
+            assert _between(a[ph], t * (1 - 1e-8), t) >= 1 and _between(a[ph], t, t * (1 + 1e-8)) >= 1
+        assert (q["umask"][ph] == 0).sum() >= n3
+        act = np.zeros(ph.shape, dtype=bool)
+        act[q["indxt"][1, :q["icellt"]] - 1, q["indxt"][0, :q["icellt"]] - 1] = True
+        prs = z[f"{pre}/stress/prs_sig"]
+        assert (act & (q["strength"] == 0)).sum() >= n10
+        assert (act & (q["strength"] > 0) & (prs == 0)).sum() >= n10 and (act & (prs > 0)).sum() >= n10, (cfg, var)
+        s1 = z[f"{pre}/principal_stress/sig1"]
+        assert (s1 == 1.0e30).sum() >= n10 and (s1 != 1.0e30).sum() >= n10
+    v = rv.BLOCK_VARIANTS
+    assert {(x["revised_evp"], x["tilt_from_slope"], x["ksub"] == x["ndte"]) for x in v.values()} == {(0, 0, False), (1, 1, True)}
+
+
+def assert_chain_coverage(cfg, case, d, f, z):
+    """the branches a chain record must reach, per case, on physical cells, from the reference's outputs"""
+    nmin = 200 if cfg == "g72x20_b72x20" else 60
+    ph = np.zeros(f["aice"].shape, dtype=bool)
+    for n, b in enumerate(d.local_blocks):
+        ph[n, b.jlo - 1:b.jhi, b.ilo - 1:b.ihi] = True
+    ew, ns, land, var = rv.DYN_CASES[case]
+    for ndte in rv.DYN_NDTE:
+        pre = f"ndte{ndte}"
+        itm, ium, tm = z[f"{pre}/icetmask"], z[f"{pre}/iceumask"] != 0, z[f"{pre}/tmass"]
+        assert (itm[ph] == 1).sum() >= nmin and ium[ph].sum() >= nmin, (cfg, case, int((itm[ph] == 1).sum()), int(ium[ph].sum()))
+        assert int(z[f"{pre}/icell"][:, 1].sum()) == ium[ph].sum()
+        if land != "none":
+            assert (f["tmask"][ph] == 0).sum() >= 6
+        if land != "none" or ns != "tripole":
+            assert (f["umask"][ph] == 0).sum() >= 6
+        old = f["iceumask"] != 0
+        assert (ium & ~old & ph).sum() >= 10 and (old & ~ium & ph).sum() >= 10
+        assert _between(tm[ph], rv.M_MIN * (1 - 1e-8), rv.M_MIN) >= 1 and _between(tm[ph], rv.M_MIN, rv.M_MIN * (1 + 1e-8)) >= 1
+        a = f["aice"][ph]
+        assert _between(a, rv.A_MIN * (1 - 1e-8), rv.A_MIN) >= 1 and _between(a, rv.A_MIN, rv.A_MIN * (1 + 1e-8)) >= 1
+        act = ph & (itm == 1)
+        assert (act & (f["strength"] == 0)).sum() >= 10
+        prs = z[f"{pre}/prs_sig"]
+        assert (act & (prs > 0)).sum() >= 10
+        if ndte == 1:            # the patch at rest: Delta == 0 exactly in the first subcycle
+            assert (act & (f["strength"] > 0) & (prs == 0)).sum() >= 10, (cfg, case, int((act & (f["strength"] > 0) & (prs == 0)).sum()))
+        assert np.abs(z[f"{pre}/uvel"][ph]).max() > 1e-3 and (z[f"{pre}/fm"][ph] > 0).any() and (z[f"{pre}/fm"][ph] < 0).any()
+    flags = {k: {c[3][k] for c in rv.DYN_CASES.values()} for k in ("revised_evp", "tilt_from_slope", "wind_on_ugrid")}
+    assert all(v == {0, 1} for v in flags.values()) and (rv.COSW, rv.SINW) != (1.0, 0.0)
+
+
+def _sig(q):
+    return [(orc.c_f64p * 4)(*[P_(q[f"{k}_{c}"]) for c in (1, 2, 3, 4)]) for k in ("stressp", "stressm", "stress12")]
+
+
+def _same(got, want, where):
+    assert got.dtype == want.dtype and np.array_equal(got, want), (where, int((got != want).sum()), np.argwhere(got != want)[:4].tolist())
+
+
+@pytest.mark.parametrize("cfg", list(rv.KERNEL_CONFIGS))
+def test_dyn_single_routines_equal_reference(cfg):
+    """orc_evp_prep1, orc_evp_prep2, orc_stress (ksub < ndte and ksub == ndte), orc_stepu, orc_evp_finish and
+    orc_principal_stress == the reference's own routines, every output array, every cell, bit for bit; classic EVP with the
+    geostrophic tilt and revised EVP with the tilt from the surface slope, a 25 degree turning angle; a full block and (on the
+    padded configuration) a block whose physical domain is 2 x 3 cells."""
+    z = load_dyn(cfg)
+    assert_block_coverage(cfg, z)
+    L = orc.lib()
+    i32, f64, pp = orc.c_i32p, orc.c_f64p, ct.POINTER(orc.OrcParams)
+    L.orc_evp_prep1.argtypes = [ct.c_int] * 6 + [f64] * 3 + [i32] + [f64] * 5 + [i32, pp]
+    L.orc_evp_prep2.argtypes = ([ct.c_int] * 6 + [i32] * 6 + [f64] * 4 + [i32] + [f64] * 6 + [i32, i32, f64, ct.c_double] + [f64] * 10 +
+                                [ct.POINTER(f64)] * 3 + [f64] * 4 + [pp])
+    L.orc_stepu.argtypes = [ct.c_int] * 3 + [f64, i32, i32] + [f64] * 19 + [pp]
+    L.orc_evp_finish.argtypes = [ct.c_int] * 3 + [f64, i32, i32] + [f64] * 10 + [pp]
+    nxb, nyb = rv.KERNEL_CONFIGS[cfg][2] + 2, rv.KERNEL_CONFIGS[cfg][3] + 2
+    n = 0
+    for rec, (ilo, ihi, jlo, jhi) in rv.BLOCK_RECORDS[cfg].items():
+        for var, v in rv.BLOCK_VARIANTS.items():
+            p = rv.block_params(var)
+            pre = f"{rec}/{var}"
+            q = {k: (a.copy() if isinstance(a, np.ndarray) else a) for k, a in rv.block_inputs(cfg, rec, var).items()}
+            o = {k: np.zeros((nyb, nxb)) for k in ("strairx", "strairy", "tmass")}
+            itm = np.zeros((nyb, nxb), np.int32)
+            L.orc_evp_prep1(nxb, nyb, ilo, ihi, jlo, jhi, P_(q["aice"]), P_(q["vice"]), P_(q["vsno"]), orc._p32(q["tmask"]), P_(q["strairxT"]),
+                            P_(q["strairyT"]), P_(o["strairx"]), P_(o["strairy"]), P_(o["tmass"]), orc._p32(itm), ct.byref(p))
+            for k in o:
+                _same(o[k], z[f"{pre}/evp_prep1/{k}"], (pre, "evp_prep1", k))
+            _same(itm, z[f"{pre}/evp_prep1/icetmask"], (pre, "evp_prep1", "icetmask"))
+
+            q = {k: (a.copy() if isinstance(a, np.ndarray) else a) for k, a in rv.block_inputs(cfg, rec, var).items()}
+            for k in ("umassdti", "waterx", "watery", "forcex", "forcey"):
+                q[k] = np.full((nyb, nxb), 9.0)
+            cnt = (ct.c_int32 * 2)()
+            idx = np.zeros((4, nxb * nyb), np.int32)
+            sp, sm, s12 = _sig(q)
+            L.orc_evp_prep2(nxb, nyb, ilo, ihi, jlo, jhi, ct.cast(ct.byref(cnt, 0), i32), ct.cast(ct.byref(cnt, 4), i32),
+                            orc._p32(idx[0]), orc._p32(idx[1]), orc._p32(idx[2]), orc._p32(idx[3]),
+                            P_(q["aiu"]), P_(q["umass"]), P_(q["umassdti"]), P_(q["fcor"]), orc._p32(q["umask"]), P_(q["uocn"]), P_(q["vocn"]),
+                            P_(q["strairx"]), P_(q["strairy"]), P_(q["ss_tltx"]), P_(q["ss_tlty"]), orc._p32(q["icetmask"]),
+                            orc._p32(q["iceumask"]), P_(q["fm"]), rv.DYN_DT, P_(q["strtltx"]), P_(q["strtlty"]), P_(q["strocnx"]),
+                            P_(q["strocny"]), P_(q["strintx"]), P_(q["strinty"]), P_(q["waterx"]), P_(q["watery"]), P_(q["forcex"]),
+                            P_(q["forcey"]), sp, sm, s12, P_(q["uvel_init"]), P_(q["vvel_init"]), P_(q["uvel"]), P_(q["vvel"]), ct.byref(p))
+            for k in [x for x in z.files if x.startswith(f"{pre}/evp_prep2/")]:
+                name = k.rsplit("/", 1)[1]
+                got = {"icell": np.array(list(cnt), np.int32), "indx": idx}.get(name, q.get(name))
+                _same(got, z[k], (pre, "evp_prep2", name))
+                n += 1
+
+            q = {k: (a.copy() if isinstance(a, np.ndarray) else a) for k, a in rv.block_inputs(cfg, rec, var).items()}
+            strv = orc.stress_block(nxb, nyb, v["ksub"], v["ndte"], np.ascontiguousarray(q["indxt"][0, :q["icellt"]]),
+                                    np.ascontiguousarray(q["indxt"][1, :q["icellt"]]), q, p)
+            for k in SN + ["shear", "divu", "prs_sig", "rdg_conv", "rdg_shear"]:
+                _same(q[k], z[f"{pre}/stress/{k}"], (pre, "stress", k))
+            _same(strv, z[f"{pre}/stress/str"], (pre, "stress", "str"))
+            assert (z[f"{pre}/stress/divu"] != rv.block_inputs(cfg, rec, var)["divu"]).any() == (v["ksub"] == v["ndte"])
+
+            q = {k: (a.copy() if isinstance(a, np.ndarray) else a) for k, a in rv.block_inputs(cfg, rec, var).items()}
+            L.orc_stepu(nxb, nyb, q["icellu"], P_(q["Cw"]), orc._p32(q["indxu"][0]), orc._p32(q["indxu"][1]), P_(q["aiu"]), P_(q["str"]),
+                        P_(q["uocn"]), P_(q["vocn"]), P_(q["waterx"]), P_(q["watery"]), P_(q["forcex"]), P_(q["forcey"]), P_(q["umassdti"]),
+                        P_(q["fm"]), P_(q["uarear"]), P_(q["strocnx"]), P_(q["strocny"]), P_(q["strintx"]), P_(q["strinty"]),
+                        P_(q["uvel_init"]), P_(q["vvel_init"]), P_(q["uvel"]), P_(q["vvel"]), ct.byref(p))
+            for k in ("strocnx", "strocny", "strintx", "strinty", "uvel", "vvel"):
+                _same(q[k], z[f"{pre}/stepu/{k}"], (pre, "stepu", k))
+
+            q = {k: (a.copy() if isinstance(a, np.ndarray) else a) for k, a in rv.block_inputs(cfg, rec, var).items()}
+            L.orc_evp_finish(nxb, nyb, q["icellu"], P_(q["Cw"]), orc._p32(q["indxu"][0]), orc._p32(q["indxu"][1]), P_(q["uvel"]), P_(q["vvel"]),
+                             P_(q["uocn"]), P_(q["vocn"]), P_(q["aiu"]), P_(q["fm"]), P_(q["strocnx"]), P_(q["strocny"]), P_(q["strocnxT"]),
+                             P_(q["strocnyT"]), ct.byref(p))
+            for k in ("strocnx", "strocny", "strocnxT", "strocnyT"):
+                _same(q[k], z[f"{pre}/evp_finish/{k}"], (pre, "evp_finish", k))
+
+            s1, s2 = np.zeros((nyb, nxb)), np.zeros((nyb, nxb))
+            L.orc_principal_stress(nxb, nyb, P_(q["stressp_1"]), P_(q["stressm_1"]), P_(q["stress12_1"]), P_(q["prs"]), P_(s1), P_(s2))
+            _same(s1, z[f"{pre}/principal_stress/sig1"], (pre, "sig1")); _same(s2, z[f"{pre}/principal_stress/sig2"], (pre, "sig2"))
+    assert n >= 30 * len(rv.BLOCK_RECORDS[cfg]) * 2
+
+
+def chain_cells(d):
+    from tests import util
+    m = {k: util.cell_mask(d, k) for k in ("all", "ne", "phys")}
+    kind = {n: "all" for n in util.ALL_CELLS}
+    kind.update({n: "ne" for n in util.NE_CELLS})
+    kind.update({n: "phys" for n in util.PHYS_CELLS})
+    return m, kind
+
+
+def chain_diff(d, got, z, pre):
+    """fields of `got` that differ from the chain record `pre` of fixture z on the cells the reference defines (tests/util.py)"""
+    m, kind = chain_cells(d)
+    bad = []
+    for k in z.files:
+        if not k.startswith(pre + "/"):
+            continue
+        n = k.split("/", 1)[1]
+        if n not in kind or n not in got:
+            continue
+        a, b = got[n][m[kind[n]]], z[k][m[kind[n]]]
+        if not np.array_equal(a != 0 if n == "iceumask" else a, b != 0 if n == "iceumask" else b):
+            bad.append((n, int((a != b).sum()), float(np.abs(a.astype(float) - b.astype(float)).max())))
+    return bad
+
+
+_chain_inputs = {}
+
+
+def chain_inputs(cfg, case):
+    """(decomp, fields) of a chain record, built once per session and never modified (callers clone)"""
+    if (cfg, case) not in _chain_inputs:
+        _chain_inputs[cfg, case] = rv.dyn_fields(cfg, case)
+    return _chain_inputs[cfg, case]
+
+
+@pytest.mark.parametrize("case", list(rv.DYN_CASES))
+@pytest.mark.parametrize("cfg", list(rv.KERNEL_CONFIGS))
+def test_evp_chain_equals_reference(cfg, case):
+    """orc.evp == the reference's evp_prep1 -> icetmask halo -> evp_prep2 -> ndte x (stress -> stepu -> velocity halo) ->
+    stress fold (tripole) -> evp_finish, run by the reference's own routines and halo updates on the whole grid, for
+    ndte = 6, 5 and 1: every output on the cells the reference defines, bit for bit; then principal_stress and the cell counts.
+    The T<->U averages inside (aiu, umass, wind stress, the last step of strocnxT / strocnyT) are the restatement's own on
+    both sides: they remain unpinned."""
+    from tests import util
+    z = load_dyn(cfg, case)
+    d, f = chain_inputs(cfg, case)
+    assert_chain_coverage(cfg, case, d, f, z)
+    ph = util.cell_mask(d, "phys")
+    for ndte in rv.DYN_NDTE:
+        pk, po = rv.dyn_params(cfg, case, ndte, f, d)
+        fo = util.clone(f)
+        nt, nu, _ = orc.evp(d, po, fo)
+        pre = f"ndte{ndte}"
+        assert len([k for k in z.files if k.startswith(pre + "/")]) >= 36
+        bad = chain_diff(d, fo, z, pre)
+        assert not bad, (cfg, case, ndte, bad)
+        assert nu == int(z[f"{pre}/icell"][:, 1].sum()) and nt == int((z[f"{pre}/icetmask"][ph] == 1).sum())
+        s1, s2 = np.zeros_like(fo["uvel"]), np.zeros_like(fo["uvel"])
+        for n in range(d.nblocks):
+            orc.lib().orc_principal_stress(d.nx_block, d.ny_block, P_(fo["stressp_1"][n]), P_(fo["stressm_1"][n]), P_(fo["stress12_1"][n]),
+                                           P_(fo["prs_sig"][n]), P_(s1[n]), P_(s2[n]))
+        assert np.array_equal(s1[ph], z[f"{pre}/sig1"][ph]) and np.array_equal(s2[ph], z[f"{pre}/sig2"][ph])

@@ -6,7 +6,11 @@ oracle/ref/Makefile; inputs tests/golden/refvec.py) -- the device counterparts o
     tripole grids in 1 and 16 (padded) blocks, with an eliminated land block -- one rank, the forced-exchange path, and
     2 - 4 x-slab ranks;
   * k_ice_strength (evpk_run with strength == NULL) against ice_strength;
-  * bound_state inside evpk_transport_remap_state's scatter against bound_state.
+  * bound_state inside evpk_transport_remap_state's scatter against bound_state;
+  * the EVP dynamics (evpk_run, and evpk_upload / prep / subcycle / finish / download in pieces) against the chain records of
+    tests/golden/ref_dyn_*.npz -- the reference's own evp_prep1, evp_prep2, stress, stepu, evp_finish run in evp()'s call order
+    with its own halo updates -- under every subcycle-kernel variant, with evpk_principal_stress and the cell counts.  The
+    T<->U averages (to_ugrid / to_tgrid) are not part of the reference build and stay pinned by the restatement alone.
 """
 from __future__ import annotations
 
@@ -245,3 +249,77 @@ def test_device_bound_state_equals_reference(cfg):
         assert np.array_equal(trcrn[:, :, ntrcr:], before[3][:, :, ntrcr:])          # tracers not in use stay
         checked += 1
     assert checked >= 2
+
+
+DYN_VARIANTS = {"default": {}, "march": {"EVPK_TILE": "0"}, "tile": {"EVPK_TILE": "1"}, "single": {"EVPK_DOUBLE": "0"},
+                "exchange": {"EVPK_FORCE_EXCHANGE": "1"}, "full_metrics": {"EVPK_COMPACT_METRICS": "0"}}
+
+
+def _dyn_chain(cfg, case, ndte, pieces=None):
+    """one chain record through the device; returns the list of differences from the reference"""
+    from cice5_amd import evpk
+    from tests import test_ref_pins as P, util
+    from tests.golden import refvec as rv
+    z = P.load_dyn(cfg, case)
+    d, f = P.chain_inputs(cfg, case)
+    pk, _ = rv.dyn_params(cfg, case, ndte, f, d)
+    g = util.clone(f)
+    s1, s2 = np.zeros_like(g["uvel"]), np.zeros_like(g["uvel"])
+    ctx = evpk.Context(d, g, device=0)
+    try:
+        ctx.set_params(pk)
+        if pieces is None:
+            ctx.run(g)
+        else:
+            assert sum(pieces) == ndte
+            ctx.upload(g); ctx.prep()
+            for n in pieces:
+                ctx.subcycle(n)
+            ctx.finish(); ctx.download(g)
+        ctx.principal_stress(s1, s2)
+        st = ctx.stats()
+        counts = (int(st.icellt), int(st.icellu))
+    finally:
+        ctx.close()
+    pre = f"ndte{ndte}"
+    ph = util.cell_mask(d, "phys")
+    bad = [(case, ndte) + b for b in P.chain_diff(d, g, z, pre)]
+    want = (int((z[f"{pre}/icetmask"][ph] == 1).sum()), int(z[f"{pre}/icell"][:, 1].sum()))
+    if counts != want:
+        bad.append((case, ndte, "icellt/icellu", counts, want))
+    for name, a in (("sig1", s1), ("sig2", s2)):
+        if not np.array_equal(a[ph], z[f"{pre}/{name}"][ph]):
+            bad.append((case, ndte, name, int((a[ph] != z[f"{pre}/{name}"][ph]).sum())))
+    return bad
+
+
+@pytest.mark.parametrize("variant", list(DYN_VARIANTS))
+@pytest.mark.parametrize("cfg", ["g72x20_b72x20", "g26x18_b8x5"])
+def test_device_evp_equals_reference_chain(cfg, variant, monkeypatch):
+    """evpk_run == the reference's own evp_prep1 -> evp_prep2 -> ndte x (stress -> stepu -> halo) -> stress fold -> evp_finish
+    (tests/golden/ref_dyn_*.npz), bit for bit on the cells tests/util.py compares, for every boundary case (cyclic / open,
+    tripole, open / closed with a land rim, an island) and ndte = 6, 5, 1; then evpk_principal_stress against the reference's
+    principal_stress and evpk_get_stats against its cell counts.  variant: the default tuning, the marching pair kernel, the
+    tile kernel, one subcycle per launch, the forced exchange path, the full-metrics kernels.  The T<->U averages inside are
+    not in the reference build: they remain pinned by the restatement alone (tests/test_ref_pins.py)."""
+    from tests import test_ref_pins as P
+    from tests.golden import refvec as rv
+    for k, v in DYN_VARIANTS[variant].items():
+        monkeypatch.setenv(k, v)
+    bad = []
+    for case in rv.DYN_CASES:
+        d, f = P.chain_inputs(cfg, case)
+        P.assert_chain_coverage(cfg, case, d, f, P.load_dyn(cfg, case))
+        for ndte in rv.DYN_NDTE:
+            bad += _dyn_chain(cfg, case, ndte)
+    assert not bad, bad[:6]
+
+
+@pytest.mark.parametrize("cfg", ["g72x20_b72x20", "g26x18_b8x5"])
+def test_device_evp_in_pieces_equals_reference_chain(cfg):
+    """evpk_upload / prep / subcycle(2) / subcycle(3) / subcycle(1) / finish / download == the reference's ndte = 6 chain"""
+    from tests.golden import refvec as rv
+    bad = []
+    for case in rv.DYN_CASES:
+        bad += _dyn_chain(cfg, case, 6, pieces=[2, 3, 1])
+    assert not bad, bad[:6]
