@@ -30,9 +30,6 @@
 
 // single translation unit: the kernels are compiled together with the host API
 #include "evpk_kernels.hip"
-#ifdef EVPK_EXPERIMENTAL
-#include "evpk_experimental.hip"      // k_subcycle2, k_subcycle3w: measured and not adopted (make exp -> libevpk_exp.so)
-#endif
 #include "evpk_remap.hip"
 #include "evpk_eap.hip"
 
@@ -234,7 +231,7 @@ struct evpk_ctx {
     bool fresh = true;          // state planes were (re)loaded from the host since the last prep
     unsigned char *tile_buf = nullptr;   // 6 tile-flag arrays: ice/dat x {A, B} (new / previous evp, swapped) + act_ice, act_any
     int tile_cur = 0;
-    bool zone_mode = false;     // k_subcycle2 reads ghost zones filled by exchange_cols (x-slabs / forced exchange)
+    bool zone_mode = false;     // the pair kernels read ghost zones filled by exchange_cols (x-slabs / forced exchange)
     // Ghost zones are zW = 2*zM columns wide (2*zM + 1 when the tripole band runs between ranks: evpk_connect): a two-subcycle launch consumes two columns of validity per side, the zone
     // columns themselves are advanced redundantly, so the neighbours exchange once per zM launches (communication avoiding).
     int zW = 2, zM = 1;
@@ -299,19 +296,18 @@ struct evpk_ctx {
     int xranks = 1;
     bool idle = false;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;   // interior strips of k_subcycle2 while `stream` exchanges the edge columns
+    hipStream_t stream2 = nullptr;   // interior strips of the pair kernel while `stream` exchanges the edge columns
     hipEvent_t evI = nullptr, evX = nullptr;
     int *d_strips2e = nullptr, *d_strips2i = nullptr;
     int *d_band = nullptr;           // strips 0..ncx-1 of a one-band launch (tripole top band)
     bool strips1_valid = false;      // d_strips / nstrips (one-subcycle kernel) match the masks of the last prep
-    bool band_mode = false;          // tripole + k_subcycle2: the top rows are redone with two one-subcycle band launches
+    bool band_mode = false;          // tripole + pair kernels: the top rows are redone with two one-subcycle band launches
     int nstrips2e = 0, nstrips2i = 0;
     bool overlap = true;
     bool ov_fixed = true;            // false: still trying the split against whole launches (first three evps on x-slabs)
     int ov_trial = 0;
     float ov_ms[2] = {0.f, 0.f};     // loop time with the split on / off
     bool compact = false;           // k_subcycle2p reads HTN/HTE instead of the eight metric planes (verified at create)
-    bool prefetch = true;           // k_subcycle2p (next row through LDS) instead of k_subcycle2; EVPK_PREFETCH=0 disables
     ncclComm_t comm = nullptr;
     ShmRelay *relay = nullptr;      // test transport instead of RCCL (unique id "EVPKSHM:<name>")
     IpcXp *ipc = nullptr;           // peer-mapped transport (unique id "EVPKIPC:<name>")
@@ -326,7 +322,7 @@ struct evpk_ctx {
     int ncx2 = 0, nstrips2 = 0;      // 61-column strips of the two-subcycle kernel
     int R2 = 16, nry2 = 0;           // their height, tuned to the active area (tune_R2)
     long long tuned_icellt = -1, tuned1_icellt = -1;
-    int slots2 = 512;                // resident 256-thread workgroups of k_subcycle2 on the whole chip
+    int slots2 = 512;                // resident 256-thread workgroups of k_subcycle2p on the whole chip
     int nsimd = 1024;                // SIMDs of the chip (4 per CU)
     double *tp_a = nullptr, *tp_b = nullptr, *tp_stage = nullptr;   // transport_upwind: two scratch planes, staging of the work array
     size_t tp_stage_n = 0;
@@ -359,22 +355,12 @@ struct evpk_ctx {
     unsigned char *d_flags2 = nullptr;
     int *d_strips2 = nullptr;
     int double_launches = 0;
-    // three subcycles per launch: k_subcycle3w, the stage-per-wave pipeline (EVPK_TRIPLE; one rank, see subcycle_impl)
-    bool use_triple = false;
-    int triple_env = -1;             // EVPK_TRIPLE=0 / 1 fixes the choice, -1: by the rule in evpk_prep
-    int ncx3 = 0, nry3 = 0, R3 = 24, nstrips3 = 0, ns_tot3_cur = 0;
-    unsigned char *d_flags3 = nullptr;
-    int *d_strips3 = nullptr, *d_ns3 = nullptr;
-    int triple_launches = 0, kernel3_timed = 0;
     int prio = 1;                        // EVPK_PRIO (default 1): SubArgs.prio
     int band_last = 1;                   // EVPK_BAND_LAST (default 1): SubArgs.band_last
     unsigned char *up_dat = nullptr;     // per tile: the uploaded inputs hold something (k_up_tiles)
     bool up_dirty = true;                // ... and an upload has happened since it was computed
-    size_t flags3_n = 0;
-    bool lpt = true;                     // EVPK_LPT=0: the strips of k_subcycle3w in position order instead of longest first
     const char *dbg_file = nullptr;      // EVPK_DEBUG_CLOCKS
     unsigned long long *d_dbg = nullptr;
-    float kernel3_ms = 0.f;
     unsigned char *d_flags = nullptr;
     int *d_strips = nullptr;
     unsigned long long *d_counts = nullptr;
@@ -570,15 +556,6 @@ extern "C" int evpk_host_free(void *ptr) {
 }
 
 // 1 if [ptr, ptr + bytes) lies inside a live evpk_pin_host / evpk_host_alloc range (the library will move it in place), else 0
-// 1 if this build contains the measured-and-rejected kernels (k_subcycle2, k_subcycle3w: -DEVPK_EXPERIMENTAL), else 0
-extern "C" int evpk_experimental_built(void) {
-#ifdef EVPK_EXPERIMENTAL
-    return 1;
-#else
-    return 0;
-#endif
-}
-
 extern "C" int evpk_host_is_mapped(const void *ptr, size_t bytes) {
     std::lock_guard<std::mutex> lk(g_pin_mu);
     const uintptr_t lo = (uintptr_t)ptr, hi = lo + bytes;
@@ -1214,7 +1191,7 @@ template <class F> static inline void with_bool(bool flag1, bool flag2, F &&f) {
 // workgroups of a launch (or of one part of it: strips, band, mirror slab) rounded up to a multiple of 8: XCD remap in the kernels
 static inline int xcd_round(int nwg) { return (nwg + 7) & ~7; }
 
-// ---- launch of the two-subcycle kernel (plain or LDS-prefetch variant) ------------------------------------
+// ---- launch of the two-subcycle kernel (marching k_subcycle2p or one of the tile kernels) ------------------
 static void launch_sub2(evpk_ctx *c, const SubArgs &a_in, hipStream_t st, bool revp, bool last2) {
     // The tripole band (and mirror-slab) workgroups as the LAST of the grid (round 5) -- in the marching kernel only.  There the
     // strips of a launch take (nearly) all workgroup slots for ~200 us and 30 band workgroups of ~50 us in FRONT of them pushed
@@ -1223,7 +1200,7 @@ static void launch_sub2(evpk_ctx *c, const SubArgs &a_in, hipStream_t st, bool r
     // started last, the band is all that is left running (1440x1080 tripole 2.90 -> 3.40 ms per evp): there it stays first.
     SubArgs a = a_in;
     a.band_last = (c->band_last && !c->tile_mode) ? 1 : 0;
-    const bool xm = a.nmir > 0 && !last2 && a.xm && (c->tile_mode || c->prefetch);      // ... then the strips of the mirror slab (x-slab ranks, XM kernels)
+    const bool xm = a.nmir > 0 && !last2 && a.xm;      // ... then the strips of the mirror slab (x-slab ranks, XM kernels)
     // the strips (tile kernels: one per workgroup, marching kernels: four), then the tripole top band as workgroups of the pair's
     // own launch (band_pair), then the strips of the mirror slab
     const int per_wg = c->tile_mode ? 1 : 4;
@@ -1244,26 +1221,12 @@ static void launch_sub2(evpk_ctx *c, const SubArgs &a_in, hipStream_t st, bool r
             if (xm) hipLaunchKernelGGL((k_subcycle2t<rv, false, true>), g, b, lds, st, a);
             else if (last2 && a.R + 3 <= 8) hipLaunchKernelGGL(k_subcycle2t8<rv>, g, b, lds, st, a);      // (no scratch)
             else with_bool(last2, [&](auto L2) { hipLaunchKernelGGL((k_subcycle2t<rv, decltype(L2)::value>), g, b, lds, st, a); });
-        } else if (c->prefetch) {
+        } else {                                 // marching, the next row prefetched through LDS
             const dim3 b(256);
             if (xm) with_bool(c->compact, [&](auto CMX) { hipLaunchKernelGGL((k_subcycle2p<rv, false, decltype(CMX)::value, true>), g, b, 0, st, a); });
             else with_bool(last2, c->compact, [&](auto L2, auto CMX) { hipLaunchKernelGGL((k_subcycle2p<rv, decltype(L2)::value, decltype(CMX)::value>), g, b, 0, st, a); });
         }
-#ifdef EVPK_EXPERIMENTAL
-        else with_bool(last2, [&](auto L2) { hipLaunchKernelGGL((k_subcycle2<rv, decltype(L2)::value>), g, dim3(256), 0, st, a); });
-#endif
     });
-}
-
-// three subcycles in one launch: one workgroup of three waves per strip (k_subcycle3w)
-static void launch_sub3(evpk_ctx *c, const SubArgs &a, hipStream_t st, bool revp) {
-#ifdef EVPK_EXPERIMENTAL
-    with_bool(revp, c->compact, [&](auto RV, auto CMX) {
-        hipLaunchKernelGGL((k_subcycle3w<decltype(RV)::value, decltype(CMX)::value>), dim3(xcd_round(a.nstrips)), dim3(192), 0, st, a);
-    });
-#else
-    (void)c; (void)a; (void)st; (void)revp;      // (never reached: evpk_create refuses EVPK_TRIPLE=1 without the kernel)
-#endif
 }
 
 // one subcycle, one row per wave (k_subcycle_t): the band launches of a tripole pair -- their sequence is on the critical path of
@@ -1344,7 +1307,7 @@ static void destroy_impl(evpk_ctx *c) {
     if (c->relay) { c->relay->close_(); delete c->relay; }
     if (c->ipc) { if (c->stream2) (void)hipStreamSynchronize(c->stream2); c->ipc->close_(); delete c->ipc; }
     void *ptrs[] = {c->itd, c->stage_itd, c->d_zflags, c->d_zrows, c->s.F, c->s.tmask, c->s.umask, c->s.iceumask, c->s.cmask, c->s.tmphm, c->d_bd, c->stage, c->d_flags,
-                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_flags3, c->d_strips3, c->d_ns3, c->d_dbg, c->up_dat};
+                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1541,7 +1504,7 @@ static int connect_impl(evpk_ctx *c, const void *unique_id) {
             // refresh as in round 3 unless EVPK_XB_MERGE=1 asks for the merged form
             if (c->comm && c->nranks > 1) c->xb_merge = false;
             if (const char *e = getenv("EVPK_XB_MERGE")) c->xb_merge = atoi(e) != 0;
-            bool ok = c->band_mode && c->nranks > 1 && c->prefetch && c->band_fused && !(xe && atoi(xe) == 0) &&
+            bool ok = c->band_mode && c->nranks > 1 && c->band_fused && !(xe && atoi(xe) == 0) &&
                       minw >= 2 * ZW_MAX && s.nyl >= XB_ROWS_MAX + 1;
             if (ok) {
                 const int P = c->nranks, nx = s.nxg;
@@ -1613,11 +1576,7 @@ static int connect_impl(evpk_ctx *c, const void *unique_id) {
     }
     {   // resident workgroups of the two-subcycle kernel variant this context launches (strip-height tuner)
         int nb = 0;
-        const void *fn =
-#ifdef EVPK_EXPERIMENTAL
-                         !c->prefetch ? (const void *)k_subcycle2<false, false> :
-#endif
-                                      (c->compact ? (const void *)k_subcycle2p<false, false, true> : (const void *)k_subcycle2p<false, false, false>);
+        const void *fn = c->compact ? (const void *)k_subcycle2p<false, false, true> : (const void *)k_subcycle2p<false, false, false>;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0) == hipSuccess && nb > 0)
             c->slots2 = nb * prop.multiProcessorCount;
     }
@@ -1821,7 +1780,8 @@ static int create_impl(evpk_ctx *c, const evpk_geom *g) {
         c->overlap = !(e && atoi(e) == 0);
         c->ov_fixed = (e != nullptr);
     }
-    { const char *e = getenv("EVPK_PREFETCH"); c->prefetch = !(e && atoi(e) == 0); }
+    // the pair kernel without the LDS prefetch was measured and not adopted: retired, see DESIGN.md
+    { const char *e = getenv("EVPK_PREFETCH"); if (e && atoi(e) == 0) FAIL(c, "EVPK_PREFETCH=0 selects k_subcycle2, which was retired (last held by commit 11c5403)"); }
     { const char *e = getenv("EVPK_TILE"); c->tile_force = e ? (atoi(e) != 0 ? 1 : 0) : -1; c->roll_force = e ? (atoi(e) == 2 ? 1 : 0) : -1; }
     { const char *e = getenv("EVPK_VERIFY_DELIVERY"); c->verify_delivery = e ? atoi(e) : 0; }
     { const char *e = getenv("EVPK_XFER_FUSED"); c->xfer_fused = !(e && atoi(e) == 0); }
@@ -1894,12 +1854,8 @@ static int create_impl(evpk_ctx *c, const evpk_geom *g) {
     if (const char *bf = getenv("EVPK_BAND_FUSED")) c->band_fused = atoi(bf) != 0;
     if (const char *ff = getenv("EVPK_FINISH_FUSED")) c->finish_fused = atoi(ff) != 0;
     if (const char *ds = getenv("EVPK_DEVICE_STRIPS")) c->dev_strips_env = atoi(ds) != 0;
-    if (const char *tr = getenv("EVPK_TRIPLE")) c->triple_env = atoi(tr) != 0 ? 1 : 0;
-#ifndef EVPK_EXPERIMENTAL
-    // k_subcycle2 (no LDS prefetch) and k_subcycle3w (three subcycles per launch) were measured and not adopted: they are not in this build
-    if (!c->prefetch) FAIL(c, "EVPK_PREFETCH=0 selects k_subcycle2, which this build of libevpk does not contain (make -C cice5_amd/csrc exp)");
-    if (c->triple_env == 1) FAIL(c, "EVPK_TRIPLE=1 selects k_subcycle3w, which this build of libevpk does not contain (make -C cice5_amd/csrc exp)");
-#endif
+    // the kernel of three subcycles per launch was measured and not adopted: retired, see DESIGN.md
+    if (const char *tr = getenv("EVPK_TRIPLE")) if (atoi(tr) != 0) FAIL(c, "EVPK_TRIPLE=1 selects k_subcycle3w, which was retired (last held by commit 11c5403)");
     c->dbg_file = getenv("EVPK_DEBUG_CLOCKS");
     if (const char *pr = getenv("EVPK_PRIO")) c->prio = atoi(pr);
     if (const char *bl = getenv("EVPK_BAND_LAST")) c->band_last = atoi(bl) != 0 ? 1 : 0;
@@ -2055,7 +2011,7 @@ extern "C" int evpk_upload(evpk_ctx *c, const evpk_step_in *in, const evpk_state
     return 0;
 }
 
-// Strip height of k_subcycle2.  The kernel's run time is quantised in "rounds" of resident workgroups
+// Strip height of the pair kernels.  The kernel's run time is quantised in "rounds" of resident workgroups
 // (2 per CU): a launch with slightly more workgroups than fit pays a whole extra round, while tall strips
 // waste less on the three redundant stage-1 rows.  Count the active strips for a few heights and take the
 // cheapest  rounds x (R+5).  Re-tuned when the active area changed by more than 5 %.
@@ -2132,45 +2088,6 @@ static int tune_R2(evpk_ctx *c) {
     c->tuned_icellt = -2;      // set from the counts of this prep below
     return 0;
 }
-
-// Strip list of the three-subcycle pipeline kernel (k_subcycle3w): flags and ordered compaction on the device, the kernel reads the
-// list's length from d_ns3; the host never waits for it.  One rank without ghost zones, marching (not tile) pairs, no tripole band
-// (round 4, stage a); EVPK_TRIPLE=0 / 1 overrides.
-#ifndef EVPK_EXPERIMENTAL
-static int prep_triple(evpk_ctx *c, int) { c->use_triple = false; return 0; }      // (k_subcycle3w is not in this build)
-#else
-static int prep_triple(evpk_ctx *c, int G) {
-    Slab &s = c->s;
-    const bool can = c->use_double && !c->eap && c->nranks == 1 && !c->zone_mode && !c->force_exchange && !c->band_mode &&
-                     !c->tile_mode && c->prefetch && c->p.ndte >= 5 && s.nyl >= 8;
-    c->use_triple = can && c->triple_env == 1;
-    if (!c->use_triple) return 0;
-    if (!c->d_flags3) {
-        const size_t n3 = (size_t)((s.nxl + 2 * (ZW_MAX - 2) + STRIP3_W - 1) / STRIP3_W) * (s.nyl + 2);
-        HIPCHK(c, hipMalloc(&c->d_flags3, 2 * n3));      // flags, then the work (active rows) of every strip
-        c->flags3_n = n3;
-        if (const char *e = getenv("EVPK_LPT")) c->lpt = atoi(e) != 0;
-        HIPCHK(c, hipMalloc(&c->d_strips3, sizeof(int) * n3));
-        HIPCHK(c, hipMalloc(&c->d_ns3, sizeof(int) * 2));
-        HIPCHK(c, hipMemset(c->d_ns3, 0, sizeof(int) * 2));
-    }
-    const char *e = getenv("EVPK_STRIP_ROWS3");
-    c->R3 = (e && atoi(e) > 0) ? std::max(2, std::min(atoi(e), 128)) : 24;
-    c->ncx3 = (s.nxl + 2 * G + STRIP3_W - 1) / STRIP3_W;
-    c->nry3 = (s.nyl + 1 + c->R3 - 1) / c->R3;
-    const int tot = c->ncx3 * c->nry3;
-    hipLaunchKernelGGL(k_strip_flags2, dim3((tot + 3) / 4), dim3(256), 0, c->stream, s, c->ncx3, c->nry3, c->R3,
-                       (c->ew == EVPK_BND_CYCLIC && !c->zone_mode) ? 1 : 0, G, c->d_flags3, (unsigned int *)nullptr,
-                       (unsigned long long *)nullptr, (int)STRIP3_W, (int)STRIP3_OWN0, 2, c->d_flags3 + c->flags3_n);
-    if (c->lpt) hipLaunchKernelGGL(k_sort_strips, dim3(1), dim3(1024), 0, c->stream, (const unsigned char *)(c->d_flags3 + c->flags3_n), tot, c->d_strips3, c->d_ns3);
-    else hipLaunchKernelGGL(k_compact_strips, dim3(1), dim3(1024), 0, c->stream, (const unsigned char *)c->d_flags3, tot, c->d_strips3, c->d_ns3);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_counts + 3, c->d_ns3, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    c->ns_tot3_cur = tot;
-    c->nstrips3 = tot;                // (the true number arrives with the loop's last event, as nstrips2 does)
-    return 0;
-}
-#endif
 
 // Strip list of the one-subcycle kernel (and, when the two-subcycle kernel is off, the active-cell counts): flags on the
 // device, compaction on the host.  Called by evpk_prep when only that kernel exists, else on first use after a prep.
@@ -2287,7 +2204,7 @@ extern "C" int evpk_prep(evpk_ctx *c) {
     c->zcompact = false;
     std::vector<unsigned char> zflags;
     if (c->zone_mode) {
-        // ghost zones for k_subcycle2: every plane it reads, the current state and the masks, all rows, once per evp
+        // ghost zones for the pair kernels: every plane they read, the current state and the masks, all rows, once per evp
         PairList pl = state_pairs(SA);
         const int per_evp[] = {F_TINYAREA /* + strength */, F_VRELC, F_UOCN, F_FORCEX, F_UMASSDTI, F_UVEL_INIT};
         const int once[] = {F_CXP, F_CXM, F_DXT, F_DXHY, F_HTN};        // grid metrics: the first evp only
@@ -2326,7 +2243,6 @@ extern "C" int evpk_prep(evpk_ctx *c) {
     if (!c->use_double && strips1(c)) return 1;
     if (c->use_double && tune_R2(c)) return 1;
     const int ns_tot2 = c->ncx2 * c->nry2;
-    if (prep_triple(c, G)) return 1;
     // one rank, or x-slab ranks on a tripole grid (no edge / interior lists, no row lists of the zone windows to make on the host)
     c->dev_strips = c->dev_strips_env && c->use_double &&
                     ((!c->zone_mode && c->nranks == 1 && !c->force_exchange) || (c->zone_mode && c->band_mode));
@@ -2500,9 +2416,9 @@ extern "C" int evpk_eap_download(evpk_ctx *c, evpk_eap_state *st) {
 
 // the per-call counters of evpk_get_stats: zero at the start of every subcycle call, whichever loop runs it
 static void reset_call_counters(evpk_ctx *c) {
-    c->kernel_ms = c->kernel2_ms = c->kernel3_ms = 0.f;
-    c->kernel_launches = c->double_launches = c->triple_launches = 0;
-    c->kernel_timed = c->kernel2_timed = c->kernel3_timed = 0;
+    c->kernel_ms = c->kernel2_ms = 0.f;
+    c->kernel_launches = c->double_launches = 0;
+    c->kernel_timed = c->kernel2_timed = 0;
     c->bound_updates = 0; c->bound_timed = 0; c->bound_ms = 0.f;
     c->xb_swaps = 0; c->zone_exchanges = 0; c->zone_bytes = 0;
 }
@@ -2549,7 +2465,7 @@ static void take_counts(evpk_ctx *c) {
 
 // ---- the timers of the subcycle loop (events owned by the context: kev, bev) --------------------------------------------------
 // Kernel timing by HIP events on the stream the launches go to, in SPANS: one event in front of a run of consecutive
-// launches of one kind (1, 2 or 3 subcycles per launch) and one behind it, launches 3..8 of every 20 by default
+// launches of one kind (1 or 2 subcycles per launch) and one behind it, launches 3..8 of every 20 by default
 // (EVPK_TIME_KERNELS=2: every launch a span of its own, 0: none).  A span's time / its launches is the per-launch time as the
 // stream's timeline has it (launch gaps included, the ~4-8 us an event pair costs spread over six launches), so that
 // launches x average never exceeds the loop time.  A span ends early when the kind or the stream changes and in front of any
@@ -2617,18 +2533,17 @@ struct LoopTimer {
         }
         if (c->time_kernels) {
             // per kind: time of its spans / launches inside them, scaled to all launches of that kind
-            double sum[4] = {0, 0, 0, 0};
-            int cnt[4] = {0, 0, 0, 0};
+            double sum[3] = {0, 0, 0};
+            int cnt[3] = {0, 0, 0};
             for (int k = 0; k < c->nkev; k++) {
                 float ms = 0.f;
                 HIPCHK(c, hipEventElapsedTime(&ms, c->kev[2 * k], c->kev[2 * k + 1]));
                 sum[c->kev_kind[k]] += ms; cnt[c->kev_kind[k]] += c->kev_count[k];
             }
-            const int n1 = c->kernel_launches - c->double_launches - c->triple_launches;
+            const int n1 = c->kernel_launches - c->double_launches;
             if (cnt[1]) c->kernel_ms = (float)(sum[1] / cnt[1] * n1);
             if (cnt[2]) c->kernel2_ms = (float)(sum[2] / cnt[2] * c->double_launches);
-            if (cnt[3]) c->kernel3_ms = (float)(sum[3] / cnt[3] * c->triple_launches);
-            c->kernel_timed = cnt[1]; c->kernel2_timed = cnt[2]; c->kernel3_timed = cnt[3];
+            c->kernel_timed = cnt[1]; c->kernel2_timed = cnt[2];
         }
         return 0;
     }
@@ -2706,24 +2621,6 @@ static int dbg_clocks_dump(evpk_ctx *c) {
         for (int k = 0; k < 65535; k++) if (h[(size_t)4 * k]) fprintf(fp, "%d %llu %llu %llx\n", k, h[(size_t)4 * k], h[(size_t)4 * k + 1], h[(size_t)4 * k + 2]);
         fclose(fp);
     }
-    return 0;
-}
-
-// three subcycles in one launch (k_subcycle3w)
-static int step_triple(SubLoop &L, SubArgs &a) {
-    evpk_ctx *c = L.c;
-    a.strips = c->d_strips3; a.nstrips = c->ns_tot3_cur; a.nsdev = c->d_ns3; a.ncx = c->ncx3; a.R = c->R3; a.G = 0;
-    a.wrap = (c->ew == EVPK_BND_CYCLIC) ? 1 : 0;
-    if (L.join()) return 1;
-    if (L.t.begin(c->stream, 3)) return 1;
-    launch_sub3(c, a, c->stream, L.revp);
-    if (L.t.end()) return 1;
-    c->kernel_launches++;
-    c->triple_launches++;
-    L.evE_valid = false;
-    c->ksub += 3;
-    L.n += 3;
-    c->cur ^= 1;
     return 0;
 }
 
@@ -2967,18 +2864,15 @@ static int subcycle_impl(evpk_ctx *c, int32_t nsub) {
         // (a small slab on a one-rank tripole grid: the band sequence of a pair -- two band launches, two folds, two hand-overs
         // between the streams, ~35 us -- costs more than two one-row-per-wave launches with their folds on one stream: 2.4 ms
         // against 1.9 per evp at 360x300, even at 720x540, measured again with the stream-memory hand-overs)
-        const bool fused_band = c->band_mode && c->band_fused && L.wrap && (c->prefetch || c->tile_mode) && s.nyl >= 4;      // see band_fused
+        const bool fused_band = c->band_mode && c->band_fused && L.wrap && s.nyl >= 4;      // see band_fused
         const bool xb = c->xband && !fused_band;
         const bool pairs = c->use_double && !c->eap && (fused_band || !(c->band_mode && c->tile_mode && c->nranks == 1 && !c->force_exchange));
         const bool pair_inside = pairs && left >= 2 && c->ksub + 2 < c->p.ndte;
-        // ... or when the second of them is the last one (k_subcycle2<.., LAST2>; tripole: the second band launch is then
+        // ... or when the second of them is the last one (the pair kernels' LAST2 variants; tripole: the second band launch is then
         // the LAST variant of k_subcycle)
         const bool pair_ends_evp = pairs && left >= 2 && (c->ksub + 2 == c->p.ndte);
         if (dbg_clocks_arm(c, a)) return 1;
-        // three subcycles in one launch (k_subcycle3w) while at least one more follows in this evp: the evp then ends with the pair /
-        // single launches below, which write the diagnostics of the last subcycle
-        if (c->use_triple && left >= 3 && c->ksub + 3 < c->p.ndte) { if (step_triple(L, a)) return 1; }
-        else if (pair_inside || pair_ends_evp) { if (step_pair(L, a, fused_band, xb, pair_ends_evp)) return 1; }
+        if (pair_inside || pair_ends_evp) { if (step_pair(L, a, fused_band, xb, pair_ends_evp)) return 1; }
         else if (step_single(L, a)) return 1;
     }
     if (L.t.close()) return 1;
@@ -2991,7 +2885,6 @@ static int subcycle_impl(evpk_ctx *c, int32_t nsub) {
     HIPCHK(c, hipEventElapsedTime(&c->loop_ms, c->ev0, c->ev1));
     if (dbg_clocks_dump(c)) return 1;
     if (c->dev_strips) take_counts(c);   // what evpk_prep left in flight has arrived with the loop's last event
-    if (c->use_triple) c->nstrips3 = (int)(c->h_counts[3] & 0xffffffffull);
     if (xp_check(c)) return 1;
     if (ov_trying) {
         if (c->ov_trial >= 1) c->ov_ms[c->ov_trial - 1] = c->loop_ms;
@@ -3834,7 +3727,7 @@ extern "C" int evpk_get_stats(evpk_ctx *c, evpk_stats *o) {
     o->nstrips = c->nstrips; o->nstrips_total = c->ncx * c->nry;
     o->subcycles_done = c->ksub;
     o->loop_ms = c->loop_ms;
-    o->kernel_ms = c->kernel_ms; o->kernel_launches = c->kernel_launches - c->double_launches - c->triple_launches;
+    o->kernel_ms = c->kernel_ms; o->kernel_launches = c->kernel_launches - c->double_launches;
     o->kernel2_ms = c->kernel2_ms; o->kernel2_launches = c->double_launches;
     o->strip_rows = c->R; o->strip_rows2 = c->use_double ? c->R2 : 0; o->nstrips2 = c->use_double ? c->nstrips2 : 0;
     o->zone_cols = c->zone_mode ? c->zW : 0; o->zone_exchanges = c->zone_exchanges; o->zone_bytes = c->zone_bytes;
@@ -3845,8 +3738,8 @@ extern "C" int evpk_get_stats(evpk_ctx *c, evpk_stats *o) {
     o->compact_metrics = c->compact ? 1 : 0;
     o->transport = c->ipc ? EVPK_XP_IPC : c->relay ? EVPK_XP_SHM_RELAY : (c->xranks > 1 ? EVPK_XP_RCCL : (c->comm ? EVPK_XP_RCCL : (c->force_exchange ? EVPK_XP_SELF : EVPK_XP_NONE)));
     o->band_row_exchanges = c->xb_swaps;
-    o->kernel3_ms = c->kernel3_ms; o->kernel3_launches = c->triple_launches; o->kernel3_timed = c->kernel3_timed;
-    o->strip_rows3 = c->use_triple ? c->R3 : 0; o->nstrips3 = c->use_triple ? c->nstrips3 : 0;
+    o->kernel3_ms = 0.f; o->kernel3_launches = 0; o->kernel3_timed = 0;      // reserved, always 0 (read by bench.py)
+    o->strip_rows3 = 0; o->nstrips3 = 0;
     int nr = 0;
     if (c->comm && ncclCommCount(c->comm, &nr) != ncclSuccess) nr = -1;
     o->rccl_ranks = nr;

@@ -4,7 +4,7 @@
 // reference spells out, so results are bit-comparable with a non-FMA CPU build.
 // fp64 sqrt and divide lower to correctly rounded sequences on gfx950.
 //
-// Hot kernels: k_subcycle2p / k_subcycle2 -- one launch = TWO EVP subcycles, and k_subcycle -- one launch = one EVP
+// Hot kernels: k_subcycle2p (and its tile variants) -- one launch = TWO EVP subcycles, and k_subcycle -- one launch = one EVP
 // subcycle = stress (ice_dyn_evp.F90:520-849) fused with stepu (ice_dyn_shared.F90:623-748).  The str(:,:,1:8)
 // work array of the reference never reaches HBM: it lives in registers and moves between lanes with DPP wave
 // shifts.  u, v and the twelve sigma planes are double buffered (read buffer `cur`, write buffer `cur^1`) so that
@@ -1082,8 +1082,8 @@ struct SubArgs {
     int nstrips, ncx, R, wrap;
     int sr, sw;        // field ids of the state buffer read / written (F_STATE0, F_STATE1 or F_STATE2)
     int jb0;           // > 0: band launch -- every strip starts at row jb0 (tripole top band), strips[] holds cx only
-    int jmax;          // k_subcycle2: rows above are not stored (tripole, single rank: the band launches own rows >= nyl-1)
-    int G;             // k_subcycle2 in ghost-zone mode: columns 1-G .. nxl+G are advanced (zones of G+2 columns per side)
+    int jmax;          // pair kernels: rows above are not stored (tripole, single rank: the band launches own rows >= nyl-1)
+    int G;             // pair kernels in ghost-zone mode: columns 1-G .. nxl+G are advanced (zones of G+2 columns per side)
     const Slab *xm;    // != nullptr (x-slab ranks on a tripole grid): the mirror slab M of band_pair, a Slab struct in device memory
     __device__ const Slab *xm_slab() const { return xm; }
     const int *nsdev;  // != nullptr: the number of entries of strips[] lives on the device (k_compact_strips wrote list and count; the
@@ -1615,18 +1615,16 @@ __device__ __forceinline__ int pair_nstrips(const SubArgs &a) {
     return a.nsdev ? __builtin_amdgcn_readfirstlane(*a.nsdev) : a.nstrips;
 }
 
-// (k_subcycle2 itself -- the pair kernel WITHOUT the LDS prefetch, superseded by k_subcycle2p in round 1 -- lives in evpk_experimental.hip,
-//  built with -DEVPK_EXPERIMENTAL only)
-
 // ------------------------------------------------------------------------------------
-// k_subcycle2p: k_subcycle2 with the next row's planes prefetched through LDS.
-// In k_subcycle2 a wave spends half of its life in s_waitcnt (225 VGPRs leave two waves per SIMD to hide HBM
-// latency, and register prefetch has no room).  Here every step first issues direct global->LDS loads
+// k_subcycle2p: the marching pair kernel -- one wave per strip of STRIP2_W columns x R rows, two subcycles while it marches
+// north -- with the next row's planes prefetched through LDS.  (Its predecessor loaded every row straight into registers: a wave
+// spent half of its life in s_waitcnt, 225 VGPRs left two waves per SIMD to hide HBM latency and register prefetch had no room;
+// it was superseded in round 1 and retired, see DESIGN.md.)  Here every step first issues direct global->LDS loads
 // (global_load_lds_dwordx4: no VGPR destination, 1 KiB per wave instruction) for the row it will need in the NEXT
 // step -- u/v at the two columns, five metric pairs, six sigma pairs of row r+1 and the stepu input pairs of
 // row r -- then computes the current step from registers; the next step reads its operands from LDS.
 // One 18 KiB ring slot per wave, 72 KiB per 256-thread workgroup, two workgroups per CU.
-// The arithmetic and the results are those of k_subcycle2.
+// The arithmetic is that of two k_subcycle launches in the same order: the results are bit-identical to them.
 // ------------------------------------------------------------------------------------
 // the eight metric planes from the primary grid lengths (ice_grid.F90:356-357, :362-367, :1455, :1533):
 //   hn = HTN(i,j), hs = HTN(i,j-1), he = HTE(i,j), hw = HTE(i-1,j)
@@ -2083,7 +2081,7 @@ __global__ __launch_bounds__(256, 2) void k_subcycle2p(SubArgs a) {      // two 
         }
     };
 
-    // ---- carried state (as in k_subcycle2) ----
+    // ---- carried state: what one march step hands to the next ----
     double uo_c = 0.0, vo_c = 0.0, uo_m = 0.0, vo_m = 0.0;
     double a1c = 0.0, a5c = 0.0, a2r = 0.0, a7r = 0.0;
     Sig g1p{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -2272,8 +2270,8 @@ template __global__ void k_subcycle2p<false, false, true, true>(SubArgs);
 template __global__ void k_subcycle2p<true, false, true, true>(SubArgs);
 
 // ------------------------------------------------------------------------------------
-// k_subcycle2t: the two fused subcycles of k_subcycle2 WITHOUT the north march -- the small-slab variant.
-// k_subcycle2 gives one wave a strip of 61 columns x R rows and lets it march north, R + 3 dependent steps of ~3 us each:
+// k_subcycle2t: the two fused subcycles of k_subcycle2p WITHOUT the north march -- the small-slab variant.
+// k_subcycle2p gives one wave a strip of 61 columns x R rows and lets it march north, R + 3 dependent steps of ~3 us each:
 // fine when there are more strips than wave slots, but a 320 x 384 grid (or one eighth of the 3600 x 2700 grid per GPU)
 // has fewer, and the launch then lasts as long as ONE wave's serial march whatever the chip could do in parallel.
 // Here a workgroup of R + 3 waves takes the same strip and every wave takes ONE row of it, r = jb - 1 + w:
@@ -2282,7 +2280,7 @@ template __global__ void k_subcycle2p<true, false, true, true>(SubArgs);
 //   phase C  T2(r)      waves 1 .. R+1       -> LDS: the same four terms of the second subcycle; sigma stored for waves 1 .. R
 //   phase D  U2(r)      waves 1 .. R         -> (u, v) stored
 // three workgroup barriers instead of R + 3 march steps; E-W neighbours still travel by DPP wave shifts.  Same strips,
-// same column / ghost-zone / tripole-band (jmax) rules, same arithmetic in the same order: bit-identical to k_subcycle2.
+// same column / ghost-zone / tripole-band (jmax) rules, same arithmetic in the same order: bit-identical to k_subcycle2p.
 // LDS: two arrays of [waves][4][64] doubles (the first one serves phases A and C).
 // ------------------------------------------------------------------------------------
 template <bool REVP, bool LAST2, bool XM>
@@ -2728,40 +2726,37 @@ template __global__ void k_subcycle2r<true, true>(SubArgs);
 template __global__ void k_subcycle2r<false, false, true>(SubArgs);
 template __global__ void k_subcycle2r<true, false, true>(SubArgs);
 
-// strip activity for k_subcycle2: any active T / U cell in the window the strip touches
-// (columns c0..c0+63 wrapped, rows jb-1..jb+R+1)
+// strip activity for the pair kernels: any active T / U cell in the window the strip touches
+// (columns c0..c0+63 wrapped, rows jb-1..jb+R+1: STRIP2_W owned columns from lane 1 on, one row read beyond the owned ones)
 // cells: if given, also counts the active T / U cells on the physical cells each strip owns (icellt, icellu of the rank)
-// W, own0, rmar: strip width, first owned lane and the rows read beyond the owned ones -- 61, 1, 1 for the pair kernels, 59, 2, 2
-// for k_subcycle3w
 __global__ void k_strip_flags2(Slab s, int ncx, int nry, int R, int cyc, int G, unsigned char *flags, unsigned int *count,
-                               unsigned long long *cells = nullptr, int W = STRIP2_W, int own0 = 1, int rmar = 1,
-                               unsigned char *work = nullptr /* rows of the window with an active cell (<= 255): the strip's run time */) {
+                               unsigned long long *cells = nullptr) {
     const int sid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (sid >= ncx * nry) return;
     const int cx = sid % ncx, ry = sid / ncx;
-    const int c = cx * W + lane - (own0 - 1) - G;
+    const int c = cx * STRIP2_W + lane - G;
     int ci = c;
     bool ok;
     if (cyc) { ci = (c - 1) % s.nxl; if (ci < 0) ci += s.nxl; ci += 1; ok = true; }
     else ok = (c >= -G && c <= s.nxl + 2 + G);
     const int jb = ry * R + 1;
-    int any = 0, nt = 0, nu = 0, nrows = 0;
-    const bool owned = (lane >= own0 && lane <= own0 + W - 1 && c >= 1 && c <= s.nxl);
+    int any = 0, nt = 0, nu = 0;
+    const bool owned = (lane >= 1 && lane <= STRIP2_W && c >= 1 && c <= s.nxl);
     {   // quick reject: cmask is non-zero only where k_prep2 ran, i.e. in tiles of act_any -- 74 % of the bench grid has none
         // (tiles: TILE_X x TILE_Y cells, the thread blocks of the per-evp kernels; columns beyond the ring count as the edge tile)
-        const int jlo = max(jb - rmar, 1), jhi = min(jb + R + rmar, s.nyl + 1);
+        const int jlo = max(jb - 1, 1), jhi = min(jb + R + 1, s.nyl + 1);
         const int tx = min(max(ci, 0), s.nxl + 1) / TILE_X;
         bool hit = false;
         if (ok)
             for (int ty = jlo / TILE_Y; ty <= jhi / TILE_Y; ty++) hit = hit || s.act_any[ty * s.ntx + tx] != 0;
         if (!__any(hit)) {
-            if (lane == 0) { if (flags) flags[sid] = 0; if (work) work[sid] = 0; }
+            if (lane == 0 && flags) flags[sid] = 0;
             return;
         }
     }
-    const int rend = jb + R + rmar;
-    for (int r0 = jb - rmar; r0 <= rend; r0 += 8) {           // eight rows' mask bytes in flight at a time
+    const int rend = jb + R + 1;
+    for (int r0 = jb - 1; r0 <= rend; r0 += 8) {           // eight rows' mask bytes in flight at a time
         unsigned char mm[8];
 #pragma unroll
         for (int q = 0; q < 8; q++) {
@@ -2773,11 +2768,9 @@ __global__ void k_strip_flags2(Slab s, int ncx, int nry, int R, int cyc, int G, 
             const int r = r0 + q;
             const unsigned char m = mm[q];
             if (m) any = 1;
-            if (work && __ballot(m != 0)) nrows++;
             if (owned && r >= jb && r < jb + R && r <= s.nyl) { nt += (m & CM_T) ? 1 : 0; nu += (m & CM_U) ? 1 : 0; }
         }
     }
-    if (work && lane == 0) work[sid] = (unsigned char)min(nrows, 255);
     const unsigned long long b = __ballot(any);
     if (cells) {
         for (int o = 32; o > 0; o >>= 1) { nt += __shfl_down(nt, o); nu += __shfl_down(nu, o); }
@@ -2861,24 +2854,6 @@ __global__ __launch_bounds__(1024) void k_compact_strips(const unsigned char *fl
         __syncthreads();
     }
     if (threadIdx.x == 0) *count = base;
-}
-
-// the active strips (work > 0) in order of DESCENDING work -- longest first, so that the workgroups the dispatcher hands out last
-// are the short ones and the launch's tail is short (k_subcycle3w runs its strips in two or three rounds of resident workgroups).
-// One workgroup: histogram, offsets, scatter (the order inside a class of equal work is arbitrary: it changes no result).
-__global__ __launch_bounds__(1024) void k_sort_strips(const unsigned char *work, int n, int *list, int *count) {
-    __shared__ int hist[256], cur[256];
-    for (int k = threadIdx.x; k < 256; k += blockDim.x) hist[k] = 0;
-    __syncthreads();
-    for (int k = threadIdx.x; k < n; k += blockDim.x) if (work[k]) atomicAdd(&hist[work[k]], 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int off = 0;
-        for (int w = 255; w >= 1; w--) { cur[w] = off; off += hist[w]; }
-        *count = off;
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < n; k += blockDim.x) if (work[k]) list[atomicAdd(&cur[work[k]], 1)] = k;
 }
 
 // ------------------------------------------------------------------------------------

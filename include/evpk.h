@@ -144,9 +144,9 @@ typedef struct {
                                 consecutive launches (launches 3..8 of every 20 by default; EVPK_TIME_KERNELS=2: every launch, 0: none),
                                 span time / launches in the spans x number of launches -- never more than loop_ms */
     int32_t kernel_launches; /* ... and their number */
-    float kernel2_ms;        /* the same for the two-subcycle kernel (k_subcycle2) */
+    float kernel2_ms;        /* the same for the two-subcycle kernels (k_subcycle2p and its tile variants) */
     int32_t kernel2_launches;
-    int32_t strip_rows, strip_rows2;   /* strip heights in use: k_subcycle, k_subcycle2 (auto-tuned) */
+    int32_t strip_rows, strip_rows2;   /* strip heights in use: k_subcycle, the two-subcycle kernels (auto-tuned) */
     int32_t nstrips2;
     int32_t zone_cols;                 /* x-slabs: ghost-zone width per side (2 x launches per exchange); 0 = no ghost zones */
     int32_t zone_exchanges;            /* ghost-zone exchanges with the slab neighbours in the last evpk_subcycle call */
@@ -165,9 +165,9 @@ typedef struct {
     int32_t band_row_exchanges;        /* x-slab ranks on a tripole grid: refreshes of the mirror slab in the last evpk_subcycle call -- one message
                                           per rank that owns columns of it, ghost zones included (the mirror rank and its neighbours with equal slabs: up to three ranks), posted
                                           together with the ghost-zone exchange; the fold itself runs inside the pair launches (band_pair) */
-    float kernel3_ms;                  /* the same as kernel2_ms for the three-subcycle pipeline kernel (k_subcycle3w) */
-    int32_t kernel3_launches, kernel3_timed;
-    int32_t strip_rows3, nstrips3;     /* its strip height and active strips */
+    float kernel3_ms;                  /* reserved, always 0 (read by bench.py) */
+    int32_t kernel3_launches, kernel3_timed;   /* reserved, always 0 (read by bench.py) */
+    int32_t strip_rows3, nstrips3;     /* reserved, always 0 (read by bench.py) */
     int32_t rccl_ranks;                /* ncclCommCount of the context's communicator (0: no RCCL communicator) */
     int32_t device;                    /* hipGetDevice ordinal the context runs on */
     int32_t device_pci;                /* (PCI domain << 16) | (bus << 8) | device of that GPU: distinct per physical device */
@@ -374,9 +374,6 @@ int evpk_unpin_host(void *ptr);
 int evpk_host_alloc(size_t bytes, void **out);
 int evpk_host_free(void *ptr);
 int evpk_host_is_mapped(const void *ptr, size_t bytes);
-/* 1 if the library was built with -DEVPK_EXPERIMENTAL (it then contains k_subcycle2 and k_subcycle3w -- measured, not adopted -- and
- * honours EVPK_PREFETCH=0 / EVPK_TRIPLE=1; the product build refuses them) */
-int evpk_experimental_built(void);
 const char *evpk_last_error(const evpk_ctx *c);  /* c may be NULL: error of the last failed evpk_create */
 
 /* Host-only description of this rank's halo exchange (no GPU needed): neighbours in the

@@ -13,10 +13,6 @@ from tests import util
 
 pytestmark = pytest.mark.gpu
 
-# k_subcycle2 (EVPK_PREFETCH=0) and k_subcycle3w (EVPK_TRIPLE=1) were measured and not adopted: the product library does not contain them
-# (csrc/evpk_experimental.hip).  Their tests run against the other build: EVPK_LIB=cice5_amd/libevpk_exp.so python -m pytest tests -m gpu -k three_subcycle
-needs_experimental = pytest.mark.skipif(not evpk.experimental(), reason="kernels of evpk_experimental.hip: EVPK_LIB=cice5_amd/libevpk_exp.so")
-
 
 def _both(nx, ny, bsx, bsy, *, ndte=120, dt=3600.0, ncalls=1, revised_evp=False, cosw=1.0, sinw=0.0,
           tilt_from_slope=False, wind_on_ugrid=False, ns="open", nsub=None, pin_host=False, **kw):
@@ -229,7 +225,7 @@ def test_forced_exchange_path(ns, monkeypatch):
 
 
 def test_two_subcycle_kernel_equals_single(monkeypatch):
-    """k_subcycle2 (two subcycles per launch) vs k_subcycle only: bit-identical, including odd ndte,
+    """k_subcycle2p (two subcycles per launch) vs k_subcycle only: bit-identical, including odd ndte,
     subcycles issued in odd pieces, revised EVP, and a non-cyclic E-W boundary.  (EVPK_TILE=0: the marching kernels; on a
     one-rank tripole grid this small the tuner would otherwise drop the pairs for one-row-per-wave single launches.)"""
     monkeypatch.setenv("EVPK_TILE", "0")
@@ -255,59 +251,25 @@ def test_two_subcycle_kernel_equals_single(monkeypatch):
         assert not util.compare(d, outs[1], outs[0])
 
 
-@needs_experimental
-@pytest.mark.parametrize("R3", ["", "3", "7", "40"])
-def test_three_subcycle_kernel_equals_single(R3, monkeypatch):
-    """k_subcycle3w (three subcycles per launch, one wave per subcycle stage, sigma and (u, v) handed from stage to stage through
-    the LDS) vs k_subcycle only: bit-identical -- ndte with every remainder mod 3, subcycles issued in odd pieces, revised EVP, a
-    non-cyclic E-W boundary, grids narrower / wider than one 58-column strip, strip heights 3, 7, 24 (default) and 40."""
-    monkeypatch.setenv("EVPK_TILE", "0")
-    if R3:
-        monkeypatch.setenv("EVPK_STRIP_ROWS3", R3)
-    for (nx, ny), kw, ndte, pieces in [((130, 96), dict(land="continents"), 31, [31]), ((130, 96), dict(land="continents"), 41, [7, 12, 22]),
-                                       ((130, 96), dict(ice="full"), 24, [24]), ((200, 75), dict(land="continents"), 36, [36]),
-                                       ((57, 40), dict(ice="full"), 17, [4, 13]), ((117, 64), dict(land="continents", ew="open"), 30, [30])]:
-        ew = kw.pop("ew", "cyclic")
-        case = synth.SynthCase(nx=nx, ny=ny, ew_boundary=C.BND_NAMES[ew], **kw)
-        d = blocks.create_distrb_cart(nx, ny, nx, ny, ew_boundary_type=ew)
-        f = synth.make_block_fields(case, d)
-        xmin = synth.global_min_dx(case)
-        outs = []
-        for mode in ("single", "triple"):
-            monkeypatch.setenv("EVPK_DOUBLE", "0" if mode == "single" else "1")
-            monkeypatch.setenv("EVPK_TRIPLE", "0" if mode == "single" else "1")
-            g = util.clone(f)
-            s = dyn.EvpDynamics(d, g, ndte=ndte, xmin=xmin, revised_evp=(ndte == 24))
-            s.init_evp(3600.0)
-            s.ctx.upload(g); s.ctx.prep()
-            for n in pieces:
-                s.ctx.subcycle(n)
-            st = s.ctx.stats()
-            assert (st.kernel3_launches > 0) == (mode == "triple"), (mode, st.kernel3_launches)
-            s.ctx.finish(); s.ctx.download(g)
-            s.close()
-            outs.append(g)
-        bad = util.compare(d, outs[1], outs[0])
-        assert not bad, ((nx, ny), kw, ndte, bad[:4])
-        assert np.abs(outs[0]["uvel"]).max() > 1e-4
-
-
-@needs_experimental
-def test_three_subcycle_kernel_equals_oracle(monkeypatch):
-    """the same kernel against the oracle: BASELINE config 3's grid in 24 blocks and a 3-call warm start (new / lost ice)"""
-    monkeypatch.setenv("EVPK_TILE", "0")
-    monkeypatch.setenv("EVPK_TRIPLE", "1")
-    seen = []
-    real = dyn.EvpDynamics.close
-
-    def close(self):
-        seen.append(int(self.ctx.stats().kernel3_launches))
-        real(self)
-
-    monkeypatch.setattr(dyn.EvpDynamics, "close", close)
-    _both(360, 300, 15, 300, land="continents", ndte=24, ncalls=2)
-    _both(320, 384, 80, 96, ndte=31, ncalls=3)
-    assert all(n > 0 for n in seen), seen
+def test_retired_kernel_knobs_are_refused(monkeypatch):
+    """EVPK_TRIPLE=1 and EVPK_PREFETCH=0 asked for pair kernels that were measured, not adopted and retired: evpk_create still refuses
+    both and names the knob.  EVPK_TRIPLE=0 / EVPK_PREFETCH=1 stay no-ops: the pairs run and the reserved three-subcycle stats are 0."""
+    monkeypatch.setenv("EVPK_TILE", "0")      # (the tuner would otherwise drop the pairs on so small a slab)
+    case, d, f = util.make_case(16, 12, 16, 12)
+    xmin = synth.global_min_dx(case)
+    for knob, value in (("EVPK_TRIPLE", "1"), ("EVPK_PREFETCH", "0")):
+        with monkeypatch.context() as m:
+            m.setenv(knob, value)
+            with pytest.raises(evpk.EvpkError, match=knob):
+                dyn.EvpDynamics(d, util.clone(f), ndte=4, xmin=xmin)
+    monkeypatch.setenv("EVPK_TRIPLE", "0")
+    monkeypatch.setenv("EVPK_PREFETCH", "1")
+    s = dyn.EvpDynamics(d, util.clone(f), ndte=4, xmin=xmin)
+    s.init_evp(3600.0)
+    s.evp(3600.0)
+    st = s.ctx.stats()
+    s.close()
+    assert st.kernel3_launches == 0 and st.kernel2_launches > 0, (st.kernel3_launches, st.kernel2_launches)
 
 
 @pytest.mark.parametrize("H", ["", "2", "5", "13"])
