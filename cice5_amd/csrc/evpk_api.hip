@@ -345,11 +345,7 @@ struct evpk_ctx {
     long long last_dl[F_COUNT] = {};  // evp_count at which each field was last downloaded (state fields under their F_STATE0 ids)
     bool io_sparse_now = false;      // the last evpk_upload was a sparse one: evpk_download may skip inactive tiles too
     bool tile_mode = false;          // the pairs run k_subcycle2t (one row per wave, no march): chosen by tune_R2 when strips are scarce
-    int tile_force = -1;             // EVPK_TILE=0 / 1 fixes the choice
-    // k_subcycle2r: the tile kernel that rolls north through strips of any height in passes of ROLL_NW - 2 rows, without the three
-    // redundant rows per tile (round 5).  EVPK_TILE=2 forces it, EVPK_TILE=1 the five-row tiles; else tune_R2 prices both
-    bool tile_roll = false;
-    int roll_force = -1;
+    int tile_force = -1;             // EVPK_TILE=0 / 1 fixes the choice (2 asked for the rolling tile kernel of round 5: retired, refused)
     unsigned int *d_tune = nullptr;
     bool use_double = false;
     unsigned char *d_flags2 = nullptr;
@@ -1209,13 +1205,7 @@ static void launch_sub2(evpk_ctx *c, const SubArgs &a_in, hipStream_t st, bool r
     // XM excludes LAST2 (the mirror slab is only advanced when another pair follows): <*, true, *, true> is never named
     with_bool(revp, [&](auto RV) {
         constexpr bool rv = decltype(RV)::value;
-        if (c->tile_mode && c->tile_roll) {      // ... rolling north through a strip of R rows: min(R + 3, ROLL_NW) waves per workgroup
-            const int nw = std::min(a.R + 3, ROLL_NW);
-            const dim3 b(nw * 64);
-            const size_t lds = std::max((size_t)nw * ROLL_LDS_PER_WAVE, band_lds);
-            if (xm) hipLaunchKernelGGL((k_subcycle2r<rv, false, true>), g, b, lds, st, a);
-            else with_bool(last2, [&](auto L2) { hipLaunchKernelGGL((k_subcycle2r<rv, decltype(L2)::value>), g, b, lds, st, a); });
-        } else if (c->tile_mode) {               // small-slab variant: one workgroup of R + 3 waves per strip, one row per wave
+        if (c->tile_mode) {                      // small-slab variant: one workgroup of R + 3 waves per strip, one row per wave
             const dim3 b((a.R + 3) * 64);
             const size_t lds = std::max((size_t)(a.R + 3) * (4096 + 5 * 1024), band_lds);
             if (xm) hipLaunchKernelGGL((k_subcycle2t<rv, false, true>), g, b, lds, st, a);
@@ -1782,7 +1772,12 @@ static int create_impl(evpk_ctx *c, const evpk_geom *g) {
     }
     // the pair kernel without the LDS prefetch was measured and not adopted: retired, see DESIGN.md
     { const char *e = getenv("EVPK_PREFETCH"); if (e && atoi(e) == 0) FAIL(c, "EVPK_PREFETCH=0 selects k_subcycle2, which was retired (last held by commit 11c5403)"); }
-    { const char *e = getenv("EVPK_TILE"); c->tile_force = e ? (atoi(e) != 0 ? 1 : 0) : -1; c->roll_force = e ? (atoi(e) == 2 ? 1 : 0) : -1; }
+    // the tile kernel that rolls north through its strip was measured and not adopted: retired, see DESIGN.md
+    {
+        const char *e = getenv("EVPK_TILE");
+        if (e && atoi(e) == 2) FAIL(c, "EVPK_TILE=2 selects k_subcycle2r, which was retired (last held by commit 2a9e752)");
+        c->tile_force = e ? (atoi(e) != 0 ? 1 : 0) : -1;
+    }
     { const char *e = getenv("EVPK_VERIFY_DELIVERY"); c->verify_delivery = e ? atoi(e) : 0; }
     { const char *e = getenv("EVPK_XFER_FUSED"); c->xfer_fused = !(e && atoi(e) == 0); }
     c->nsimd = 4 * prop.multiProcessorCount;
@@ -2019,15 +2014,14 @@ static int tune_R2(evpk_ctx *c) {
     const char *e = getenv("EVPK_STRIP_ROWS");
     if (e && atoi(e) > 0) {
         c->tile_mode = (c->tile_force == 1);
-        c->tile_roll = c->tile_mode && c->roll_force == 1;
-        c->R2 = std::max(1, std::min(atoi(e), (c->tile_mode && !c->tile_roll) ? 13 : 64)); c->nry2 = (c->s.nyl + 1 + c->R2 - 1) / c->R2;
+        c->R2 = std::max(1, std::min(atoi(e), c->tile_mode ? 13 : 64)); c->nry2 = (c->s.nyl + 1 + c->R2 - 1) / c->R2;
         return 0;
     }
     // icellt of this prep is not known yet on the host; use the previous one as the trigger
     if (c->tuned_icellt >= 0 && std::llabs(c->icellt - c->tuned_icellt) * 20 <= c->tuned_icellt) return 0;
     static const int cand[] = {2, 3, 4, 5, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32, 36, 40, 48};
     static const int tcand[] = {2, 3, 4, 5, 6, 8, 10, 13};        // tile heights of k_subcycle2t: R + 3 <= 16 waves per workgroup
-    static const int rcand[] = {11, 17, 23, 29, 35, 47, 59};      // strip heights of k_subcycle2r: R + 3 = ROLL_NW + k (ROLL_NW - 2), whole passes
+    static const int rcand[] = {11, 17, 23, 29, 35, 47, 59};      // strip heights of the retired rolling tile kernel, see below: R + 3 = 8 + 6 k
     const int ncand = (int)(sizeof(cand) / sizeof(cand[0])), ntc = (int)(sizeof(tcand) / sizeof(tcand[0])), nrc = (int)(sizeof(rcand) / sizeof(rcand[0]));
     Slab &s = c->s;
     HIPCHK(c, hipMemsetAsync(c->d_tune, 0, sizeof(unsigned int) * 64, c->stream));
@@ -2065,25 +2059,26 @@ static int tune_R2(evpk_ctx *c) {
         const double cost = 3.6 * per_simd + 6.0;
         if (cost < bestT * 0.999) { bestT = cost; bestH = tcand[k]; }
     }
-    // the rolling tile kernel: the same wave-rows without the three redundant rows per tile, passes of ROLL_NW - 2 rows behind one
-    // another in a workgroup (two waves per SIMD and pass at least), four barriers per pass
+    // The estimate of a RETIRED kernel: the tile kernel of round 5 that rolled north through a strip in passes of six rows, eight
+    // waves per workgroup, without the three redundant rows per tile (four barriers per pass).  It was measured and not adopted
+    // (profiles/r05_v1/roll_ab.txt: 26 % fewer rows computed, the same rows per microsecond -- the small slabs are bound by the
+    // latency of a workgroup's phase chain, not by the arithmetic) and the tuner never launched it, but its estimate has always been
+    // part of the comparison below and still tips the choice to k_subcycle2t on mid-size slabs (1440x1080 tripole: march 52.8,
+    // tile 53.0, this term 43.0 us).  Kept because removing it changes which kernel runs there; to be replaced only together with
+    // a measurement on those grids, as ADVICE.md asks.  It feeds tile_mode only: R2 is bestH or bestR.
+    constexpr int roll_nw = 8;      // waves per workgroup of that kernel
     double bestRo = 1e300;
-    int bestRr = rcand[0];
     for (int k = 0; k < nrc; k++) {
         const unsigned int nt = cnt[ncand + ntc + k];
         if (nt == 0 || rcand[k] + 3 > s.nyl + 8) continue;
-        const int passes = 1 + (rcand[k] + 3 - ROLL_NW) / (ROLL_NW - 2);
+        const int passes = 1 + (rcand[k] + 3 - roll_nw) / (roll_nw - 2);
         const double per_simd = std::max(2.0 * passes, (double)nt * (rcand[k] + 3) / (double)c->nsimd);
         const double cost = 3.6 * per_simd + 6.0 + 0.6 * passes;
-        if (cost < bestRo * 0.999) { bestRo = cost; bestRr = rcand[k]; }
+        if (cost < bestRo * 0.999) bestRo = cost;
     }
     c->tile_mode = c->tile_force >= 0 ? (c->tile_force == 1) : (std::min(bestT, bestRo) < best);
     if (best > 1e299 && bestT > 1e299) c->tile_mode = false;
-    // (measured, profiles/r05_v1/roll_ab.txt: the rolling kernel computes 26 % fewer rows and delivers the same rows per microsecond --
-    //  six of its eight waves work in a phase, four barriers per pass: the small slabs are bound by the latency of a workgroup's phase
-    //  chain, not by the arithmetic -- so the tuner never takes it; EVPK_TILE=2 does)
-    c->tile_roll = c->tile_mode && c->roll_force == 1 && bestRo < 1e299;
-    c->R2 = c->tile_mode ? (c->tile_roll ? bestRr : bestH) : bestR;
+    c->R2 = c->tile_mode ? bestH : bestR;
     c->nry2 = (s.nyl + 1 + c->R2 - 1) / c->R2;
     c->tuned_icellt = -2;      // set from the counts of this prep below
     return 0;
@@ -3732,7 +3727,7 @@ extern "C" int evpk_get_stats(evpk_ctx *c, evpk_stats *o) {
     o->strip_rows = c->R; o->strip_rows2 = c->use_double ? c->R2 : 0; o->nstrips2 = c->use_double ? c->nstrips2 : 0;
     o->zone_cols = c->zone_mode ? c->zW : 0; o->zone_exchanges = c->zone_exchanges; o->zone_bytes = c->zone_bytes;
     o->overlap_split = !c->ov_fixed ? -1 : (c->overlap ? 1 : 0);
-    o->tile_kernel = (c->use_double && c->tile_mode) ? (c->tile_roll ? 2 : 1) : 0;
+    o->tile_kernel = (c->use_double && c->tile_mode) ? 1 : 0;
     o->kernel_timed = c->kernel_timed; o->kernel2_timed = c->kernel2_timed;
     o->bound_ms = c->bound_ms; o->bound_updates = c->bound_updates;
     o->compact_metrics = c->compact ? 1 : 0;

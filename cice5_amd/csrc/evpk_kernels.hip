@@ -1166,74 +1166,9 @@ __device__ __forceinline__ void store_sig(char *rb, size_t pp, int SB, unsigned 
     stp(rb, pp, SB + S_S12, lo, g.s121, g.s122);  stp(rb, pp, SB + S_S12 + 2, lo, g.s123, g.s124);
 }
 
-// ---- fp64 sqrt and divide, FOUR AT A TIME (round 4) ----
-// hipcc expands sqrt() and `/` of doubles into dependent chains of 17 and 11 instructions (v_rsq_f64 / v_rcp_f64, Newton steps as
-// fma, v_div_scale / v_div_fmas / v_div_fixup) and emits the four Deltas and the four divisions of a T cell ONE AFTER THE OTHER: 112
-// instructions in which every one waits for the one before it (the profile of k_subcycle2p: one wave alone on its SIMD issues one
-// VALU instruction per 8.4 cycles, a pair per 5.5, where the pipe takes one per 4).  Here the same sequences -- instruction for
-// instruction what the compiler emits (AMDGPU lowering of fsqrt.f64 / fdiv.f64), hence the same correctly rounded results -- are
-// written out for four operands side by side, so that each instruction has three independent neighbours between itself and its
-// consumer.  tests: every parity test runs through them (bit-identical with the oracle's sqrt() and `/`).
-__device__ __forceinline__ void sqrt4_f64(double &x0, double &x1, double &x2, double &x3) {
-    const double tiny = 0x1.0p-767;
-    const bool s0 = x0 < tiny, s1 = x1 < tiny, s2 = x2 < tiny, s3 = x3 < tiny;
-    const double a0 = __builtin_amdgcn_ldexp(x0, s0 ? 256 : 0), a1 = __builtin_amdgcn_ldexp(x1, s1 ? 256 : 0);
-    const double a2 = __builtin_amdgcn_ldexp(x2, s2 ? 256 : 0), a3 = __builtin_amdgcn_ldexp(x3, s3 ? 256 : 0);
-    const double y0 = __builtin_amdgcn_rsq(a0), y1 = __builtin_amdgcn_rsq(a1), y2 = __builtin_amdgcn_rsq(a2), y3 = __builtin_amdgcn_rsq(a3);
-    double g0 = a0 * y0, g1 = a1 * y1, g2 = a2 * y2, g3 = a3 * y3;
-    double h0 = y0 * 0.5, h1 = y1 * 0.5, h2 = y2 * 0.5, h3 = y3 * 0.5;
-    const double r0 = __builtin_fma(-h0, g0, 0.5), r1 = __builtin_fma(-h1, g1, 0.5), r2 = __builtin_fma(-h2, g2, 0.5), r3 = __builtin_fma(-h3, g3, 0.5);
-    g0 = __builtin_fma(g0, r0, g0); g1 = __builtin_fma(g1, r1, g1); g2 = __builtin_fma(g2, r2, g2); g3 = __builtin_fma(g3, r3, g3);
-    double d0 = __builtin_fma(-g0, g0, a0), d1 = __builtin_fma(-g1, g1, a1), d2 = __builtin_fma(-g2, g2, a2), d3 = __builtin_fma(-g3, g3, a3);
-    h0 = __builtin_fma(h0, r0, h0); h1 = __builtin_fma(h1, r1, h1); h2 = __builtin_fma(h2, r2, h2); h3 = __builtin_fma(h3, r3, h3);
-    g0 = __builtin_fma(d0, h0, g0); g1 = __builtin_fma(d1, h1, g1); g2 = __builtin_fma(d2, h2, g2); g3 = __builtin_fma(d3, h3, g3);
-    d0 = __builtin_fma(-g0, g0, a0); d1 = __builtin_fma(-g1, g1, a1); d2 = __builtin_fma(-g2, g2, a2); d3 = __builtin_fma(-g3, g3, a3);
-    g0 = __builtin_fma(d0, h0, g0); g1 = __builtin_fma(d1, h1, g1); g2 = __builtin_fma(d2, h2, g2); g3 = __builtin_fma(d3, h3, g3);
-    g0 = __builtin_amdgcn_ldexp(g0, s0 ? -128 : 0); g1 = __builtin_amdgcn_ldexp(g1, s1 ? -128 : 0);
-    g2 = __builtin_amdgcn_ldexp(g2, s2 ? -128 : 0); g3 = __builtin_amdgcn_ldexp(g3, s3 ? -128 : 0);
-    const int zi = 0x260;       // +inf | +0 | -0: sqrt(x) = x
-    x0 = __builtin_amdgcn_class(a0, zi) ? a0 : g0; x1 = __builtin_amdgcn_class(a1, zi) ? a1 : g1;
-    x2 = __builtin_amdgcn_class(a2, zi) ? a2 : g2; x3 = __builtin_amdgcn_class(a3, zi) ? a3 : g3;
-}
-// q_k = n / d_k
-__device__ __forceinline__ void div4_f64(double n, double d0, double d1, double d2, double d3, double &q0, double &q1, double &q2, double &q3) {
-    bool f0, f1, f2, f3, u0, u1, u2, u3;
-    const double e0 = __builtin_amdgcn_div_scale(n, d0, false, &u0), e1 = __builtin_amdgcn_div_scale(n, d1, false, &u1);
-    const double e2 = __builtin_amdgcn_div_scale(n, d2, false, &u2), e3 = __builtin_amdgcn_div_scale(n, d3, false, &u3);
-    double r0 = __builtin_amdgcn_rcp(e0), r1 = __builtin_amdgcn_rcp(e1), r2 = __builtin_amdgcn_rcp(e2), r3 = __builtin_amdgcn_rcp(e3);
-    double t0 = __builtin_fma(-e0, r0, 1.0), t1 = __builtin_fma(-e1, r1, 1.0), t2 = __builtin_fma(-e2, r2, 1.0), t3 = __builtin_fma(-e3, r3, 1.0);
-    r0 = __builtin_fma(r0, t0, r0); r1 = __builtin_fma(r1, t1, r1); r2 = __builtin_fma(r2, t2, r2); r3 = __builtin_fma(r3, t3, r3);
-    t0 = __builtin_fma(-e0, r0, 1.0); t1 = __builtin_fma(-e1, r1, 1.0); t2 = __builtin_fma(-e2, r2, 1.0); t3 = __builtin_fma(-e3, r3, 1.0);
-    r0 = __builtin_fma(r0, t0, r0); r1 = __builtin_fma(r1, t1, r1); r2 = __builtin_fma(r2, t2, r2); r3 = __builtin_fma(r3, t3, r3);
-    const double m0 = __builtin_amdgcn_div_scale(n, d0, true, &f0), m1 = __builtin_amdgcn_div_scale(n, d1, true, &f1);
-    const double m2 = __builtin_amdgcn_div_scale(n, d2, true, &f2), m3 = __builtin_amdgcn_div_scale(n, d3, true, &f3);
-    const double p0 = m0 * r0, p1 = m1 * r1, p2 = m2 * r2, p3 = m3 * r3;
-    t0 = __builtin_fma(-e0, p0, m0); t1 = __builtin_fma(-e1, p1, m1); t2 = __builtin_fma(-e2, p2, m2); t3 = __builtin_fma(-e3, p3, m3);
-    q0 = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(t0, r0, p0, f0), d0, n);
-    q1 = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(t1, r1, p1, f1), d1, n);
-    q2 = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(t2, r2, p2, f2), d2, n);
-    q3 = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(t3, r3, p3, f3), d3, n);
-}
-// (q0, q1) = (n0, n1) / d: two quotients by one denominator, side by side (stepu)
-__device__ __forceinline__ void div2_f64(double n0, double n1, double d, double &q0, double &q1) {
-    bool f0, f1, u0, u1;
-    const double e0 = __builtin_amdgcn_div_scale(n0, d, false, &u0), e1 = __builtin_amdgcn_div_scale(n1, d, false, &u1);
-    double r0 = __builtin_amdgcn_rcp(e0), r1 = __builtin_amdgcn_rcp(e1);
-    double t0 = __builtin_fma(-e0, r0, 1.0), t1 = __builtin_fma(-e1, r1, 1.0);
-    r0 = __builtin_fma(r0, t0, r0); r1 = __builtin_fma(r1, t1, r1);
-    t0 = __builtin_fma(-e0, r0, 1.0); t1 = __builtin_fma(-e1, r1, 1.0);
-    r0 = __builtin_fma(r0, t0, r0); r1 = __builtin_fma(r1, t1, r1);
-    const double m0 = __builtin_amdgcn_div_scale(n0, d, true, &f0), m1 = __builtin_amdgcn_div_scale(n1, d, true, &f1);
-    const double p0 = m0 * r0, p1 = m1 * r1;
-    t0 = __builtin_fma(-e0, p0, m0); t1 = __builtin_fma(-e1, p1, m1);
-    q0 = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(t0, r0, p0, f0), d, n0);
-    q1 = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(t1, r1, p1, f1), d, n1);
-}
-
 // ---- stress of one T cell (ice_dyn_evp.F90:618-847), the reference's operation order ----
 // u/v naming: _ij = (i,j), _mj = (i-1,j), _im = (i,j-1), _mm = (i-1,j-1).  g: sigma in -> sigma out.
-// ILP: the four Deltas and the four divisions through sqrt4_f64 / div4_f64 (the kernels with registers to spare for it)
-template <bool DIAG, bool ILP = false>
+template <bool DIAG>
 __device__ __forceinline__ void stress_cell(const TMet &m, double u_ij, double u_mj, double u_im, double u_mm,
                                             double v_ij, double v_mj, double v_im, double v_mm,
                                             double ecci, double arlx1i, double denom1, double tarear,
@@ -1263,8 +1198,7 @@ __device__ __forceinline__ void stress_cell(const TMet &m, double u_ij, double u
     double Deltanw = divunw * divunw + ecci * (tensionnw * tensionnw + shearnw * shearnw);
     double Deltase = divuse * divuse + ecci * (tensionse * tensionse + shearse * shearse);
     double Deltasw = divusw * divusw + ecci * (tensionsw * tensionsw + shearsw * shearsw);
-    if (ILP) sqrt4_f64(Deltane, Deltanw, Deltase, Deltasw);
-    else { Deltane = sqrt(Deltane); Deltanw = sqrt(Deltanw); Deltase = sqrt(Deltase); Deltasw = sqrt(Deltasw); }
+    Deltane = sqrt(Deltane); Deltanw = sqrt(Deltanw); Deltase = sqrt(Deltase); Deltasw = sqrt(Deltasw);
 
     if (DIAG) {                                                                     // :665-677
         dg.divu = 0.25 * (divune + divunw + divuse + divusw) * tarear;
@@ -1277,14 +1211,10 @@ __device__ __forceinline__ void stress_cell(const TMet &m, double u_ij, double u
     }
 
     // replacement pressure / Delta (:683-697)
-    double c0ne, c0nw, c0sw, c0se;
-    if (ILP) div4_f64(m.strength, fmax(Deltane, m.tiny), fmax(Deltanw, m.tiny), fmax(Deltasw, m.tiny), fmax(Deltase, m.tiny), c0ne, c0nw, c0sw, c0se);
-    else {
-        c0ne = m.strength / fmax(Deltane, m.tiny);
-        c0nw = m.strength / fmax(Deltanw, m.tiny);
-        c0sw = m.strength / fmax(Deltasw, m.tiny);
-        c0se = m.strength / fmax(Deltase, m.tiny);
-    }
+    double c0ne = m.strength / fmax(Deltane, m.tiny);
+    double c0nw = m.strength / fmax(Deltanw, m.tiny);
+    double c0sw = m.strength / fmax(Deltasw, m.tiny);
+    double c0se = m.strength / fmax(Deltase, m.tiny);
     if (DIAG) dg.prs = c0ne * Deltane;
     const double c1ne = c0ne * arlx1i, c1nw = c0nw * arlx1i, c1sw = c0sw * arlx1i, c1se = c0se * arlx1i;
     c0ne = c1ne * ecci; c0nw = c1nw * ecci; c0sw = c1sw * ecci; c0se = c1se * ecci;
@@ -1358,7 +1288,6 @@ __device__ __forceinline__ UStat load_ustat(const char *ru, size_t pp, unsigned 
     const double2 fo = ldp(ru, pp, F_FORCEX, lo), mf = ldp(ru, pp, F_UMASSDTI, lo);
     return UStat{va.x, va.y, oc.x, oc.y, fo.x, fo.y, mf.x, mf.y};
 }
-template <bool ILP = false>
 __device__ __forceinline__ void stepu_cell(const UStat &q, double uold, double vold, double ui, double vi,
                                            double sx, double sy, double brlx, double revp, double cosw, double sinw,
                                            double &un, double &vn, double &strintx, double &strinty) {
@@ -1376,11 +1305,8 @@ __device__ __forceinline__ void stepu_cell(const UStat &q, double uold, double v
     strinty = q.uarear * sy;
     const double cc1 = strintx + q.forcex + taux + q.umassdti * (brlx * uold + revp * ui);   // :731-734
     const double cc2 = strinty + q.forcey + tauy + q.umassdti * (brlx * vold + revp * vi);
-    if (ILP) div2_f64(cca * cc1 + ccb * cc2, cca * cc2 - ccb * cc1, ab2, un, vn);
-    else {
-        un = (cca * cc1 + ccb * cc2) / ab2;                                         // :736-737
-        vn = (cca * cc2 - ccb * cc1) / ab2;
-    }
+    un = (cca * cc1 + ccb * cc2) / ab2;                                             // :736-737
+    vn = (cca * cc2 - ccb * cc1) / ab2;
 }
 
 template <bool LAST, bool REVP>
@@ -1941,13 +1867,12 @@ __device__ __forceinline__ void lds_dma16(const char *gsrc, double2 *lds_slot) {
 // for the address; a vector add and a v_readfirstlane for M0 when the wave index is not known to be uniform).  Used by the tile
 // kernels.  In k_subcycle2p it took 54 of the 1 393 vector instructions out of a march step (with the zero fills of lane-private
 // state: 1 393 -> 1 314) and changed its time by NOTHING (profiles/r05_v1/diet_ab.txt: 0.2147 against 0.2150 ms per launch,
-// alternating on one box) -- that kernel is not bound by instruction issue; it keeps the builtin.  M0 is written behind the
-// compiler's back: use this only on paths where every LDS-DMA goes through it.
+// alternating on one box) -- that kernel is not bound by instruction issue; it keeps the builtin.
 // (the slot's offset is an immediate of the s_add that makes M0: one SGPR -- the wave's LDS base -- serves all slots; with a value per
 // slot the compiler hoisted eighteen of them out of the march, spilled them and read them back with v_readlane)
 template <int SLOT>
 __device__ __forceinline__ void lds_dma16s(const char *sbase, unsigned voff, unsigned lds_base) {
-    asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_base), "n"(SLOT * 1024) : "memory", "scc");
+    asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_base), "n"(SLOT * 1024) : "memory", "scc", "m0");
 }
 
 // CM (compact metrics): slots 2,3 hold (HTN,HTE) at columns c and c-1 instead of the four metric pairs in slots 2..5
@@ -1969,10 +1894,6 @@ __device__ __forceinline__ SlabV slab_view(const SubArgs &a, bool mir) {
     return v;
 }
 
-#ifndef EVPK_K2P_ILP
-#define EVPK_K2P_ILP 0      // measured (round 4, scripts/lib_ab.sh): 255 VGPRs + 2 spilled, 0 ... -1.5 % -- the partner wave already fills the bubbles
-#endif
-constexpr bool K2P_ILP = EVPK_K2P_ILP != 0;
 template <bool REVP, bool LAST2, bool CM, bool XM = false>
 __global__ __launch_bounds__(256, 2) void k_subcycle2p(SubArgs a) {      // two workgroups per CU: at most 256 VGPRs
     __shared__ double2 smem[4 * PF_SLOTS * 64];
@@ -2182,7 +2103,7 @@ __global__ __launch_bounds__(256, 2) void k_subcycle2p(SubArgs a) {      // two 
         if (__any(t1act)) {
             if (t1act) {
                 Diag dg;
-                stress_cell<false, K2P_ILP>(mt, un_c, un_m, uo_c, uo_m, vn_c, vn_m, vo_c, vo_m, a.ecci, a.arlx1i, a.denom1, 0.0, g1, o1, dg);
+                stress_cell<false>(mt, un_c, un_m, uo_c, uo_m, vn_c, vn_m, vo_c, vo_m, a.ecci, a.arlx1i, a.denom1, 0.0, g1, o1, dg);
             }
         }
         const double a2n = shfl_dn1(o1.s2), a4n = shfl_dn1(o1.s4), a7n = shfl_dn1(o1.s7), a8n = shfl_dn1(o1.s8);
@@ -2192,7 +2113,7 @@ __global__ __launch_bounds__(256, 2) void k_subcycle2p(SubArgs a) {      // two 
         if (__any(u1act)) {
             if (u1act) {
                 double sxi, syi;
-                stepu_cell<K2P_ILP>(q1, uo_c, vo_c, ui1, vi1, ((a1c + a2r) + o1.s3) + a4n, ((a5c + o1.s6) + a7r) + a8n,
+                stepu_cell(q1, uo_c, vo_c, ui1, vi1, ((a1c + a2r) + o1.s3) + a4n, ((a5c + o1.s6) + a7r) + a8n,
                            a.brlx, a.revp, a.cosw, a.sinw, u1_c, v1_c, sxi, syi);
             }
         }
@@ -2210,7 +2131,7 @@ __global__ __launch_bounds__(256, 2) void k_subcycle2p(SubArgs a) {      // two 
                 double tarear = 0.0;
                 if (LAST2) tarear = *reinterpret_cast<const double *>(rq + (size_t)(F_TAREAR >> 1) * pp + lo + (F_TAREAR & 1) * 8);
                 const TMet mt2 = CM ? tmet_from_lengths(hn_p, hn_pp, he_p, hw_p, tiny_p, str_p) : mtp;
-                stress_cell<LAST2, K2P_ILP>(mt2, u1_c, u1_m, u1p_c, u1p_m, v1_c, v1_m, v1p_c, v1p_m, a.ecci, a.arlx1i, a.denom1, tarear, g2, o2, dg);
+                stress_cell<LAST2>(mt2, u1_c, u1_m, u1p_c, u1p_m, v1_c, v1_m, v1p_c, v1p_m, a.ecci, a.arlx1i, a.denom1, tarear, g2, o2, dg);
                 if (own && q2 >= jb && q2 < jb + R && q2 <= jmax) {
                     store_sig(rq, pp, SW, lo, g2);
                     if (cyc && c == 1) store_sig(rq, pp, SW, lo + (unsigned)nxl * 16u, g2);
@@ -2230,7 +2151,7 @@ __global__ __launch_bounds__(256, 2) void k_subcycle2p(SubArgs a) {      // two 
         if (__any(u2act)) {
             if (u2act) {
                 double un, vn, sxi, syi;
-                stepu_cell<K2P_ILP>(qp, u1p_c, v1p_c, uip, vip, ((b1c + b2r) + o2.s3) + b4n, ((b5c + o2.s6) + b7r) + b8n,
+                stepu_cell(qp, u1p_c, v1p_c, uip, vip, ((b1c + b2r) + o2.s3) + b4n, ((b5c + o2.s6) + b7r) + b8n,
                            a.brlx, a.revp, a.cosw, a.sinw, un, vn, sxi, syi);
                 char *const ru = base + (size_t)q3 * rowb;
                 stp(ru, pp, SW + S_U, lo, un, vn);
@@ -2484,247 +2405,6 @@ template __global__ void k_subcycle2t<false, false, true>(SubArgs);
 template __global__ void k_subcycle2t<true, false, true>(SubArgs);
 template __global__ void k_subcycle2t8<false>(SubArgs);
 template __global__ void k_subcycle2t8<true>(SubArgs);
-
-// ------------------------------------------------------------------------------------
-// k_subcycle2r (round 5): k_subcycle2t that ROLLS north -- the one-row-per-wave tile WITHOUT its redundant rows.
-// A tile of k_subcycle2t computes T1 on R + 3 rows, U1 on R + 2, T2 on R + 1 for R owned rows (8, 7, 6 for 5: 1.4 x the stress
-// work), and the small slabs it serves are bound by fp64 issue, not by latency (450 x 2700: 17 K wave-rows x 1 450 instructions on
-// 1 024 SIMDs = the 42 us the launch takes).  Here a workgroup of NW waves takes a strip of R >= NW - 3 rows and works through it
-// in PASSES of the same four phases; a row that could not finish in a pass because the row above it had not started (the top
-// row has T1 only, the one below it lacks U2) is KEPT by its wave -- sigma after the first subcycle, the metrics, its str terms
-// stay in that wave's registers -- and finishes in the next pass beside NW - 2 new rows:
-//   pass p:  A  T1 of the new rows s .. t            (s = 0, t = NW - 1 in the first pass; then s = t' + 1, t = s + NW - 3)
-//            B  U1 of rows s - 1 .. t - 1            (needs T1 of the row above: LDS)
-//            C  T2 of rows s - 1 .. t - 1            (needs U1 of the row below: LDS; sigma stored)
-//            D  U2 of rows s - 2 .. t - 2            (needs T2 of the row above: LDS; (u, v) stored)
-//            rows <= t - 2 are complete: their waves take rows + NW
-// Row q of the strip lives on wave q mod NW for all four phases, so the LDS rows of k_subcycle2t serve unchanged (the row above /
-// below is the next / previous wave, cyclically).  Every pass runs NW - 2 rows through every phase: R + 3 T1 rows, R + 2 U1, R + 1
-// T2 per R owned rows of a STRIP instead of a five-row tile.  Four barriers per pass (the fourth keeps a fast wave's next T1 terms
-// out of the LDS row a slow wave's U2 still reads).  Same strips, lists, column / ghost-zone / band (jmax) rules and arithmetic as
-// k_subcycle2t and k_subcycle2p: bit-identical.
-// ------------------------------------------------------------------------------------
-constexpr int ROLL_NW = 8;                           // waves per workgroup (two workgroups per CU)
-constexpr size_t ROLL_LDS_PER_WAVE = 10 * 1024;      // X 2 KiB + Y 1 + Z 3 + Q 4
-template <bool REVP, bool LAST2, bool XM = false>
-__global__ __launch_bounds__(512, 4) void k_subcycle2r(SubArgs a) {
-    extern __shared__ double tl[];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int NW = blockDim.x >> 6;
-    const int nband8 = (a.nband + 7) & ~7;
-    const int nmir8 = XM ? ((a.nmir + 7) & ~7) : 0;
-    const int vb = a.band_last ? (int)((blockIdx.x + (unsigned)(nband8 + nmir8)) % gridDim.x) : (int)blockIdx.x;      // (see k_subcycle2p)
-    if (vb < nband8) {                   // tripole top band of this pair (one rank; the launch asks for the LDS)
-        if (vb < a.nband) band_pair<REVP, LAST2>(a, vb, tl);
-        return;
-    }
-    const bool mir = XM && vb - nband8 < nmir8;
-    const SlabV s = slab_view(a, mir);
-    const int jmax = mir ? a.mjmax : a.jmax;
-    int wg, st;
-    if (mir) {
-        wg = vb - nband8;
-        if (wg >= a.nmir) return;                     // (the whole workgroup leaves: no barrier is left waiting)
-        st = wg;
-    } else {
-        const int bidx = vb - nband8 - nmir8;
-        const int ns = pair_nstrips(a);
-        const int chunk = a.nsdev ? (ns + 7) >> 3 : ((int)gridDim.x - nband8 - nmir8) >> 3;
-        wg = (bidx & 7) * chunk + (bidx >> 3);
-        if ((bidx >> 3) >= chunk || wg >= ns) return; // (likewise)
-        st = __builtin_amdgcn_readfirstlane(a.strips[wg]);
-        if (w == 0) dbg_stamp(a, wg, 0);
-    }
-    const int cx = st % a.ncx, ry = st / a.ncx;
-    const int R = a.R, nxl = s.nxl, nyl = s.nyl;
-    const int G = a.G;
-    const int c = cx * STRIP2_W + lane - G;
-    const int jb = ry * R + 1;
-    const bool cyc = a.wrap != 0;
-    int ci = c, cm1 = c - 1;
-    bool okc, okm;
-    if (cyc) {
-        ci = (c - 1) % nxl; if (ci < 0) ci += nxl; ci += 1;
-        cm1 = (c - 2) % nxl; if (cm1 < 0) cm1 += nxl; cm1 += 1;
-        okc = okm = true;
-    } else {
-        okc = (c >= -1 - G && c <= nxl + 2 + G);
-        okm = (cm1 >= -1 - G && cm1 <= nxl + 2 + G);
-        if (!okc) ci = 0;
-        if (!okm) cm1 = 0;
-    }
-    const bool tcol = cyc ? true : (c >= -G && c <= nxl + 2 + G);
-    const bool ucol = cyc ? true : (c >= -G && c <= nxl + 1 + G);
-    const bool own = (lane >= 1 && lane <= STRIP2_W && c >= 1 - G && c <= nxl + G);
-
-    const size_t pp0 = (size_t)s.pitch * 16;
-    const size_t rowb = (size_t)s.rstride * 16;
-    const unsigned lo = (unsigned)(C0 + ci) * 16u, lom = (unsigned)(C0 + cm1) * 16u;
-    const int SR = a.sr, SW = a.sw;
-    char *const base = reinterpret_cast<char *>(s.F);
-    // LDS per wave: X 4 x 64 doubles (the str terms the row below needs), Y 2 x 64 ((u, v) after the first subcycle; the column to the
-    // west is the lane below), Z 6 x 64 (what the row's own later phases need of its stresses: nothing of a row is carried in
-    // registers from one stress to the next except sigma and the metrics), Q 4 x 64 double2 (the stepu inputs): 10 KiB, two
-    // workgroups of eight waves per CU
-    double *const X = tl, *const Y = tl + (size_t)NW * 256, *const Z = tl + (size_t)NW * 384;
-    const int wup = (w + 1 == NW) ? 0 : w + 1, wdn = (w == 0) ? NW - 1 : w - 1;      // the waves of the rows above / below mine
-    double *const Xw = X + (size_t)w * 256 + lane, *const Yw = Y + (size_t)w * 128 + lane, *const Zw = Z + (size_t)w * 384 + lane;
-    const double *const Xn = X + (size_t)wup * 256 + lane, *const Ys = Y + (size_t)wdn * 128 + lane;
-    double2 *const Qw = reinterpret_cast<double2 *>(tl + (size_t)NW * 768) + (size_t)w * 4 * 64;
-    const unsigned Qb = (unsigned)(size_t)(__attribute__((address_space(3))) void *)Qw;      // (LDS byte address, uniform: w is)
-    auto load_q = [&](UStat &q, double &ui, double &vi, const char *rbq) {
-        const double2 va = Qw[0 * 64 + lane], oc = Qw[1 * 64 + lane], fo = Qw[2 * 64 + lane], mf = Qw[3 * 64 + lane];
-        q = UStat{va.x, va.y, oc.x, oc.y, fo.x, fo.y, mf.x, mf.y};
-        ui = 0.0; vi = 0.0;
-        if (REVP) { const double2 iv = ldp(rbq, pp0, F_UVEL_INIT, lo); ui = iv.x; vi = iv.y; }      // (revised EVP only: read where it is used)
-    };
-
-    const int qmax = R + 2;                           // rows q = 0 .. R + 2 of the strip: r = jb - 1 + q
-    int q = w;                                        // the row this wave holds
-    int sp = 0, tp = (NW - 1 < qmax) ? NW - 1 : qmax; // T1 runs on rows sp .. tp in this pass
-    // the state of the held row (lives across passes while the row waits for the rows above it)
-    Sig g1{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // sigma after the first subcycle: the one thing a row keeps in registers between its stresses
-
-    for (;;) {
-        // (the plane offsets inside a row -- some twenty products with the pitch -- are made again in every pass: as loop invariants the
-        //  compiler kept them all in scalar registers, spilled 34 of those and fetched them back lane by lane)
-        size_t pp = pp0;
-        asm volatile("" : "+s"(pp));
-        const unsigned pp32 = (unsigned)pp;
-        // ---------------- phase A: T1 of the new rows ----------------
-        // (the mask byte, the old velocity and the metrics of the held row are re-read where a later phase needs them -- they come out
-        //  of the L2 -- instead of living in registers across the passes: the register budget is the tile kernel's)
-        const int r = jb - 1 + q;
-        const bool rowok = (r >= 0 && r <= nyl + 1);
-        char *const rb = base + (size_t)(rowok ? r : 0) * rowb;
-        const unsigned char m = (rowok && okc && q <= qmax) ? s.cmask[(size_t)r * s.pitch + C0 + ci] : (unsigned char)0;
-        const bool t1act = tcol && (m & CM_T) != 0;
-        if (q >= sp && q <= tp) {
-            double un_c = 0.0, vn_c = 0.0;
-            double un_m = 0.0, vn_m = 0.0, uo_c = 0.0, vo_c = 0.0, uo_m = 0.0, vo_m = 0.0;
-            if (rowok) {
-                if (okc) { const double2 v = ldp(rb, pp, SR + S_U, lo); un_c = v.x; vn_c = v.y; }
-                if (okm) { const double2 v = ldp(rb, pp, SR + S_U, lom); un_m = v.x; vn_m = v.y; }
-            }
-            if (r - 1 >= 0 && r - 1 <= nyl + 1) {
-                const char *rs = base + (size_t)(r - 1) * rowb;
-                if (okc) { const double2 v = ldp(rs, pp, SR + S_U, lo); uo_c = v.x; vo_c = v.y; }
-                if (okm) { const double2 v = ldp(rs, pp, SR + S_U, lom); uo_m = v.x; vo_m = v.y; }
-            }
-            const bool u1need = (q <= qmax - 1) && ucol && (m & CM_U) != 0 && r >= 1 && r <= nyl;
-            Str8 o1{0, 0, 0, 0, 0, 0, 0, 0};
-            g1 = Sig{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            TMet mt{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            if (__any(t1act)) {
-                if (t1act) { mt = load_tmet(rb, pp, lo); g1 = load_sig(rb, pp, SR, lo); }
-            }
-            if (__any(u1need)) {      // the stepu inputs of this row serve both subcycles: global -> LDS directly
-                if (u1need) {
-                    lds_dma16s<0>(rb + (size_t)((unsigned)(F_VRELC >> 1) * pp32), lo, Qb);
-                    lds_dma16s<1>(rb + (size_t)((unsigned)(F_UOCN >> 1) * pp32), lo, Qb);
-                    lds_dma16s<2>(rb + (size_t)((unsigned)(F_FORCEX >> 1) * pp32), lo, Qb);
-                    lds_dma16s<3>(rb + (size_t)((unsigned)(F_UMASSDTI >> 1) * pp32), lo, Qb);
-                }
-            }
-            if (__any(t1act)) {
-                if (t1act) {
-                    Diag dg;
-                    stress_cell<false>(mt, un_c, un_m, uo_c, uo_m, vn_c, vn_m, vo_c, vo_m, a.ecci, a.arlx1i, a.denom1, 0.0, g1, o1, dg);
-                }
-            }
-            const double a2n = shfl_dn1(o1.s2), a7n = shfl_dn1(o1.s7), a4n = shfl_dn1(o1.s4), a8n = shfl_dn1(o1.s8);
-            Xw[0] = o1.s3; Xw[64] = o1.s6; Xw[128] = a4n; Xw[192] = a8n;
-            Zw[0] = o1.s1 + a2n; Zw[64] = o1.s5; Zw[128] = a7n;      // (for this row's U1, this pass or the next)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (this wave's LDS-DMA has landed)
-        }
-        __syncthreads();
-
-        // ---------------- phase B: U1 of rows sp - 1 .. tp - 1 ----------------
-        const bool doB = (q >= sp - 1 && q <= tp - 1 && q >= 0);
-        if (doB) {
-            const bool u1act = ucol && (m & CM_U) != 0 && r >= 1 && r <= nyl;
-            double un_c = 0.0, vn_c = 0.0;
-            if (rowok && okc) { const double2 v = ldp(rb, pp, SR + S_U, lo); un_c = v.x; vn_c = v.y; }
-            double u1_c = un_c, v1_c = vn_c;          // an inactive cell keeps its velocity
-            if (__any(u1act)) {
-                if (u1act) {
-                    double sxi, syi;
-                    UStat q1; double ui1, vi1;
-                    load_q(q1, ui1, vi1, rb);
-                    stepu_cell(q1, un_c, vn_c, ui1, vi1, (Zw[0] + Xn[0]) + Xn[128], ((Zw[64] + Xn[64]) + Zw[128]) + Xn[192],
-                               a.brlx, a.revp, a.cosw, a.sinw, u1_c, v1_c, sxi, syi);
-                }
-            }
-            Yw[0] = u1_c; Yw[64] = v1_c;              // (phases C and D of this row read them back from here; (c-1, r) is the lane below)
-        }
-        __syncthreads();
-
-        // ---------------- phase C: T2 of rows sp - 1 .. tp - 1 (from row 1 of the strip) ----------------
-        const bool doC = doB && q >= 1;
-        if (doC) {
-            const bool t2act = t1act && lane >= 1;
-            Str8 o2{0, 0, 0, 0, 0, 0, 0, 0};
-            if (__any(t2act)) {
-                if (t2act) {
-                    const TMet mt = load_tmet(rb, pp, lo);
-                    Sig g2 = g1;
-                    Diag dg;
-                    double tarear = 0.0;
-                    if (LAST2) tarear = *reinterpret_cast<const double *>(rb + (size_t)(F_TAREAR >> 1) * pp + lo + (F_TAREAR & 1) * 8);
-                    stress_cell<LAST2>(mt, Yw[0], Yw[-1], Ys[0], Ys[-1], Yw[64], Yw[63], Ys[64], Ys[63], a.ecci, a.arlx1i, a.denom1, tarear, g2, o2, dg);
-                    if (own && q <= R && r <= jmax) {
-                        store_sig(rb, pp, SW, lo, g2);
-                        if (cyc && c == 1) store_sig(rb, pp, SW, lo + (unsigned)nxl * 16u, g2);     // east ghost T column = image of column 1
-                        if (LAST2) {
-                            st1(rb, pp, F_DIVU, lo, dg.divu);       st1(rb, pp, F_RDGCONV, lo, dg.rdg_conv);
-                            st1(rb, pp, F_RDGSHEAR, lo, dg.rdg_shear); st1(rb, pp, F_SHEAR, lo, dg.shear);
-                            st1(rb, pp, F_PRSSIG, lo, dg.prs);
-                        }
-                    }
-                }
-            }
-            const double b2n = shfl_dn1(o2.s2), b7n = shfl_dn1(o2.s7), b4n = shfl_dn1(o2.s4), b8n = shfl_dn1(o2.s8);
-            Xw[0] = o2.s3; Xw[64] = o2.s6; Xw[128] = b4n; Xw[192] = b8n;
-            Zw[192] = o2.s1 + b2n; Zw[256] = o2.s5; Zw[320] = b7n;      // (for this row's U2)
-        }
-        __syncthreads();
-
-        // ---------------- phase D: U2 of rows sp - 2 .. tp - 2 (rows 1 .. R of the strip) ----------------
-        const bool doD = (q >= sp - 2 && q <= tp - 2 && q >= 1 && q <= R);
-        if (doD) {
-            const bool u2act = own && (m & CM_U) != 0 && r <= nyl && r <= jmax;
-            if (__any(u2act)) {
-                if (u2act) {
-                    double un, vn, sxi, syi;
-                    UStat q1; double ui1, vi1;
-                    load_q(q1, ui1, vi1, rb);
-                    stepu_cell(q1, Yw[0], Yw[64], ui1, vi1, (Zw[192] + Xn[0]) + Xn[128], ((Zw[256] + Xn[64]) + Zw[320]) + Xn[192],
-                               a.brlx, a.revp, a.cosw, a.sinw, un, vn, sxi, syi);
-                    stp(rb, pp, SW + S_U, lo, un, vn);
-                    if (cyc) {
-                        if (c == 1) stp(rb, pp, SW + S_U, lo + (unsigned)nxl * 16u, un, vn);
-                        if (c == nxl) stp(rb, pp, SW + S_U, lo - (unsigned)nxl * 16u, un, vn);
-                    }
-                    if (LAST2) { st1(rb, pp, F_STRINTX, lo, sxi); st1(rb, pp, F_STRINTY, lo, syi); }
-                }
-            }
-        }
-        if (tp >= qmax) break;                        // the strip's last row has had its T1: everything finished in this pass
-        if (q <= tp - 2) q += NW;                     // my row is complete: the next one of this wave
-        sp = tp + 1;
-        tp = (sp + NW - 3 < qmax) ? sp + NW - 3 : qmax;
-        __syncthreads();                              // (a slow wave's phase D still reads the LDS row a new T1 is about to rewrite)
-    }
-    if (w == 0 && !mir) dbg_stamp(a, wg, 1);
-}
-
-template __global__ void k_subcycle2r<false, false>(SubArgs);
-template __global__ void k_subcycle2r<true, false>(SubArgs);
-template __global__ void k_subcycle2r<false, true>(SubArgs);
-template __global__ void k_subcycle2r<true, true>(SubArgs);
-template __global__ void k_subcycle2r<false, false, true>(SubArgs);
-template __global__ void k_subcycle2r<true, false, true>(SubArgs);
 
 // strip activity for the pair kernels: any active T / U cell in the window the strip touches
 // (columns c0..c0+63 wrapped, rows jb-1..jb+R+1: STRIP2_W owned columns from lane 1 on, one row read beyond the owned ones)

@@ -13,8 +13,10 @@ from tests import util
 
 pytestmark = pytest.mark.gpu
 
-# ({"EVPK_TILE": "2"}: the rolling tile kernel of round 5; the slot once held {"EVPK_PREFETCH": "0"}, whose kernel was retired and is refused)
-MODES = [{}, {"EVPK_FORCE_EXCHANGE": "1"}, {"EVPK_DOUBLE": "0"}, {"EVPK_TILE": "2"}, {"EVPK_FORCE_EXCHANGE": "1", "EVPK_ZONE_M": "2"},
+# ({"EVPK_TILE": "1", "EVPK_STRIP_ROWS": "13"}: the sixteen-wave tile; the slot once held {"EVPK_PREFETCH": "0"}, then {"EVPK_TILE": "2"},
+#  whose kernels were retired and are refused -- it stays a slot: the list's length and order decide every seed's draw)
+MODES = [{}, {"EVPK_FORCE_EXCHANGE": "1"}, {"EVPK_DOUBLE": "0"}, {"EVPK_TILE": "1", "EVPK_STRIP_ROWS": "13"},
+         {"EVPK_FORCE_EXCHANGE": "1", "EVPK_ZONE_M": "2"},
          {"EVPK_COMPACT_METRICS": "0"}, {"EVPK_STRIP_ROWS": "3"}, {"EVPK_FORCE_EXCHANGE": "1", "EVPK_OVERLAP": "0"},
          {"EVPK_FORCE_EXCHANGE": "2"}, {"EVPK_FORCE_EXCHANGE": "2", "EVPK_ZONE_M": "1"},
          {"EVPK_TILE": "1"}, {"EVPK_TILE": "1", "EVPK_FORCE_EXCHANGE": "1"}, {"EVPK_TILE": "1", "EVPK_STRIP_ROWS": "2"}, {"EVPK_TILE": "0"}]
