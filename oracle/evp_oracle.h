@@ -9,10 +9,15 @@
  * block / distribution arithmetic -- those reference routines compile here unmodified (oracle/ref/Makefile) and their
  * outputs are the fixtures tests/golden/ref_*.npz (tests/test_ref_pins.py).  Pinned the same way, by a slice of ice_dyn_shared /
  * ice_dyn_evp cut out at build time (oracle/ref/Makefile `kernels`, tests/golden/ref_dyn_*.npz): orc_evp_prep1, orc_evp_prep2,
- * orc_stress, orc_stepu, orc_evp_finish, orc_principal_stress, each alone and as the chain orc_evp runs.  PARITY UNPINNED for
- * the call order inside evp() (written from it; the routine itself reaches ice_grid), to_ugrid / to_tgrid, horizontal_remap and
- * eap: ice_grid needs the netCDF Fortran module (source/ice_grid.F90:144), absent from the image; the remap and EAP routines
- * could be sliced like the dynamics and are not yet; the reference ships no tests or golden vectors.  For those this restatement is checked by decomposition invariance and analytic properties
+ * orc_stress, orc_stepu, orc_evp_finish, orc_principal_stress, each alone and as the chain orc_evp runs.  And by a slice of
+ * ice_transport_remap (same target, oracle/ref/ref_remap.F90, tests/golden/ref_remap_*.npz): make_masks, construct_fields,
+ * limited_gradient, departure_points, locate_triangles, triangle_coordinates, transport_integrals, update_fields, each alone
+ * (orc_remap_*) and as the chain orc_horizontal_remap runs, on velocities that enter every triangle branch l_fixed_area =
+ * .false. can reach (tests/test_ref_pins.py: assert_remap_coverage).  PARITY UNPINNED for the call order inside evp() and
+ * horizontal_remap() (written from them; the routines themselves reach ice_grid), l_fixed_area = .true., state_to_tracers /
+ * tracers_to_state, to_ugrid / to_tgrid and eap: ice_grid needs the netCDF Fortran module (source/ice_grid.F90:144), absent
+ * from the image; the EAP routines could be sliced like the others and are not yet (their trigonometry needs a tolerance
+ * argument of its own); the reference ships no tests or golden vectors.  For those this restatement is checked by decomposition invariance and analytic properties
  * (tests/test_oracle.py), and tests/golden/evp_*.npz hold ITS OWN outputs (regression pins, not reference vectors).
  *
  * Array convention: every field is a Fortran-ordered block array
@@ -207,6 +212,31 @@ int orc_horizontal_remap(const orc_geom *g, double dt, int ncat, int ntrace, con
                          int l_fixed_area, const int32_t *tracer_type, const int32_t *depend, const int32_t *has_dependents,
                          int integral_order, int l_dp_midpt, const double *HTE, const double *HTN, const double *dxu, const double *dyu,
                          const double *tarear, const double *hm);
+
+/* The eight routines of ice_transport_remap ALONE on one block (remap_oracle.c), as the single-routine records of
+ * tests/golden/ref_remap_blk.*.npz call the reference's: planes (ny, nx); tm, tmask, tc, tx, ty, mtflx: ntrace planes of one
+ * category (NULL: open water / the mass alone); xp, yp: [6][4] planes, iflux, jflux, triarea: [6] planes. */
+void orc_remap_make_masks(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int open_water, int ntrace, const int32_t *has_dependents,
+                          const double *mm, double *mmask, const double *tm, double *tmask, int32_t *icells);
+void orc_remap_limited_gradient(int nx, int ny, int ilo, int ihi, int jlo, int jhi, const double *phi, const double *phimask,
+                                const double *cnx, const double *cny, double *gx, double *gy);
+void orc_remap_construct_fields(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int ntrace, const int32_t *tracer_type,
+                                const int32_t *depend, const int32_t *has_dependents, const double *hm, const double *mm, double *mc,
+                                double *mx, double *my, const double *mmask, const double *tm, double *tc, double *tx, double *ty,
+                                const double *tmask);
+int orc_remap_departure_points(int nx, int ny, int ilo, int ihi, int jlo, int jhi, double dt, const double *uvel, const double *vvel,
+                               const double *dxu, const double *dyu, const double *HTN, const double *HTE, double *dpx, double *dpy,
+                               int l_dp_midpt, int32_t *ijstop);
+void orc_remap_locate_triangles(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int north, const double *dpx, const double *dpy,
+                                const double *dxu, const double *dyu, double *xp, double *yp, int32_t *iflux, int32_t *jflux, double *triarea);
+void orc_remap_triangle_coordinates(int nx, int ny, int integral_order, const double *triarea, double *xp, double *yp);
+void orc_remap_transport_integrals(int nx, int ny, int ntrace, const int32_t *tracer_type, const int32_t *depend, int integral_order,
+                                   const double *triarea, const int32_t *iflux, const int32_t *jflux, const double *xp, const double *yp,
+                                   const double *mc, const double *mx, const double *my, double *mflx, const double *tc, const double *tx,
+                                   const double *ty, double *mtflx);
+int orc_remap_update_fields(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int ntrace, const int32_t *tracer_type, const int32_t *depend,
+                            const double *tarear, const double *mflxe, const double *mflxn, double *mm, const double *mtflxe,
+                            const double *mtflxn, double *tm, int32_t *ijstop);
 
 void orc_evp(const orc_geom *g, const orc_params *p, orc_fields *f, int nsub_override,
              int64_t counts[2], double *loop_seconds /* [0] wall time of the subcycle loop, [1] the halo updates' share of it; may be NULL */);

@@ -3,7 +3,8 @@
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py -- never by the cice5_amd product path.
 Parity: halo updates, ice_strength, evp_prep1/2, stress, stepu, evp_finish pinned by reference output (tests/golden/ref_*.npz);
-to_ugrid / to_tgrid, remap and eap UNPINNED (oracle/evp_oracle.h).
+the eight routines of ice_transport_remap and their chain in horizontal_remap's order likewise (tests/golden/ref_remap_*.npz);
+to_ugrid / to_tgrid, the call order of evp() / horizontal_remap() and eap UNPINNED (oracle/evp_oracle.h).
 """
 from __future__ import annotations
 
@@ -152,6 +153,14 @@ def lib():
         _lib.orc_horizontal_remap.argtypes = ([ct.POINTER(OrcGeom), ct.c_double, ct.c_int, ct.c_int] + [c_f64p] * 4 + [ct.c_int] +
                                               [c_i32p] * 3 + [ct.c_int, ct.c_int] + [c_f64p] * 6)
         _lib.orc_horizontal_remap.restype = ct.c_int
+        I, F, P = ct.c_int, c_f64p, c_i32p          # the eight remap routines alone on one block (remap_oracle.c)
+        for name, args in (("make_masks", [I] * 8 + [P, F, F, F, F, P]), ("limited_gradient", [I] * 6 + [F] * 6),
+                           ("construct_fields", [I] * 7 + [P] * 3 + [F] * 11), ("departure_points", [I] * 6 + [ct.c_double] + [F] * 8 + [I, P]),
+                           ("locate_triangles", [I] * 7 + [F] * 6 + [P, P, F]), ("triangle_coordinates", [I] * 3 + [F] * 3),
+                           ("transport_integrals", [I] * 3 + [P, P, I, F, P, P] + [F] * 10),
+                           ("update_fields", [I] * 7 + [P, P] + [F] * 7 + [P])):
+            fn = getattr(_lib, "orc_remap_" + name)
+            fn.argtypes, fn.restype = args, ct.c_int
         _lib.orc_transport_remap_state.argtypes = ([ct.POINTER(OrcGeom), ct.c_double] + [ct.c_int] * 5 + [ct.c_double] + [c_f64p] * 7 +
                                                    [c_i32p] * 3 + [ct.c_int] * 2 + [c_f64p] * 6)
         _lib.orc_halo_stress.argtypes = [ct.POINTER(OrcGeom), c_f64p, c_f64p]

@@ -2,9 +2,15 @@
  * oracle/remap_oracle.c -- CPU restatement of the incremental-remapping transport of CICE5
  * (source/ice_transport_remap.F90: horizontal_remap and its subroutines), plain C99.
  *
- * TEST INFRASTRUCTURE ONLY, PARITY UNPINNED (see evp_oracle.h): the reference ships no vectors for this path and cannot
- * be built here; what pins this file are the properties the scheme is built to have (conservation, monotonicity,
- * exactness for uniform fields, tests/test_oracle.py) and decomposition invariance.
+ * TEST INFRASTRUCTURE ONLY.  PARITY PINNED by the reference's own output (see evp_oracle.h) for make_masks, construct_fields,
+ * limited_gradient, departure_points, locate_triangles, triangle_coordinates, transport_integrals and update_fields -- a slice
+ * of ice_transport_remap cut out at build time (oracle/ref/Makefile `kernels`, oracle/ref/ref_remap.F90) -- each alone on one
+ * block (the orc_remap_* entries at the end of this file) and chained on whole grids in horizontal_remap's order with the
+ * reference's own halo updates (orc_horizontal_remap), bit for bit: tests/golden/ref_remap_*.npz, tests/test_ref_pins.py.
+ * UNPINNED: the call order of horizontal_remap itself (it reaches ice_grid and cannot be built; the chain is written from
+ * it), l_fixed_area = .true. (not implemented here), state_to_tracers / tracers_to_state (orc_transport_remap_state); for
+ * those, the properties the scheme is built to have (conservation, monotonicity, exactness for uniform fields,
+ * tests/test_oracle.py) and decomposition invariance remain the check.
  *
  * Every routine follows the operation order of the Fortran it cites (-ffp-contract=off); Fortran evaluates a + b + c as
  * (a + b) + c and a*b*c as (a*b)*c, and so does the C below.  Arrays are (nx, ny) blocks, i fastest, 1-based through IX().
@@ -146,7 +152,7 @@ static void construct_fields(int nx, int ny, int ilo, int ihi, int jlo, int jhi,
  * ------------------------------------------------------------------------- */
 static int departure_points(int nx, int ny, int ilo, int ihi, int jlo, int jhi, double dt, const double *uvel, const double *vvel,
                             const double *dxu, const double *dyu, const double *HTN, const double *HTE, double *dpx, double *dpy,
-                            int l_dp_midpt) {
+                            int l_dp_midpt, int32_t *ijstop /* istop, jstop of the last offending corner, or NULL */) {
     const size_t nn = (size_t)nx * ny;
     int l_stop = 0;
     for (size_t k = 0; k < nn; k++) { dpx[k] = c0; dpy[k] = c0; }
@@ -155,7 +161,10 @@ static int departure_points(int nx, int ny, int ilo, int ihi, int jlo, int jhi, 
             const size_t k = IX(i, j);
             dpx[k] = -dt * uvel[k];
             dpy[k] = -dt * vvel[k];
-            if (dpx[k] < -HTN[k] || dpx[k] > HTN[IX(i + 1, j)] || dpy[k] < -HTE[k] || dpy[k] > HTE[IX(i, j + 1)]) l_stop = 1;   /* :1583-1589 */
+            if (dpx[k] < -HTN[k] || dpx[k] > HTN[IX(i + 1, j)] || dpy[k] < -HTE[k] || dpy[k] > HTE[IX(i, j + 1)]) {   /* :1564-1569 */
+                l_stop = 1;
+                if (ijstop) { ijstop[0] = i; ijstop[1] = j; }
+            }
         }
     if (l_stop) return 1;
     if (l_dp_midpt)                                                                   /* :1611-1667 */
@@ -186,8 +195,25 @@ static int departure_points(int nx, int ny, int ilo, int ihi, int jlo, int jhi, 
 /* ---------------------------------------------------------------------------
  * locate_triangles (:1680-3047) + triangle_coordinates (:3078-3187) for ONE edge; l_fixed_area = .false. only.
  * north != 0: the north edge of cell (i,j), else its east edge.  Outputs per group ng = 0..5: xp/yp[ng][0..3], the source
- * cell (iflux, jflux) and triarea (0 if below the eps16 threshold, :2890-2893).
+ * cell (iflux, jflux) and triarea (0 if below the eps16 threshold, :2940-2942).  integral_order = 0: locate_triangles alone (the
+ * vertices in the source cell's coordinates, xp / yp[0] left zero).
  * ------------------------------------------------------------------------- */
+/* triangle_coordinates (:3078-3187) for one triangle: the quadrature points from the three vertices xp / yp[1..3] */
+static void triangle_points(int integral_order, double *xp, double *yp) {
+    xp[0] = P333 * (xp[1] + xp[2] + xp[3]);
+    yp[0] = P333 * (yp[1] + yp[2] + yp[3]);
+    if (integral_order == 2)
+        for (int nv = 1; nv <= NVERT; nv++) {
+            xp[nv] = p5 * xp[nv] + p5 * xp[0];
+            yp[nv] = p5 * yp[nv] + p5 * yp[0];
+        }
+    else if (integral_order != 1)
+        for (int nv = 1; nv <= NVERT; nv++) {
+            xp[nv] = p4 * xp[nv] + p6 * xp[0];
+            yp[nv] = p4 * yp[nv] + p6 * yp[0];
+        }
+}
+
 typedef struct { double xp[NGROUPS][NVERT + 1], yp[NGROUPS][NVERT + 1], triarea[NGROUPS]; int iflux[NGROUPS], jflux[NGROUPS]; } edge_tri;
 
 static void edge_triangles(int nx, int i, int j, int north, const double *dpx, const double *dpy, const double *dxu, const double *dyu,
@@ -322,20 +348,14 @@ static void edge_triangles(int nx, int i, int j, int north, const double *dpx, c
                 t->yp[ng][nv] = -w1 - c1 * jshift;
             }
         }
-        /* triangle_coordinates (:3078-3187): quadrature points */
-        t->xp[ng][0] = P333 * (t->xp[ng][1] + t->xp[ng][2] + t->xp[ng][3]);
-        t->yp[ng][0] = P333 * (t->yp[ng][1] + t->yp[ng][2] + t->yp[ng][3]);
-        if (integral_order == 2)
-            for (int nv = 1; nv <= NVERT; nv++) {
-                t->xp[ng][nv] = p5 * t->xp[ng][nv] + p5 * t->xp[ng][0];
-                t->yp[ng][nv] = p5 * t->yp[ng][nv] + p5 * t->yp[ng][0];
-            }
-        else if (integral_order != 1)
-            for (int nv = 1; nv <= NVERT; nv++) {
-                t->xp[ng][nv] = p4 * t->xp[ng][nv] + p6 * t->xp[ng][0];
-                t->yp[ng][nv] = p4 * t->yp[ng][nv] + p6 * t->yp[ng][0];
-            }
+        if (integral_order) triangle_points(integral_order, t->xp[ng], t->yp[ng]);
     }
+}
+
+/* edges whose two departure points are both zero carry no flux and are left out of the lists (:1955-1979) */
+static int edge_moves(int nx, int i, int j, int north, const double *dpx, const double *dpy) {
+    const size_t ka = IX(i, j), kb = north ? IX(i - 1, j) : IX(i, j - 1);
+    return dpx[kb] != c0 || dpy[kb] != c0 || dpx[ka] != c0 || dpy[ka] != c0;
 }
 
 /* ---------------------------------------------------------------------------
@@ -410,7 +430,7 @@ static void edge_integrals(int nx, int ntrace, const int32_t *tracer_type, const
  * ------------------------------------------------------------------------- */
 static int update_fields(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int ntrace, const int32_t *tracer_type, const int32_t *depend,
                          const double *tarear, const double *mflxe, const double *mflxn, double *mm, double *const *mtflxe,
-                         double *const *mtflxn, double *const *tm) {
+                         double *const *mtflxn, double *const *tm, int32_t *ijstop /* or NULL */) {
     const size_t nn = (size_t)nx * ny;
     int l_stop = 0;
     double **mtold = NULL;
@@ -435,8 +455,10 @@ static int update_fields(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int
             const size_t k = IX(i, j);
             const double w1 = mflxe[k] - mflxe[IX(i - 1, j)] + mflxn[k] - mflxn[IX(i, j - 1)];
             mm[k] = mm[k] - w1 * tarear[k];
-            if (mm[k] < -puny) l_stop = 1;
-            else if (mm[k] < c0) mm[k] = c0;
+            if (mm[k] < -puny) {
+                l_stop = 1;
+                if (ijstop) { ijstop[0] = i; ijstop[1] = j; }
+            } else if (mm[k] < c0) mm[k] = c0;
         }
     if (!l_stop && tm)
         for (int nt = 0; nt < ntrace; nt++)
@@ -506,7 +528,7 @@ int orc_horizontal_remap(const orc_geom *g, double dt, int ncat, int ntrace, con
             construct_fields(nx, ny, ilo, ihi, jlo, jhi, ntrace, tracer_type, depend, has_dependents, hm + o, MM(b, n), PL(mc, n, b),
                              PL(mx, n, b), PL(my, n, b), mmask, tmp, tcp, txp, typ, (const double *const *)tmk);
         }
-        if (departure_points(nx, ny, ilo, ihi, jlo, jhi, dt, uvel + o, vvel + o, dxu + o, dyu + o, HTN + o, HTE + o, dpx + o, dpy + o, l_dp_midpt))
+        if (departure_points(nx, ny, ilo, ihi, jlo, jhi, dt, uvel + o, vvel + o, dxu + o, dyu + o, HTN + o, HTE + o, dpx + o, dpy + o, l_dp_midpt, NULL))
             rc = 1;
         for (int nt = 0; nt < ntrace; nt++) free(tmk[nt]);
         free(tmk); free(tmp); free(tcp); free(txp); free(typ); free(mmask);
@@ -540,8 +562,8 @@ int orc_horizontal_remap(const orc_geom *g, double dt, int ncat, int ntrace, con
             for (int j = jb; j <= je; j++)
                 for (int i = ib; i <= ie; i++) {
                     /* edges whose departure points are all zero carry no flux (:1911-1929) */
-                    const size_t ka = IX(i, j), kb = north ? IX(i - 1, j) : IX(i, j - 1);
-                    if (!(dpx[o + kb] != c0 || dpy[o + kb] != c0 || dpx[o + ka] != c0 || dpy[o + ka] != c0)) continue;
+                    const size_t ka = IX(i, j);
+                    if (!edge_moves(nx, i, j, north, dpx + o, dpy + o)) continue;
                     edge_triangles(nx, i, j, north, dpx + o, dpy + o, dxu + o, dyu + o, integral_order, &t);
                     edge_integrals(nx, ntrace, tracer_type, depend, integral_order, &t, PL(mc, 0, b), PL(mx, 0, b), PL(my, 0, b), &mf[ka], NULL, NULL,
                                    NULL, NULL);
@@ -556,7 +578,7 @@ int orc_horizontal_remap(const orc_geom *g, double dt, int ncat, int ntrace, con
                     }
                 }
         }
-        if (update_fields(nx, ny, ilo, ihi, jlo, jhi, ntrace, tracer_type, depend, tarear + o, mflxe, mflxn, MM(b, 0), NULL, NULL, NULL)) rc = 2;
+        if (update_fields(nx, ny, ilo, ihi, jlo, jhi, ntrace, tracer_type, depend, tarear + o, mflxe, mflxn, MM(b, 0), NULL, NULL, NULL, NULL)) rc = 2;
         double **fe = calloc((size_t)(ntrace ? ntrace : 1), sizeof(double *)), **fn = calloc((size_t)(ntrace ? ntrace : 1), sizeof(double *)),
                **tmn = calloc((size_t)(ntrace ? ntrace : 1), sizeof(double *));
         for (int n = 1; n <= ncat && !rc; n++) {
@@ -565,7 +587,7 @@ int orc_horizontal_remap(const orc_geom *g, double dt, int ncat, int ntrace, con
                 tmn[nt] = TM(b, n, nt);
             }
             if (update_fields(nx, ny, ilo, ihi, jlo, jhi, ntrace, tracer_type, depend, tarear + o, mflxe + (size_t)n * nn, mflxn + (size_t)n * nn,
-                              MM(b, n), fe, fn, ntrace ? tmn : NULL))
+                              MM(b, n), fe, fn, ntrace ? tmn : NULL, NULL))
                 rc = 2;
         }
         free(fe); free(fn); free(tmn); free(tcp); free(txp); free(typ);
@@ -651,4 +673,127 @@ int orc_transport_remap_state(const orc_geom *g, double dt, int ncat, int ntrcr,
     }
     free(aim); free(trm);
     return rc;
+}
+
+/* ---------------------------------------------------------------------------
+ * The eight routines ALONE on one block, for the single-routine records of tests/golden/ref_remap_blk.*.npz (tests/test_ref_pins.py).
+ * Thin wrappers: the arithmetic is the static routines above.  Arrays as the fixtures hold them: planes (ny, nx); mm, mmask,
+ * mc .. (ncat + 1 planes); tm, tmask, tc .. (ntrace planes of ONE category); triangle arrays xp, yp [NGROUPS][NVERT + 1] planes,
+ * iflux, jflux, triarea [NGROUPS] planes.
+ * ------------------------------------------------------------------------- */
+static void plane_ptrs(int ntrace, size_t nn, const double *a, const double **p) { for (int nt = 0; nt < ntrace; nt++) p[nt] = a ? a + (size_t)nt * nn : NULL; }
+
+/* one category; open water comes without tracers (tm = NULL).  icells: the cells construct_fields loops over afterwards -- mm > puny on the physical
+ * cells (:1001-1011) -- except for open water, which the reference counts on the whole block (:930-943) */
+void orc_remap_make_masks(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int open_water, int ntrace, const int32_t *has_dependents,
+                          const double *mm, double *mmask, const double *tm, double *tmask, int32_t *icells) {
+    const size_t nn = (size_t)nx * ny;
+    const double *tmp[64]; double *tmk[64];
+    plane_ptrs(ntrace, nn, tm, tmp);
+    for (int nt = 0; nt < ntrace; nt++) tmk[nt] = tmask ? tmask + (size_t)nt * nn : NULL;
+    make_masks(nx, ny, ntrace, has_dependents, mm, mmask, tm ? tmp : NULL, tm ? tmk : NULL);
+    *icells = 0;
+    for (int j = open_water ? 1 : jlo; j <= (open_water ? ny : jhi); j++)
+        for (int i = open_water ? 1 : ilo; i <= (open_water ? nx : ihi); i++)
+            if (mm[IX(i, j)] > puny) (*icells)++;
+}
+
+void orc_remap_limited_gradient(int nx, int ny, int ilo, int ihi, int jlo, int jhi, const double *phi, const double *phimask,
+                                const double *cnx, const double *cny, double *gx, double *gy) {
+    limited_gradient(nx, ny, ilo, ihi, jlo, jhi, phi, phimask, cnx, cny, gx, gy);
+}
+
+/* one category; tm = NULL: without tracers (open water) */
+void orc_remap_construct_fields(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int ntrace, const int32_t *tracer_type,
+                                const int32_t *depend, const int32_t *has_dependents, const double *hm, const double *mm, double *mc,
+                                double *mx, double *my, const double *mmask, const double *tm, double *tc, double *tx, double *ty,
+                                const double *tmask) {
+    const size_t nn = (size_t)nx * ny;
+    const double *tmp[64], *tmk[64]; double *tcp[64], *txp[64], *typ[64];
+    plane_ptrs(ntrace, nn, tm, tmp); plane_ptrs(ntrace, nn, tmask, tmk);
+    for (int nt = 0; nt < ntrace; nt++) { tcp[nt] = tc + (size_t)nt * nn; txp[nt] = tx + (size_t)nt * nn; typ[nt] = ty + (size_t)nt * nn; }
+    if (tm) construct_fields(nx, ny, ilo, ihi, jlo, jhi, ntrace, tracer_type, depend, has_dependents, hm, mm, mc, mx, my, mmask, tmp, tcp, txp, typ, tmk);
+    else construct_fields(nx, ny, ilo, ihi, jlo, jhi, ntrace, tracer_type, depend, has_dependents, hm, mm, mc, mx, my, mmask, NULL, NULL, NULL, NULL, NULL);
+}
+
+/* returns l_stop; ijstop[2]: istop, jstop (untouched without a stop) */
+int orc_remap_departure_points(int nx, int ny, int ilo, int ihi, int jlo, int jhi, double dt, const double *uvel, const double *vvel,
+                               const double *dxu, const double *dyu, const double *HTN, const double *HTE, double *dpx, double *dpy,
+                               int l_dp_midpt, int32_t *ijstop) {
+    return departure_points(nx, ny, ilo, ihi, jlo, jhi, dt, uvel, vvel, dxu, dyu, HTN, HTE, dpx, dpy, l_dp_midpt, ijstop);
+}
+
+static void edge_range(int north, int ilo, int ihi, int jlo, int jhi, int *ib, int *ie, int *jb, int *je) {
+    *ib = north ? ilo : ilo - 1; *ie = ihi; *jb = north ? jlo - 1 : jlo; *je = jhi;                                  /* :1872-1875, :1906-1909 */
+}
+
+/* every edge of one kind; the arrays are zero (iflux / jflux: the cell itself) where the reference lists no triangle */
+void orc_remap_locate_triangles(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int north, const double *dpx, const double *dpy,
+                                const double *dxu, const double *dyu, double *xp, double *yp, int32_t *iflux, int32_t *jflux, double *triarea) {
+    const size_t nn = (size_t)nx * ny;
+    int ib, ie, jb, je;
+    edge_tri t;
+    edge_range(north, ilo, ihi, jlo, jhi, &ib, &ie, &jb, &je);
+    memset(xp, 0, nn * NGROUPS * (NVERT + 1) * 8); memset(yp, 0, nn * NGROUPS * (NVERT + 1) * 8); memset(triarea, 0, nn * NGROUPS * 8);
+    for (int ng = 0; ng < NGROUPS; ng++)
+        for (int j = 1; j <= ny; j++)
+            for (int i = 1; i <= nx; i++) { iflux[ng * nn + IX(i, j)] = i; jflux[ng * nn + IX(i, j)] = j; }
+    for (int j = jb; j <= je; j++)
+        for (int i = ib; i <= ie; i++) {
+            if (!edge_moves(nx, i, j, north, dpx, dpy)) continue;
+            edge_triangles(nx, i, j, north, dpx, dpy, dxu, dyu, 0, &t);
+            for (int ng = 0; ng < NGROUPS; ng++) {
+                iflux[ng * nn + IX(i, j)] = t.iflux[ng]; jflux[ng * nn + IX(i, j)] = t.jflux[ng]; triarea[ng * nn + IX(i, j)] = t.triarea[ng];
+                for (int nv = 0; nv <= NVERT; nv++) {
+                    xp[((size_t)ng * (NVERT + 1) + nv) * nn + IX(i, j)] = t.xp[ng][nv]; yp[((size_t)ng * (NVERT + 1) + nv) * nn + IX(i, j)] = t.yp[ng][nv];
+                }
+            }
+        }
+}
+
+/* in place on the triangles with triarea != 0 (the reference's compressed lists) */
+void orc_remap_triangle_coordinates(int nx, int ny, int integral_order, const double *triarea, double *xp, double *yp) {
+    const size_t nn = (size_t)nx * ny;
+    for (int ng = 0; ng < NGROUPS; ng++)
+        for (size_t k = 0; k < nn; k++) {
+            if (triarea[ng * nn + k] == c0) continue;
+            double x[NVERT + 1], y[NVERT + 1];
+            for (int nv = 0; nv <= NVERT; nv++) { x[nv] = xp[((size_t)ng * (NVERT + 1) + nv) * nn + k]; y[nv] = yp[((size_t)ng * (NVERT + 1) + nv) * nn + k]; }
+            triangle_points(integral_order, x, y);
+            for (int nv = 0; nv <= NVERT; nv++) { xp[((size_t)ng * (NVERT + 1) + nv) * nn + k] = x[nv]; yp[((size_t)ng * (NVERT + 1) + nv) * nn + k] = y[nv]; }
+        }
+}
+
+/* one category, every edge of one kind; tc = NULL: the mass flux alone */
+void orc_remap_transport_integrals(int nx, int ny, int ntrace, const int32_t *tracer_type, const int32_t *depend, int integral_order,
+                                   const double *triarea, const int32_t *iflux, const int32_t *jflux, const double *xp, const double *yp,
+                                   const double *mc, const double *mx, const double *my, double *mflx, const double *tc, const double *tx,
+                                   const double *ty, double *mtflx) {
+    const size_t nn = (size_t)nx * ny;
+    const double *tcp[64], *txp[64], *typ[64];
+    double flx[64];
+    edge_tri t;
+    plane_ptrs(ntrace, nn, tc, tcp); plane_ptrs(ntrace, nn, tx, txp); plane_ptrs(ntrace, nn, ty, typ);
+    for (size_t k = 0; k < nn; k++) {
+        for (int ng = 0; ng < NGROUPS; ng++) {
+            t.triarea[ng] = triarea[ng * nn + k]; t.iflux[ng] = iflux[ng * nn + k]; t.jflux[ng] = jflux[ng * nn + k];
+            for (int nv = 0; nv <= NVERT; nv++) { t.xp[ng][nv] = xp[((size_t)ng * (NVERT + 1) + nv) * nn + k]; t.yp[ng][nv] = yp[((size_t)ng * (NVERT + 1) + nv) * nn + k]; }
+        }
+        edge_integrals(nx, ntrace, tracer_type, depend, integral_order, &t, mc, mx, my, &mflx[k], tc ? tcp : NULL, tc ? txp : NULL,
+                       tc ? typ : NULL, tc ? flx : NULL);
+        if (tc) for (int nt = 0; nt < ntrace; nt++) mtflx[(size_t)nt * nn + k] = flx[nt];
+    }
+}
+
+/* one category in place; tm = NULL: the mass alone.  Returns l_stop; ijstop[2] as for the departure points */
+int orc_remap_update_fields(int nx, int ny, int ilo, int ihi, int jlo, int jhi, int ntrace, const int32_t *tracer_type, const int32_t *depend,
+                            const double *tarear, const double *mflxe, const double *mflxn, double *mm, const double *mtflxe,
+                            const double *mtflxn, double *tm, int32_t *ijstop) {
+    const size_t nn = (size_t)nx * ny;
+    double *fe[64], *fn[64], *tmp[64];
+    for (int nt = 0; nt < ntrace; nt++) {
+        fe[nt] = (double *)mtflxe + (size_t)nt * nn; fn[nt] = (double *)mtflxn + (size_t)nt * nn; tmp[nt] = tm + (size_t)nt * nn;
+    }
+    return update_fields(nx, ny, ilo, ihi, jlo, jhi, ntrace, tracer_type, depend, tarear, mflxe, mflxn, mm, tm ? fe : NULL, tm ? fn : NULL,
+                         tm ? tmp : NULL, ijstop);
 }

@@ -195,6 +195,8 @@ def main():
         print(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
     from tests.golden import make_ref_kernels          # the slice fixtures ref_dyn_*.npz (evp_prep1 .. stress)
     make_ref_kernels.main()
+    from tests.golden import make_ref_remap            # the remap slice fixtures ref_remap_*.npz (make_masks .. update_fields)
+    make_ref_remap.main()
 
 
 if __name__ == "__main__":

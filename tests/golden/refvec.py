@@ -369,3 +369,265 @@ def block_inputs(cfg, rec, var):
     q["indxt"], q["icellt"] = lst(q["icetmask"], jhi + 1, ihi + 1)
     q["indxu"], q["icellu"] = lst((aiu > 0.01) & (q["umask"] != 0), jhi, ihi)
     return {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in q.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the REMAP fixtures (oracle/ref/ref_remap.F90, tests/golden/make_ref_remap.py -> ref_remap_*.npz): the reference's own
+# make_masks / construct_fields / limited_gradient / departure_points / locate_triangles / triangle_coordinates /
+# transport_integrals / update_fields, alone on one block and chained on the whole grid in horizontal_remap's order.
+REMAP_NCAT = 3                                   # NICECAT of the ref_remap build (RNCAT in oracle/ref/Makefile)
+REMAP_DEPEND = (0, 1, 2 + 1, 2 + 2)              # with hice, hsno in front: tracer types 1, 1, 1, 2, 2, 3
+REMAP_DT = 3600.0
+# the largest local Courant number |u| dt / dxu of the rough velocities.  Found on the CPU with the reference binary
+# (make_ref_remap.py --courant): departure_points accepts every value below 1, but the divergent corners of a field whose
+# sign changes from corner to corner empty a cell faster than a uniform flow does, and update_fields stops on a negative
+# mass in some case of some config for 0.45 and above (in steps of 0.05: 9, 8, 8, 7, 3, 2, 1 of the 20 chains stop at 0.9, 0.8,
+# 0.7, 0.6, 0.55, 0.5, 0.45); 0.4 is the largest step for which no chain stops.
+REMAP_COURANT = 0.4
+# case -> (boundary / land case of DYN_CASES, trcr_depend or None for ntrace = 0, [(integral_order, l_dp_midpt), ...]);
+# the six (order, rule) pairs all occur
+REMAP_CASES = {
+    "cyclic_open": ("cyclic_open", REMAP_DEPEND, [(3, 1), (2, 0)]),
+    "cyclic_tripole": ("cyclic_tripole", REMAP_DEPEND, [(3, 1), (1, 0)]),
+    "open_closed_rim": ("open_closed_rim", REMAP_DEPEND, [(3, 0), (2, 1)]),
+    "cyclic_open_patch": ("cyclic_open_patch", REMAP_DEPEND, [(1, 1), (3, 1)]),
+    "areas_only": ("cyclic_tripole", None, [(3, 1), (2, 0)]),
+}
+# the two stop cases -> (return code, integral_order, l_dp_midpt): the fields of `cyclic_open` with one corner moving 1.25
+# cells, resp. the four corners of one cell flying apart at Courant 0.95 under the Euler rule (the midpoint rule reads the
+# velocity half way, where such a field has almost none) (remap_fields)
+REMAP_STOPS = {"bad_departure": (1, 3, 1), "negative_mass": (2, 3, 0)}
+REMAP_GRID = ["hm", "uvel", "vvel", "dxu", "dyu", "HTN", "HTE", "tarear"]        # the planes ref_remap.F90 reads, in its order
+
+
+def remap_tables(trcr_depend):
+    from oracle import orc
+    if trcr_depend is None:
+        e = np.zeros(0, dtype=np.int32)
+        return e, e.copy(), e.copy()
+    return orc.remap_tables(list(trcr_depend))
+
+
+def _remap_state(h, icy, ocean, ncat, ntrace):
+    """mm (ncat + 1, ...), tm (ncat, ntrace, ...) on arrays of any shape: categories with holes, masses at, just below and
+    just above puny, tracers with dependents at |tm| <= puny and exactly zero, values without meaning in cells without ice"""
+    shape = icy.shape
+    mm = np.zeros((ncat + 1,) + shape)
+    tm = np.zeros((ncat, ntrace) + shape)
+    for n in range(1, ncat + 1):
+        a = 0.05 + 0.25 * h(f"a{n}")
+        a[h(f"hole{n}") < 0.25] = 0.0
+        thr = h(f"thr{n}")
+        a[thr < 0.04] = 0.5e-11
+        a[(thr >= 0.04) & (thr < 0.07)] = 1.0e-11
+        a[(thr >= 0.07) & (thr < 0.10)] = 1.0e-11 * (1 + 1e-6)
+        a[~icy] = 0.0
+        mm[n] = a
+        for k in range(ntrace):
+            t = h(f"t{n}_{k}")
+            if k == 0:
+                v = 0.2 + 3.0 * t                                # hice
+            elif k == 1:
+                v = np.where(t < 0.2, 0.0, 0.3 * t)              # hsno
+            else:
+                v = 4.0 * t - 2.0
+            if k in (0, 2, 3):                                   # the tracers other tracers depend on (REMAP_DEPEND)
+                s = h(f"s{n}_{k}")
+                v = np.where(s < 0.05, 0.5e-11 * np.sign(v), v)
+                v = np.where((s >= 0.05) & (s < 0.08), 0.0, v)
+            junk = h(f"j{n}_{k}") < 0.3
+            tm[n - 1, k] = np.where((a > 0) | junk, v, 0.0)
+    mm[0] = np.where(ocean, 1.0 - mm[1:].sum(axis=0), 0.0)
+    return mm, tm
+
+
+def _remap_courant(h, shape, courant):
+    """Courant numbers per corner in (-courant, courant) with sign changes from corner to corner; 6 % of the corners at rest,
+    5 % each with exactly one component zero (ydl == 0, ydr == 0, xdl == xcl of locate_triangles under the Euler rule)"""
+    cx, cy = courant * (2.0 * h("cx") - 1.0), courant * (2.0 * h("cy") - 1.0)
+    z = h("zero")
+    cx[z < 0.11] = 0.0
+    cy[(z < 0.06) | ((z >= 0.11) & (z < 0.16))] = 0.0
+    return cx, cy
+
+
+def remap_fields(cfg, case, courant=None, stop=None):
+    """(decomp, fields, mm, tm, tables) of a chain record: the grid, masks and boundaries of dyn_fields(cfg, base case) with
+    the remap grid arrays, a rough velocity field and an ice state from the hash; ghost cells current (halo updates of the
+    pinned restatement).  stop: one of REMAP_STOPS."""
+    from cice5_amd import constants as C, synth
+    from oracle import orc
+    base, trcr_depend, _ = REMAP_CASES[case]
+    nx, ny, bx, by, _ = KERNEL_CONFIGS[cfg]
+    ew, ns, land, _ = DYN_CASES[base]
+    d, f = dyn_fields(cfg, base)
+    sc = synth.SynthCase(nx=nx, ny=ny, ew_boundary=C.BND_NAMES[ew], ns_boundary=C.BND_NAMES[ns], land="none")
+    synth.add_remap_grid(sc, d, f)
+    f["hm"] = f["tmask"].astype(np.float64)
+    kmt, _ = kmt_ulat(nx, ny, bx, by, ew, ns, land)
+    ocean = kmt > 0
+    h = lambda k: hash01((ny, nx), seed_of(cfg, case, "remap", k))
+    tables = remap_tables(trcr_depend)
+    ntrace = len(tables[0])
+
+    def scatter(G, loc, kind):
+        a = np.zeros((d.nblocks, d.ny_block, d.nx_block))
+        for n, b in enumerate(d.local_blocks):
+            ni, nj = b.ihi - b.ilo + 1, b.jhi - b.jlo + 1
+            a[n, b.jlo - 1:b.jhi, b.ilo - 1:b.ihi] = G[b.jglob_lo - 1:b.jglob_lo - 1 + nj, b.iglob_lo - 1:b.iglob_lo - 1 + ni]
+        orc.halo_r8(d, a, loc, kind, 0.0)
+        return a
+    jj, ii = np.meshgrid(np.arange(1, ny + 1), np.arange(1, nx + 1), indexing="ij")
+    icy = ocean & (h("icy") < 0.85)
+    gm, gt = _remap_state(h, icy, ocean, REMAP_NCAT, ntrace)
+    cx, cy = _remap_courant(h, (ny, nx), REMAP_COURANT if courant is None else courant)
+    pc, pr = zero_patch(nx)
+    rest = (ii >= pc) & (ii < pc + 5) & (jj >= pr) & (jj < pr + 5)
+    cx[rest] = 0.0; cy[rest] = 0.0
+    I, J = np.arange(1, nx + 1)[None, :], np.arange(1, ny + 1)[:, None]
+    gu = cx * sc.field("dxu", I, J) / REMAP_DT
+    gv = cy * sc.field("dyu", I, J) / REMAP_DT
+    # two pairs of departure points that mirror each other through the midpoint of a north resp. an east edge in exact arithmetic
+    # (dx, dy = -/+ 1/4, +/- 1/8 on the north edge, the same rotated on the east edge): xic == 0 and ydm == 0 under the Euler
+    # rule, the equalities of `xic >= c0` and `ydm >= c0` (:2564-2565).  The corners' dxu, dyu become 4 dt S and 8 dt S' with
+    # S, S' the powers of two that change them least (below), their velocities S, S', so every quotient is exact.  The corners
+    # lie inside a block of either config, away from the land of every case and from the patch at rest.
+    jm = ny - 6
+    gdx, gdy = sc.field("dxu", I, J) + 0 * J, sc.field("dyu", I, J) + 0 * I
+    pow2 = lambda x: 2.0 ** np.round(np.log2(x))
+    mirror = []
+    for pair, kx, ky in ((((jm, 11, 1.0, -1.0), (jm, 12, -1.0, 1.0)), 4, 8), (((jm, 14, -1.0, -1.0), (jm - 1, 14, 1.0, 1.0)), 8, 4)):
+        sx = pow2(max(gdx[j, i] for j, i, _, _ in pair) / (kx * REMAP_DT))
+        sy = pow2(max(gdy[j, i] for j, i, _, _ in pair) / (ky * REMAP_DT))
+        for j, i, su, sv in pair:
+            assert ocean[j - 1:j + 2, i - 1:i + 2].all() and not rest[j, i]
+            gu[j, i], gv[j, i] = su * sx, sv * sy
+            mirror.append((j, i, kx * REMAP_DT * sx, ky * REMAP_DT * sy))
+    jc, ic = ny // 2, (2 * nx) // 3                      # 0-based cell well inside the ocean of every case
+    if stop == "bad_departure":
+        gu[jc, ic] = -1.25 * sc.field("dxu", I, J)[jc, ic] / REMAP_DT
+    elif stop == "negative_mass":                        # the four corners of one cell fly apart at Courant 0.95
+        for dj, di, su, sv in ((0, 0, 1, 1), (0, -1, -1, 1), (-1, 0, 1, -1), (-1, -1, -1, -1)):
+            gu[jc + dj, ic + di] = su * 0.95 * sc.field("dxu", I, J)[jc + dj, ic + di] / REMAP_DT
+            gv[jc + dj, ic + di] = sv * 0.95 * sc.field("dyu", I, J)[jc + dj, ic + di] / REMAP_DT
+        gm[1, jc, ic] = 0.3
+        gm[0, jc, ic] = 1.0 - gm[1:, jc, ic].sum()
+    else:
+        assert stop is None
+    for j, i, new_dxu, new_dyu in mirror:
+        for n, b in enumerate(d.local_blocks):
+            lj, li = j + 1 - b.jglob_lo + b.jlo - 1, i + 1 - b.iglob_lo + b.ilo - 1          # 0-based block-local indices
+            if b.jlo - 1 <= lj < b.jhi and b.ilo - 1 <= li < b.ihi:
+                assert b.jlo - 1 < lj < b.jhi - 1 and b.ilo - 1 < li < b.ihi - 1, "a mirror corner lies in a neighbour's halo"
+                f["dxu"][n, lj, li], f["dyu"][n, lj, li] = new_dxu, new_dyu
+    f["uvel"] = scatter(gu, C.LOC_NECORNER, C.KIND_VECTOR) * f["umask"]
+    f["vvel"] = scatter(gv, C.LOC_NECORNER, C.KIND_VECTOR) * f["umask"]
+    mm = np.stack([scatter(gm[n], C.LOC_CENTER, C.KIND_SCALAR) for n in range(REMAP_NCAT + 1)], axis=1)
+    tm = np.zeros((d.nblocks, REMAP_NCAT, ntrace, d.ny_block, d.nx_block))
+    for n in range(REMAP_NCAT):
+        for k in range(ntrace):
+            tm[:, n, k] = scatter(gt[n, k], C.LOC_CENTER, C.KIND_SCALAR)
+    f = {k: np.ascontiguousarray(v) for k, v in f.items()}
+    return d, f, np.ascontiguousarray(mm), np.ascontiguousarray(tm), tables
+
+
+# single-routine records: one call of each routine on one block of g26x18_b8x5 (a 10 x 7 block keeps the triangle arrays
+# small), every cell of every input plane -- ghost cells included -- its own value from the hash
+REMAP_BLOCK_CFG = "g26x18_b8x5"
+REMAP_BLOCK_VARIANTS = {"t6_o3_mid": (REMAP_DEPEND, 3, 1), "t6_o2_euler": (REMAP_DEPEND, 2, 0), "t6_o1_mid": (REMAP_DEPEND, 1, 1),
+                        "t3_o3_euler": ((0, 1), 3, 0),           # types 1, 1, 1, 2 with hice the only tracer with dependents
+                        "t0_o3_mid": (None, 3, 1),
+                        "t6_stop": (REMAP_DEPEND, 3, 1)}         # departure_points stops
+REMAP_BLOCK_GRID = REMAP_GRID + ["phi", "cnx", "cny"]
+
+
+def remap_block_inputs(rec, var):
+    """mm (ncat + 1, ny, nx), tm (ncat, ntrace, ny, nx), the planes of REMAP_BLOCK_GRID, the tables"""
+    cfg = REMAP_BLOCK_CFG
+    nx, ny, bx, by, _ = KERNEL_CONFIGS[cfg]
+    nxb, nyb = bx + 2, by + 2
+    trcr_depend, order, midpt = REMAP_BLOCK_VARIANTS[var]
+    tables = remap_tables(trcr_depend)
+    h = lambda k: hash01((nyb, nxb), seed_of(cfg, rec, var, "rblk", k))
+    ocean = h("ocean") > 0.1
+    mm, tm = _remap_state(h, ocean & (h("icy") < 0.85), ocean, REMAP_NCAT, len(tables[0]))
+    q = {"hm": ocean.astype(np.float64)}
+    q["dxu"], q["dyu"] = 2.0e4 * (1.0 + 0.3 * h("dxu")), 3.0e4 * (1.0 + 0.3 * h("dyu"))
+    q["HTN"], q["HTE"] = 2.0e4 * (1.0 + 0.3 * h("htn")), 3.0e4 * (1.0 + 0.3 * h("hte"))
+    q["tarear"] = 1.0 / (q["HTN"] * q["HTE"])
+    cx, cy = _remap_courant(h, (nyb, nxb), 0.6)
+    q["uvel"], q["vvel"] = cx * q["dxu"] / REMAP_DT, cy * q["dyu"] / REMAP_DT
+    if var == "t6_o2_euler" and rec == "full":
+        # (a) departure points BETWEEN the two bounds of the stop test (ice_transport_remap.F90:1564-1565 compares dpx with
+        # HTN(i+1,j), dpy with HTE(i,j+1), not with the corner's own): no stop
+        j, i = next((j, i) for j in range(1, 3) for i in range(1, nxb - 2) if q["HTN"][j, i + 1] > 1.05 * q["HTN"][j, i])
+        q["uvel"][j, i] = -0.5 * (q["HTN"][j, i] + q["HTN"][j, i + 1]) / REMAP_DT
+        j, i = next((j, i) for j in range(4, nyb - 2) for i in range(1, 4) if q["HTE"][j + 1, i] > 1.05 * q["HTE"][j, i])
+        q["vvel"][j, i] = -0.5 * (q["HTE"][j, i] + q["HTE"][j + 1, i]) / REMAP_DT
+        # (b) two departure points that mirror each other through the midpoint of a north edge, in exact arithmetic (dx = -/+ 1/4,
+        # dy = +/- 1/8): xic == 0 and ydm == 0, the equalities of `xic >= c0` and `ydm >= c0` (:2564-2565)
+        for i, sgn in ((5, 1.0), (6, -1.0)):
+            q["dxu"][3, i], q["dyu"][3, i] = 4 * REMAP_DT, 8 * REMAP_DT
+            q["uvel"][3, i], q["vvel"][3, i] = sgn, -sgn
+    if var == "t6_stop":
+        q["vvel"][3, 4] = 1.5 * q["HTE"][3, 4] / REMAP_DT; q["uvel"][2, 2] = -1.5 * q["HTN"][2, 2] / REMAP_DT
+    jj, ii = np.meshgrid(np.arange(nyb), np.arange(nxb), indexing="ij")          # a ramp under the noise: few cells are extrema
+    q["phi"], q["cnx"], q["cny"] = 0.35 * ii - 0.25 * jj + 0.8 * h("phi"), 0.2 * (h("cnx") - 0.5), 0.2 * (h("cny") - 0.5)
+    return mm, tm, {k: np.ascontiguousarray(q[k]) for k in REMAP_BLOCK_GRID}, tables, order, midpt
+
+
+# The (group, iflux - i, jflux - j, sign of triarea) signatures locate_triangles can produce with l_fixed_area = .false.,
+# per edge kind.  Source cells (ice_transport_remap.F90:1879-1890 north, :1913-1924 east): TL, BL, TR, BR, TC, BC.  The sign
+# of triarea per group and source cell: REMAP_SIGNS below.
+#   group 1  TL (:2057)  BL (:2072)  TL1 (:2087, with BL1 in group 3)  BL2 (:2115, with TL2 in group 3)
+#   group 2  TR (:2150)  BR (:2165)  TR1 (:2180, with BR1 in group 3)  BR2 (:2208, with TR2 in group 3)
+#   group 3  BL1 (:2087)  TL2 (:2115)  BR1 (:2180)  TR2 (:2208)
+#   groups 4, 5, 6  the TC / BC triangles: all three in TC (:2397), all three in BC (:2478), and the eight crossing cases
+#            ydl >= 0 > ydr (:2564, :2606, :2648, :2690) and ydl < 0 <= ydr (:2732, :2774, :2816, :2858) by the sign of xic and
+#            of ydm, which put group 4 and 5 on opposite sides of the edge and group 6 on the side of ydm.
+# Every signature below must occur on both edge kinds in the chain fixtures; beyond the signatures, REMAP_PATTERNS names the
+# branches by the source cells of several groups of ONE edge, which tells apart what a signature alone cannot.
+# EXCLUDED as unreachable: GROUP 6 altogether.  With l_fixed_area = .false. its triangle is (DL, DR, DM), (DL, IC, DM) or
+# (ICR, ICL, DM) (:2397-2898): DM is the midpoint of DL DR, IC lies on that line, and ICL = ICR = IC (:2047-2050; :2257-2388 move them and DM
+# only when the area is prescribed), so its three vertices are collinear or two of them coincide, its area is zero up to rounding
+# and falls under the eps16 threshold (:2940): the reference lists no group-6 triangle on any fixture (the generator and
+# assert_remap_coverage fail if one appears).  For the same reason the SIGN OF ydm cannot be told from any output: the
+# two branches of each crossing case that differ in it give groups 4 and 5 the same vertices, source cells and area factors
+# and differ in group 6 only; the patterns below therefore tell the crossing cases apart by the sign of xic alone.
+# ALSO EXCLUDED: "ydl >= 0, ydr >= 0, ydm < 0" (:2437) and "ydl < 0, ydr < 0, ydm >= 0" (:2519), both marked rare.  With
+# l_fixed_area = .false. DM is the midpoint of DL DR (:2027-2028) and is never moved; DL / DR are moved to IL / IR (:2242-2250),
+# which lie on the same straight line, so as long as xcl <= xdm <= xcr -- that is |dx_left + dx_right| <= 1, true for every
+# Courant number up to 0.5 -- ydm lies between the two ordinates and cannot have the sign neither has.  (Beyond 0.5 the
+# midpoint can leave the edge's span; REMAP_COURANT stays below.)
+def _shifts(north):
+    return dict(TL=(-1, 1), BL=(-1, 0), TR=(1, 1), BR=(1, 0), TC=(0, 1), BC=(0, 0)) if north else \
+           dict(TL=(1, 1), BL=(0, 1), TR=(1, -1), BR=(0, -1), TC=(1, 0), BC=(0, 0))
+
+
+# group -> (source cell, sign of triarea) it can hold; the sign is that of areafact times the orientation of the three vertices
+# in the order the branch stores them (A > 0 iff counterclockwise, :2934-2938), worked out from CL = (-1/2, 0), CR = (1/2, 0) and
+# the branch's own conditions:  TL (CL, IL, DL) ccw x -  |  BL (CL, DL, IL) ccw x +  |  TL1 (CL, DL, IC) ccw x +  with
+# BL1 (CL, IC, IL) ccw x +  |  TL2 (CL, IL, IC) ccw x -  with BL2 (CL, IC, DL) ccw x -; the right-hand side mirrored;
+# group 4 (CL, CR / IC, DL) is ccw in every branch: - in TC, + in BC; group 5 (CR, DR, DL / IC) is ccw in the crossing cases
+# and "nearly always" otherwise (:2911-2918: when it is not, the quadrilateral is the difference of two triangles): both signs.
+REMAP_SIGNS = {1: (("TL", -1), ("TL", 1), ("BL", 1), ("BL", -1)), 2: (("TR", -1), ("TR", 1), ("BR", 1), ("BR", -1)),
+               3: (("TL", -1), ("BL", 1), ("TR", -1), ("BR", 1)), 4: (("TC", -1), ("BC", 1)),
+               5: (("TC", -1), ("BC", 1), ("TC", 1), ("BC", -1))}
+
+
+def remap_signatures(north):
+    s = _shifts(north)
+    return {(g,) + s[c] + (sign,) for g, cells in REMAP_SIGNS.items() for c, sign in cells}
+
+
+# branch name -> {group: its source cell on one edge, or (cell, False): the group does not hold a triangle of that cell;
+# "xic": sign of xic, 1 standing for `xic >= c0`, 0 for xic == 0 exactly}
+REMAP_PATTERNS = {
+    "TL": {1: "TL", 3: ("BL", False)}, "BL": {1: "BL", 3: ("TL", False)}, "TL1+BL1": {1: "TL", 3: "BL"}, "TL2+BL2": {1: "BL", 3: "TL"},
+    "TR": {2: "TR", 3: ("BR", False)}, "BR": {2: "BR", 3: ("TR", False)}, "TR1+BR1": {2: "TR", 3: "BR"}, "TR2+BR2": {2: "BR", 3: "TR"},
+    "TC*a": {4: "TC", 5: "TC"}, "BC*a": {4: "BC", 5: "BC"},
+    # the crossing cases (:2564-2898) by the sign of xic, read back from the vertex of the BC triangle that lies on the edge
+    "ydl>=0>ydr xic>=0": {4: "TC", 5: "BC", "xic": 1}, "ydl>=0>ydr xic<0": {4: "TC", 5: "BC", "xic": -1},
+    "ydl<0<=ydr xic<0": {4: "BC", 5: "TC", "xic": -1}, "ydl<0<=ydr xic>=0": {4: "BC", 5: "TC", "xic": 1},
+    "ydl>=0>ydr xic==0": {4: "TC", 5: "BC", "xic": 0},          # the mirrored pairs of remap_fields (Euler rule)
+}

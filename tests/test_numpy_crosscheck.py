@@ -217,3 +217,36 @@ def test_numpy_horizontal_remap_equals_c_oracle_on_a_tripole_domain():
     assert npremap.horizontal_remap(g, mw[0], tw[0], dt, ttype, depend, has,
                                     halo_update=lambda a, loc, kind: halo_update(a, loc, C.KIND_SCALAR)) in (0, 2)
     assert not (np.array_equal(mw[0][phys], mo[0][phys]) and np.array_equal(tw[0][:, :, 1:-1, 1:-1], to[0][:, :, 1:-1, 1:-1]))
+
+
+@pytest.mark.parametrize("case", ["cyclic_open", "cyclic_tripole", "open_closed_rim", "cyclic_open_patch", "areas_only"])
+def test_numpy_horizontal_remap_equals_reference_chain(case):
+    """the second reading (tests/npremap.py) against the REFERENCE'S OWN routines run in horizontal_remap's order
+    (tests/golden/ref_remap_g72x20_b72x20.*.npz, the one-block config: npremap works on one block), bit for bit on physical
+    cells, with the pinned halo routine plugged in; and its two stop codes"""
+    from tests import npremap, test_ref_pins as P
+    from tests.golden import refvec as rv
+    cfg = "g72x20_b72x20"
+    assert list(rv.REMAP_CASES) == ["cyclic_open", "cyclic_tripole", "open_closed_rim", "cyclic_open_patch", "areas_only"]
+
+    def run(d, f, mm, tm, tables, order, midpt):
+        def halo_update(a, loc, kind):
+            t = np.ascontiguousarray(a[None])
+            orc.halo_r8(d, t, loc, kind, 0.0)
+            a[...] = t[0]
+        g = {k: v[0] for k, v in f.items() if isinstance(v, np.ndarray) and v.ndim == 3}
+        return npremap.horizontal_remap(g, mm[0], tm[0], rv.REMAP_DT, *tables, order=order, midpt=bool(midpt), halo_update=halo_update)
+
+    z = P.load_remap(cfg, case)
+    d, f, mm, tm, tables = rv.remap_fields(cfg, case)
+    assert d.nblocks == 1
+    bad = []
+    for order, midpt in rv.REMAP_CASES[case][2]:
+        mn, tn = mm.copy(), tm.copy()
+        assert run(d, f, mn, tn, tables, order, midpt) == 0
+        bad += P.remap_diff(d, case, f"o{order}m{midpt}", mn, tn, mm, tm, z)
+    assert not bad, bad[:4]
+    if case == "cyclic_open":
+        for name, (rc, order, midpt) in rv.REMAP_STOPS.items():
+            d, f, mm, tm, tables = rv.remap_fields(cfg, case, stop=name)
+            assert run(d, f, mm.copy(), tm.copy(), tables, order, midpt) == rc, name

@@ -7,7 +7,9 @@ Covered (the ghost-cell part of f-3):
   create_blocks (ice_blocks.F90:111), create_distribution cartesian (ice_distribution.F90:535) incl. land-block elimination
   (ice_domain.F90:387-441), ice_HaloUpdate 2DR8 / 3DR8 / 2DI4 for every field location x field type on cyclic / open /
   closed / tripole grids in 1 and 16 (padded) blocks, ice_HaloUpdate_stress, bound_state (ice_state.F90:173),
-  ice_strength (ice_mechred.F90:2111), global_minval.
+  ice_strength (ice_mechred.F90:2111), global_minval;
+  the dynamics slice (evp_prep1 .. principal_stress, alone and as evp()'s chain) and the remap slice (make_masks .. update_fields
+  of ice_transport_remap.F90, alone and as horizontal_remap's chain, with the count of the triangle branches entered).
 """
 from __future__ import annotations
 
@@ -493,3 +495,233 @@ def test_evp_chain_equals_reference(cfg, case):
             orc.lib().orc_principal_stress(d.nx_block, d.ny_block, P_(fo["stressp_1"][n]), P_(fo["stressm_1"][n]), P_(fo["stress12_1"][n]),
                                            P_(fo["prs_sig"][n]), P_(s1[n]), P_(s2[n]))
         assert np.array_equal(s1[ph], z[f"{pre}/sig1"][ph]) and np.array_equal(s2[ph], z[f"{pre}/sig2"][ph])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# horizontal_remap: the reference's own make_masks / construct_fields / limited_gradient / departure_points /
+# locate_triangles / triangle_coordinates / transport_integrals / update_fields (tests/golden/ref_remap_*.npz; slice and driver:
+# oracle/ref/Makefile, oracle/ref/ref_remap.F90; inputs: refvec.remap_fields / remap_block_inputs)
+def load_remap(cfg, case):
+    return np.load(os.path.join(HERE, "golden", f"ref_remap_{cfg}.{case}.npz"))
+
+
+def assert_remap_coverage(cfg, per_case=None, stops=None):
+    """the branches of locate_triangles the chain fixtures of one config enter, counted by the generator over the REFERENCE'S
+    compressed triangle lists: every signature of refvec.remap_signatures and every branch of refvec.REMAP_PATTERNS on both
+    edge kinds, no signature outside the list, the six (order, rule) pairs, and the two stop cases"""
+    if per_case is None:
+        per_case = {case: load_remap(cfg, case) for case in rv.REMAP_CASES}
+        stops = load_remap(cfg, "stops")
+    sig, pat, combos = {}, {}, set()
+    for case, z in per_case.items():
+        for order, midpt in rv.REMAP_CASES[case][2]:
+            pre = f"o{order}m{midpt}"
+            assert z[f"{pre}/stop"][0] == 0, (cfg, case, pre, "the reference stopped: lower refvec.REMAP_COURANT")
+            combos.add((order, midpt))
+            for e, g, di, dj, s, n in z[f"{pre}/sig"]:
+                sig[(e, g, di, dj, s)] = sig.get((e, g, di, dj, s), 0) + n
+            for e, p, n in z[f"{pre}/pat"]:
+                pat[(e, p)] = pat.get((e, p), 0) + n
+    assert combos == {(o, m) for o in (1, 2, 3) for m in (0, 1)}
+    names = list(rv.REMAP_PATTERNS)
+    for e in (0, 1):
+        want = rv.remap_signatures(e == 1)
+        got = {k[1:] for k in sig if k[0] == e}
+        assert want <= got, (cfg, "edge kind", e, "signatures never produced:", sorted(want - got))
+        assert got <= want, (cfg, "edge kind", e, "signatures outside the derived list:", sorted(got - want))
+        missing = [names[p] for p in range(len(names)) if pat.get((e, p), 0) == 0]
+        assert not missing, (cfg, "edge kind", e, "branches never entered:", missing)
+    for name, (rc, _, _) in rv.REMAP_STOPS.items():
+        assert stops[name][0] == rc, (name, stops[name])
+    return sig, pat
+
+
+@pytest.mark.parametrize("cfg", list(rv.KERNEL_CONFIGS))
+def test_remap_fixtures_cover_the_triangle_branches(cfg):
+    sig, pat = assert_remap_coverage(cfg)
+    assert min(sig.values()) >= 1 and min(pat.values()) >= 1
+
+
+def remap_phys(d, a):
+    """the physical cells of a (nblocks, ..., ny, nx) array, and the rest"""
+    m = np.zeros((d.nblocks,) + (1,) * (a.ndim - 3) + (d.ny_block, d.nx_block), dtype=bool)
+    for n, b in enumerate(d.local_blocks):
+        m[n, ..., b.jlo - 1:b.jhi, b.ilo - 1:b.ihi] = True
+    return np.broadcast_to(m, a.shape)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int64)
+
+
+def remap_diff(d, case, pre, got_m, got_t, mm, tm, z):
+    """differences from a chain record: physical cells bit for bit (signed zeros included), ghost cells as they were"""
+    bad = []
+    for name, got, inp, want in (("mm", got_m, mm, z[f"{pre}/mm"]), ("tm", got_t, tm, z[f"{pre}/tm"])):
+        ph = remap_phys(d, got)
+        if not np.array_equal(_bits(got)[ph], _bits(want)[ph]):
+            k = np.argwhere((_bits(got) != _bits(want)) & ph)
+            bad.append((case, pre, name, len(k), [(tuple(int(v) for v in q), float(got[tuple(q)]), float(want[tuple(q)])) for q in k[:3]]))
+        if not np.array_equal(_bits(got)[~ph], _bits(inp)[~ph]):
+            bad.append((case, pre, name, "ghost cells written", int((_bits(got) != _bits(inp))[~ph].sum())))
+    return bad
+
+
+@pytest.mark.parametrize("case", list(rv.REMAP_CASES))
+@pytest.mark.parametrize("cfg", list(rv.KERNEL_CONFIGS))
+def test_horizontal_remap_equals_reference_chain(cfg, case):
+    """orc_horizontal_remap == the reference's own routines run in horizontal_remap's order with its own halo updates, on every
+    physical cell of mm and tm, bit for bit: rough velocities whose sign changes from corner to corner (every triangle branch,
+    see assert_remap_coverage), corners at rest, masses around puny, tracers with dependents around puny, 1 and 16 padded
+    blocks, cyclic / open / closed / tripole boundaries, land, six tracers of the three types and none"""
+    z = load_remap(cfg, case)
+    d, f, mm, tm, tables = rv.remap_fields(cfg, case)
+    bad = []
+    for order, midpt in rv.REMAP_CASES[case][2]:
+        mo, to = mm.copy(), tm.copy()
+        assert orc.horizontal_remap(d, rv.REMAP_DT, f, mo, to, *tables, integral_order=order, l_dp_midpt=bool(midpt)) == 0
+        assert np.abs(mo - mm).max() > 1e-3
+        bad += remap_diff(d, case, f"o{order}m{midpt}", mo, to, mm, tm, z)
+    assert not bad, bad[:4]
+
+
+@pytest.mark.parametrize("cfg", list(rv.KERNEL_CONFIGS))
+def test_horizontal_remap_stop_cases_equal_reference(cfg):
+    """the reference's two l_stop cases: 1 where departure_points stops, 2 where update_fields meets a negative mass"""
+    z = load_remap(cfg, "stops")
+    for name, (rc, order, midpt) in rv.REMAP_STOPS.items():
+        assert z[name][0] == rc
+        d, f, mm, tm, tables = rv.remap_fields(cfg, "cyclic_open", stop=name)
+        assert orc.horizontal_remap(d, rv.REMAP_DT, f, mm.copy(), tm.copy(), *tables, integral_order=order, l_dp_midpt=bool(midpt)) == rc, name
+
+
+def _same_bits(got, want, where):
+    """equal bit for bit: -0.0 and +0.0 differ"""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.dtype == want.dtype and got.shape == want.shape, (where, got.dtype, want.dtype, got.shape, want.shape)
+    ne = got.view(np.int64) != want.view(np.int64) if got.dtype == np.float64 else got != want
+    assert not ne.any(), (where, int(ne.sum()), [(k, float(got[tuple(k)]), float(want[tuple(k)])) for k in np.argwhere(ne)[:4].tolist()])
+
+
+def load_remap_blk(var):
+    return np.load(os.path.join(HERE, "golden", f"ref_remap_blk.{var}.npz"))
+
+
+def _listed(z, pre, e):
+    """(group, j, i) index arrays of the reference's compressed triangle lists: the only entries of xp, yp, iflux, jflux its
+    arrays define"""
+    ic, ii, jj = z[f"{pre}/locate_triangles/{e}/icells"], z[f"{pre}/locate_triangles/{e}/indxi"], z[f"{pre}/locate_triangles/{e}/indxj"]
+    g = np.concatenate([np.full(ic[k], k) for k in range(6)])
+    i = np.concatenate([ii[k, :ic[k]] for k in range(6)]) - 1
+    j = np.concatenate([jj[k, :ic[k]] for k in range(6)]) - 1
+    return g, j, i
+
+
+@pytest.mark.parametrize("var", list(rv.REMAP_BLOCK_VARIANTS))
+def test_remap_single_routines_equal_reference(var):
+    """each of the eight routines of ice_transport_remap ALONE: the C restatement's routine on the reference's recorded input of
+    that routine (what the routine before it returned) == the reference's recorded output, bit for bit with signed zeros.
+    Blocks: a full 8 x 5 block and a padded 2 x 3 one; variants: six tracers of types 1 1 1 2 2 3 with integral orders 3, 2, 1
+    and both departure-point rules, a table with one tracer with dependents, no tracers, and the departure-point stop.
+    Compared where the Fortran defines its arrays: triangle vertices, iflux / jflux through the compressed lists; the open-
+    water mc on physical cells (the reference lists open water over the whole block, make_masks :930-943, so its
+    construct_fields also sets mc = mm in ghost cells, which horizontal_remap's halo update overwrites: a difference of
+    interface, asserted here)."""
+    L, z = orc.lib(), load_remap_blk(var)
+    cfg = rv.REMAP_BLOCK_CFG
+    nx, ny = rv.KERNEL_CONFIGS[cfg][2] + 2, rv.KERNEL_CONFIGS[cfg][3] + 2
+    ncat, P32 = rv.REMAP_NCAT, orc._p32
+    c = np.ascontiguousarray
+    checked = 0
+    for rec, (ilo, ihi, jlo, jhi) in rv.BLOCK_RECORDS[cfg].items():
+        pre = f"{rec}/{var}"
+        mm, tm, q, (ttype, depend, has), order, midpt = rv.remap_block_inputs(rec, var)
+        nt = len(ttype)
+        ttype, depend, has = c(ttype, dtype=np.int32), c(depend, dtype=np.int32), c(has, dtype=np.int32)
+        box = (nx, ny, ilo, ihi, jlo, jhi)
+        phys = np.zeros((ny, nx), dtype=bool); phys[jlo - 1:jhi, ilo - 1:ihi] = True
+        eq = lambda got, key: _same_bits(got, z[f"{pre}/{key}"], (pre, key))
+        N = lambda a: (P32(a) if a.dtype == np.int32 else P_(a)) if a.size else None
+        # make_masks
+        mmask, tmask, icells = np.zeros_like(mm), np.zeros_like(tm), np.zeros(ncat + 1, dtype=np.int32)
+        for n in range(ncat + 1):
+            L.orc_remap_make_masks(*box, int(n == 0), nt, P32(has) if nt else None, P_(c(mm[n])), P_(mmask[n]), N(tm[n - 1]) if n else None,
+                                   N(tmask[n - 1]) if n else None, P32(icells[n:n + 1]))
+        eq(mmask, "make_masks/mmask"); eq(tmask, "make_masks/tmask")
+        assert np.array_equal(icells, z[f"{pre}/make_masks/icells"]), (pre, icells, z[f"{pre}/make_masks/icells"])
+        rm, rt = z[f"{pre}/make_masks/mmask"], z[f"{pre}/make_masks/tmask"]
+        # limited_gradient
+        gx, gy = np.zeros((ny, nx)), np.zeros((ny, nx))
+        L.orc_remap_limited_gradient(*box, P_(q["phi"]), P_(c(rm[1])), P_(q["cnx"]), P_(q["cny"]), P_(gx), P_(gy))
+        eq(gx, "limited_gradient/gx"); eq(gy, "limited_gradient/gy")
+        live = int((rm[1][phys] > 0).sum())                         # phi is a ramp under noise: few of the unmasked cells are extrema
+        assert rec == "pad" or (live >= 10 and min(np.count_nonzero(gx), np.count_nonzero(gy)) >= live // 2), (live, np.count_nonzero(gx))
+        # construct_fields
+        mc, mx, my = np.zeros_like(mm), np.zeros_like(mm), np.zeros_like(mm)
+        tc, tx, ty = np.zeros_like(tm), np.zeros_like(tm), np.zeros_like(tm)
+        for n in range(ncat + 1):
+            wt = n > 0
+            L.orc_remap_construct_fields(*box, nt, N(ttype), N(depend), N(has), P_(q["hm"]), P_(c(mm[n])), P_(mc[n]), P_(mx[n]), P_(my[n]),
+                                         P_(c(rm[n])), P_(c(tm[n - 1])) if wt else None, P_(tc[n - 1]) if wt else None,
+                                         P_(tx[n - 1]) if wt else None, P_(ty[n - 1]) if wt else None, P_(c(rt[n - 1])) if wt else None)
+        want0 = z[f"{pre}/construct_fields/mc"][0]
+        _same_bits(mc[1:], z[f"{pre}/construct_fields/mc"][1:], (pre, "mc")); _same_bits(mc[0][phys], want0[phys], (pre, "mc open water"))
+        assert np.array_equal(want0[~phys], np.where(mm[0] > 1e-11, mm[0], 0.0)[~phys]) and not mc[0][~phys].any()
+        for k, a in (("mx", mx), ("my", my), ("tc", tc), ("tx", tx), ("ty", ty)):
+            eq(a, f"construct_fields/{k}")
+        rmc, rmx, rmy = (z[f"{pre}/construct_fields/{k}"] for k in ("mc", "mx", "my"))
+        rtc, rtx, rty = (z[f"{pre}/construct_fields/{k}"] for k in ("tc", "tx", "ty"))
+        # departure_points
+        dpx, dpy, ij = np.zeros((ny, nx)), np.zeros((ny, nx)), np.zeros(2, dtype=np.int32)
+        stop = L.orc_remap_departure_points(*box, rv.REMAP_DT, *(P_(q[k]) for k in ("uvel", "vvel", "dxu", "dyu", "HTN", "HTE")), P_(dpx), P_(dpy),
+                                            midpt, P32(ij))
+        assert (stop, ij[0], ij[1]) == tuple(z[f"{pre}/departure_points/stop"]), (pre, stop, ij, z[f"{pre}/departure_points/stop"])
+        eq(dpx, "departure_points/dpx"); eq(dpy, "departure_points/dpy")
+        checked += 1
+        if stop:
+            assert var == "t6_stop"
+            continue
+        rdx, rdy = c(z[f"{pre}/departure_points/dpx"]), c(z[f"{pre}/departure_points/dpy"])
+        flx = {}
+        for e, north in (("east", 0), ("north", 1)):
+            # locate_triangles
+            xp, yp = np.zeros((6, 4, ny, nx)), np.zeros((6, 4, ny, nx))
+            ifl, jfl, tri = np.zeros((6, ny, nx), dtype=np.int32), np.zeros((6, ny, nx), dtype=np.int32), np.zeros((6, ny, nx))
+            L.orc_remap_locate_triangles(*box, north, P_(rdx), P_(rdy), P_(q["dxu"]), P_(q["dyu"]), P_(xp), P_(yp), P32(ifl), P32(jfl), P_(tri))
+            g, j, i = _listed(z, pre, e)
+            assert len(g) > (4 if rec == "pad" else 40)
+            eq(tri, f"locate_triangles/{e}/triarea")                 # zero wherever no triangle is listed, on both sides
+            assert np.array_equal(np.argwhere(tri != 0), np.array(sorted(zip(g, j, i))).reshape(-1, 3))
+            for k, a in (("iflux", ifl), ("jflux", jfl)):
+                assert np.array_equal(a[g, j, i], z[f"{pre}/locate_triangles/{e}/{k}"][g, j, i]), (pre, e, k)
+            for k, a in (("xp", xp), ("yp", yp)):
+                _same_bits(a[g, 1:, j, i], z[f"{pre}/locate_triangles/{e}/{k}"][g, 1:, j, i], (pre, e, k))
+            # triangle_coordinates, on the reference's vertices
+            rtri = c(z[f"{pre}/locate_triangles/{e}/triarea"])
+            xq, yq = c(z[f"{pre}/locate_triangles/{e}/xp"]), c(z[f"{pre}/locate_triangles/{e}/yp"])
+            L.orc_remap_triangle_coordinates(nx, ny, order, P_(rtri), P_(xq), P_(yq))
+            for k, a in (("xp", xq), ("yp", yq)):
+                _same_bits(a[g, :, j, i], z[f"{pre}/triangle_coordinates/{e}/{k}"][g, :, j, i], (pre, e, k, "coordinates"))
+            # transport_integrals, on the reference's triangles and fields
+            rxp, ryp = c(z[f"{pre}/triangle_coordinates/{e}/xp"]), c(z[f"{pre}/triangle_coordinates/{e}/yp"])
+            rif, rjf = c(z[f"{pre}/locate_triangles/{e}/iflux"]), c(z[f"{pre}/locate_triangles/{e}/jflux"])
+            mflx, mtflx = np.zeros_like(mm), np.zeros_like(tm)
+            for n in range(ncat + 1):
+                wt = n > 0
+                L.orc_remap_transport_integrals(nx, ny, nt, N(ttype), N(depend), order, P_(rtri), P32(rif), P32(rjf), P_(rxp), P_(ryp),
+                                                P_(c(rmc[n])), P_(c(rmx[n])), P_(c(rmy[n])), P_(mflx[n]),
+                                                P_(c(rtc[n - 1])) if wt else None, P_(c(rtx[n - 1])) if wt else None,
+                                                P_(c(rty[n - 1])) if wt else None, P_(mtflx[n - 1]) if wt else None)
+            eq(mflx, f"transport_integrals/{e}/mflx"); eq(mtflx, f"transport_integrals/{e}/mtflx")
+            assert rec == "pad" or np.count_nonzero(mflx) > 40
+            flx[e] = (z[f"{pre}/transport_integrals/{e}/mflx"], z[f"{pre}/transport_integrals/{e}/mtflx"])
+        # update_fields, on the reference's fluxes
+        um, ut, stops = mm.copy(), tm.copy(), np.zeros((ncat + 1, 3), dtype=np.int32)
+        for n in range(ncat + 1):
+            wt = n > 0
+            stops[n, 0] = L.orc_remap_update_fields(*box, nt, N(ttype), N(depend), P_(q["tarear"]), P_(c(flx["east"][0][n])), P_(c(flx["north"][0][n])),
+                                                    P_(um[n]), P_(c(flx["east"][1][n - 1])) if wt else None,
+                                                    P_(c(flx["north"][1][n - 1])) if wt else None, P_(ut[n - 1]) if wt else None, P32(stops[n, 1:]))
+        assert np.array_equal(stops, z[f"{pre}/update_fields/stop"]), (pre, stops, z[f"{pre}/update_fields/stop"])
+        eq(um, "update_fields/mm"); eq(ut, "update_fields/tm")
+    assert checked == 2

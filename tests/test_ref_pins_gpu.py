@@ -10,7 +10,10 @@ oracle/ref/Makefile; inputs tests/golden/refvec.py) -- the device counterparts o
   * the EVP dynamics (evpk_run, and evpk_upload / prep / subcycle / finish / download in pieces) against the chain records of
     tests/golden/ref_dyn_*.npz -- the reference's own evp_prep1, evp_prep2, stress, stepu, evp_finish run in evp()'s call order
     with its own halo updates -- under every subcycle-kernel variant, with evpk_principal_stress and the cell counts.  The
-    T<->U averages (to_ugrid / to_tgrid) are not part of the reference build and stay pinned by the restatement alone.
+    T<->U averages (to_ugrid / to_tgrid) are not part of the reference build and stay pinned by the restatement alone;
+  * horizontal_remap (evpk_transport_remap) against the chain records of tests/golden/ref_remap_*.npz -- the reference's own
+    make_masks .. update_fields run in horizontal_remap's order with its own halo updates -- under every remap-kernel variant,
+    with the return codes of its two stop cases.
 """
 from __future__ import annotations
 
@@ -323,3 +326,61 @@ def test_device_evp_in_pieces_equals_reference_chain(cfg):
     for case in rv.DYN_CASES:
         bad += _dyn_chain(cfg, case, 6, pieces=[2, 3, 1])
     assert not bad, bad[:6]
+
+
+REMAP_VARIANTS = {"default": {}, "unfused": {"EVPK_REMAP_FUSED": "0"}, "planes": {"EVPK_REMAP_DIRECT": "0"}, "exchange": {"EVPK_FORCE_EXCHANGE": "1"}}
+
+
+def _remap_device(d, f, mm, tm, tables, order, midpt):
+    """evpk_transport_remap on uploaded velocities, as tests/test_parity_gpu.py's _remap_on_device"""
+    from cice5_amd import dyn
+    from tests.golden import refvec as rv
+    s = dyn.EvpDynamics(d, f, ndte=10, xmin=1.0e4)
+    try:
+        s.set_evp_parameters(3600.0)
+        s.ctx.upload(f)
+        s.ctx.remap_init(f["dxu"], f["dyu"], f["hm"])
+        return s.ctx.transport_remap(rv.REMAP_DT, mm, tm if tm.shape[2] else None, *tables, integral_order=order, l_dp_midpt=bool(midpt))
+    finally:
+        s.close()
+
+
+@pytest.mark.parametrize("variant", list(REMAP_VARIANTS))
+@pytest.mark.parametrize("cfg", ["g72x20_b72x20", "g26x18_b8x5"])
+def test_device_transport_remap_equals_reference_chain(cfg, variant, monkeypatch):
+    """evpk_transport_remap == the reference's own make_masks -> construct_fields -> departure_points -> halo updates ->
+    locate_triangles -> triangle_coordinates -> transport_integrals -> update_fields (tests/golden/ref_remap_*.npz), bit for
+    bit on the physical cells of mm and tm with the ghost cells untouched: every boundary / land case, six tracers of the
+    three types and none, integral orders 1 - 3 and both departure-point rules, velocities that enter every triangle branch
+    (tests/test_ref_pins.py: assert_remap_coverage).  variant: the fused tile kernel, three kernels through memory, planes
+    and a scatter pass, the forced exchange path."""
+    from tests import test_ref_pins as P
+    from tests.golden import refvec as rv
+    for k, v in REMAP_VARIANTS[variant].items():
+        monkeypatch.setenv(k, v)
+    P.assert_remap_coverage(cfg)
+    bad = []
+    for case in rv.REMAP_CASES:
+        z = P.load_remap(cfg, case)
+        d, f, mm, tm, tables = rv.remap_fields(cfg, case)
+        for order, midpt in rv.REMAP_CASES[case][2]:
+            mg, tg = mm.copy(), tm.copy()
+            rc = _remap_device(d, f, mg, tg, tables, order, midpt)
+            if rc != 0:
+                bad.append((case, order, midpt, "rc", rc))
+            bad += P.remap_diff(d, case, f"o{order}m{midpt}", mg, tg, mm, tm, z)
+    assert not bad, bad[:4]
+
+
+@pytest.mark.parametrize("cfg", ["g72x20_b72x20", "g26x18_b8x5"])
+def test_device_transport_remap_stop_cases_equal_reference(cfg):
+    """the reference's two l_stop cases come back as REMAP_BAD_DEPARTURE / REMAP_NEGATIVE_MASS"""
+    from cice5_amd import evpk
+    from tests import test_ref_pins as P
+    from tests.golden import refvec as rv
+    z = P.load_remap(cfg, "stops")
+    codes = {1: evpk.REMAP_BAD_DEPARTURE, 2: evpk.REMAP_NEGATIVE_MASS}
+    for name, (rc, order, midpt) in rv.REMAP_STOPS.items():
+        assert z[name][0] == rc
+        d, f, mm, tm, tables = rv.remap_fields(cfg, "cyclic_open", stop=name)
+        assert _remap_device(d, f, mm.copy(), tm.copy(), tables, order, midpt) == codes[rc], name
