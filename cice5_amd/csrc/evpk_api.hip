@@ -31,6 +31,7 @@
 // single translation unit: the kernels are compiled together with the host API
 #include "evpk_kernels.hip"
 #include "evpk_remap.hip"
+#include "evpk_ridge.hip"
 #include "evpk_eap.hip"
 
 using namespace evpk;
@@ -335,6 +336,12 @@ struct evpk_ctx {
     double *uw_pool = nullptr; size_t uw_pool_n = 0;      // evpk_transport_upwind_state: one input + 3 + ntrcr output planes
     double **uw_tab = nullptr; signed char *uw_sgn = nullptr;
     size_t rm_pool_n = 0, rm_stage_n = 0, rm_tab_n = 0;
+    // evpk_ridge_ice: the planes that pass between its kernels, the ridging masks, the per-iteration block flags, the control words, staging
+    double *rg_pool = nullptr, *rg_stage = nullptr;
+    unsigned *rg_mask = nullptr;
+    int *rg_flags = nullptr;
+    RidgeCtl *rg_ctl = nullptr;
+    size_t rg_pool_n = 0, rg_stage_n = 0, rg_mask_n = 0, rg_flags_n = 0;
     // EAP (kdyn = 2): set by evpk_eap_init -- the subcycle loop then runs stress_eap / stepu / stepa (evpk_eap.hip)
     bool eap = false;
     EapDev E{};
@@ -1297,7 +1304,7 @@ static void destroy_impl(evpk_ctx *c) {
     if (c->relay) { c->relay->close_(); delete c->relay; }
     if (c->ipc) { if (c->stream2) (void)hipStreamSynchronize(c->stream2); c->ipc->close_(); delete c->ipc; }
     void *ptrs[] = {c->itd, c->stage_itd, c->d_zflags, c->d_zrows, c->s.F, c->s.tmask, c->s.umask, c->s.iceumask, c->s.cmask, c->s.tmphm, c->d_bd, c->stage, c->d_flags,
-                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
+                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_stage, c->rg_mask, c->rg_flags, c->rg_ctl, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -3372,6 +3379,163 @@ extern "C" int evpk_transport_upwind_state(evpk_ctx *c, double dt, int32_t ncat,
         if (staged[q]) HIPCHK(c, hipMemcpyAsync(host5[q], dev5[q], sizeof(double) * n5[q], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return xp_check(c);
+}
+
+// ---- ridge_ice (source/ice_mechred.F90:101-746) on the caller's state arrays (kernels in evpk_ridge.hip) ----
+extern "C" int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
+                              const evpk_ridge_tracers *t, const double *hin_max, const double *rdg_conv, const double *rdg_shear, double *aice0,
+                              double *aicen, double *vicen, double *vsnon, double *trcrn, evpk_ridge_diag *diag, int32_t stop[4]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = 0;
+    if (c->nranks > 1) FAIL(c, "evpk_ridge_ice: nranks = %d: ridging on more than one rank is not supported yet", c->nranks);
+    if (!t || !hin_max || !aice0 || !aicen || !vicen || !vsnon || !stop || ntrcr < 0 || ntrcr_dim < ntrcr || (ntrcr > 0 && (!trcrn || !trcr_depend)))
+        FAIL(c, "evpk_ridge_ice: a required argument is missing");
+    if (!c->connected) FAIL(c, "evpk_ridge_ice: the context is not connected yet (evpk_connect)");
+    if (!c->have_params) FAIL(c, "evpk_ridge_ice: evpk_set_params has not been called (krdg_partic, krdg_redist, mu_rdg, rhos)");
+    if (!(dt > 0.0) || ndtd < 1) FAIL(c, "evpk_ridge_ice: dt = %g, ndtd = %d", dt, ndtd);
+    if (ncat < 1 || ncat > MAXCAT) FAIL(c, "evpk_ridge_ice: ncat = %d not in 1..%d", ncat, MAXCAT);
+    if (ntrcr > RG_MAXT) FAIL(c, "evpk_ridge_ice: ntrcr = %d exceeds %d", ntrcr, RG_MAXT);
+    if (c->p.krdg_redist == 0)
+        FAIL(c, "evpk_ridge_ice: krdg_redist = 0 is not supported: the reference's ridge_shift reads hrmax with the index of its compressed "
+                "list of ridging cells (ice_mechred.F90:1724-1725), so its result depends on which other cells of the block ridge");
+    if (c->p.krdg_partic != 0 && c->p.krdg_partic != 1) FAIL(c, "evpk_ridge_ice: krdg_partic = %d", c->p.krdg_partic);
+    if ((rdg_conv == nullptr) != (rdg_shear == nullptr)) FAIL(c, "evpk_ridge_ice: rdg_conv and rdg_shear must both be given or both be NULL");
+    if (!rdg_conv && !(c->prepped && c->ksub >= c->p.ndte))
+        FAIL(c, "evpk_ridge_ice: rdg_conv = NULL needs the deformation rates of a finished evp / eap on the device");
+    const int nts[] = {t->nt_qsno, t->nt_alvl, t->nt_vlvl, t->nt_apnd, t->nt_hpnd, t->nt_fbri};
+    for (int q : nts) if (q < 0 || q > ntrcr) FAIL(c, "evpk_ridge_ice: tracer index %d not in 0..ntrcr = %d", q, ntrcr);
+    if (t->nslyr < 0 || (t->nslyr > 0 && (t->nt_qsno < 1 || t->nt_qsno + t->nslyr - 1 > ntrcr))) FAIL(c, "evpk_ridge_ice: nt_qsno / nslyr beyond ntrcr");
+    if (t->tr_pond_topo && (t->nt_apnd < 1 || t->nt_hpnd < 1)) FAIL(c, "evpk_ridge_ice: tr_pond_topo without nt_apnd / nt_hpnd");
+    if (t->tr_pond_lvl && t->nt_apnd > 0 && t->nt_alvl < 1) FAIL(c, "evpk_ridge_ice: tr_pond_lvl without nt_alvl");
+    if (!c->nblocks) return 0;
+    Slab &s = c->s;
+    HIPCHK(c, hipSetDevice(c->device));
+    RidgeArgs A{};
+    A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
+    A.nt_qsno = t->nt_qsno; A.nslyr = t->nslyr; A.nt_alvl = t->nt_alvl; A.nt_vlvl = t->nt_vlvl; A.nt_apnd = t->nt_apnd; A.nt_hpnd = t->nt_hpnd;
+    A.nt_fbri = t->nt_fbri; A.tr_pond_topo = t->tr_pond_topo ? 1 : 0;
+    A.dt = dt; A.dti_thermo = 1.0 / (ndtd * dt);
+    for (int n = 0; n <= ncat; n++) A.hin_max[n] = hin_max[n];
+    A.hin_max[ncat] = 1.0e8;
+    const bool pond_at = t->tr_pond_cesm || t->tr_pond_topo;
+    for (int it = 1; it <= ntrcr; it++) {
+        const int dep = trcr_depend[it - 1], k = it - 1;
+        // how atrcrn is built (:1456-1513) and compute_tracers (ice_itd.F90:1407-1499), their branches in the reference's order
+        A.acc[k] = -1; A.rule[k] = -1; A.d1[k] = 0; A.d2[k] = 0; A.slot[k] = 0;
+        if (dep == 0) { A.acc[k] = 0; A.rule[k] = 1; }
+        else if (dep == 1) { A.acc[k] = 1; A.rule[k] = 2; }
+        else if (dep == 2) { A.acc[k] = 2; A.rule[k] = 3; }
+        else if (t->nt_fbri > 0 && dep == 2 + t->nt_fbri) { A.acc[k] = 6; A.rule[k] = 6; A.d1[k] = 3; }
+        else if (t->nt_alvl > 0 && dep == 2 + t->nt_alvl) { A.acc[k] = 3; A.rule[k] = 4; A.d1[k] = 1; }
+        else if (t->nt_apnd > 0 && dep == 2 + t->nt_apnd && pond_at) { A.acc[k] = 4; A.rule[k] = 4; A.d1[k] = 2; }
+        else if (t->nt_apnd > 0 && dep == 2 + t->nt_apnd && t->tr_pond_lvl) { A.acc[k] = 5; A.rule[k] = 5; A.d1[k] = 1; A.d2[k] = 2; }
+        if (it == t->nt_alvl) A.slot[k] = 1;
+        else if (it == t->nt_apnd) A.slot[k] = 2;
+        else if (it == t->nt_fbri) A.slot[k] = 3;
+    }
+    const size_t nblk = (size_t)c->nyb * c->nxb, nb = (size_t)c->nblocks, N = nb * nblk;
+    // the caller's arrays: in place where the device sees them, else through a staging copy (up, and down again at the end)
+    evpk_ridge_diag dg{};
+    if (diag) dg = *diag;
+    struct Arr { double *host; size_t n; double **slot; bool out; };
+    const size_t n2 = N, n3 = N * ncat;
+    Arr arr[] = {
+        {aice0, n2, &A.aice0, true}, {aicen, n3, &A.aicen, true}, {vicen, n3, &A.vicen, true}, {vsnon, n3, &A.vsnon, true},
+        {ntrcr ? trcrn : nullptr, n3 * ntrcr_dim, &A.trcrn, true},
+        {const_cast<double *>(rdg_conv), n2, const_cast<double **>(&A.rdg_conv), false}, {const_cast<double *>(rdg_shear), n2, const_cast<double **>(&A.rdg_shear), false},
+        {dg.dardg1dt, n2, &A.dardg1dt, true}, {dg.dardg2dt, n2, &A.dardg2dt, true}, {dg.dvirdgdt, n2, &A.dvirdgdt, true}, {dg.opening, n2, &A.opening, true},
+        {dg.fpond, n2, &A.fpond, true}, {dg.fresh, n2, &A.fresh, true}, {dg.fhocn, n2, &A.fhocn, true},
+        {dg.dardg1ndt, n3, &A.dardg1ndt, true}, {dg.dardg2ndt, n3, &A.dardg2ndt, true}, {dg.dvirdgndt, n3, &A.dvirdgndt, true},
+        {dg.aparticn, n3, &A.aparticn, true}, {dg.krdgn, n3, &A.krdgn, true}, {dg.araftn, n3, &A.araftn, true}, {dg.vraftn, n3, &A.vraftn, true},
+        {dg.aredistn, n3, &A.aredistn, true}, {dg.vredistn, n3, &A.vredistn, true}};
+    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
+    bool staged[NARR];
+    size_t need = 0;
+    for (int q = 0; q < NARR; q++) {
+        *arr[q].slot = (arr[q].host && arr[q].n) ? (double *)mapped_alias(arr[q].host, sizeof(double) * arr[q].n) : nullptr;
+        staged[q] = arr[q].host && arr[q].n && !*arr[q].slot;
+        if (staged[q]) need += arr[q].n;
+    }
+    if (c->rg_stage_n < need) {
+        if (c->rg_stage) (void)hipFree(c->rg_stage);
+        c->rg_stage = nullptr; c->rg_stage_n = 0;
+        HIPCHK(c, hipMalloc(&c->rg_stage, sizeof(double) * need));
+        c->rg_stage_n = need;
+    }
+    {
+        double *q2 = c->rg_stage;
+        for (int q = 0; q < NARR; q++)
+            if (staged[q]) {
+                HIPCHK(c, hipMemcpyAsync(q2, arr[q].host, sizeof(double) * arr[q].n, hipMemcpyHostToDevice, c->stream));
+                *arr[q].slot = q2; q2 += arr[q].n;
+            }
+    }
+    const size_t npool = RidgePool::planes(ncat) * N, nflags = (size_t)(RG_NITER + 1) * nb;
+    if (c->rg_pool_n < npool) {
+        if (c->rg_pool) (void)hipFree(c->rg_pool);
+        c->rg_pool = nullptr; c->rg_pool_n = 0;
+        HIPCHK(c, hipMalloc(&c->rg_pool, sizeof(double) * npool));
+        c->rg_pool_n = npool;
+    }
+    if (c->rg_mask_n < N) {
+        if (c->rg_mask) (void)hipFree(c->rg_mask);
+        c->rg_mask = nullptr; c->rg_mask_n = 0;
+        HIPCHK(c, hipMalloc(&c->rg_mask, sizeof(unsigned) * N));
+        c->rg_mask_n = N;
+    }
+    if (c->rg_flags_n < nflags) {
+        if (c->rg_flags) (void)hipFree(c->rg_flags);
+        c->rg_flags = nullptr; c->rg_flags_n = 0;
+        HIPCHK(c, hipMalloc(&c->rg_flags, sizeof(int) * nflags));
+        c->rg_flags_n = nflags;
+    }
+    if (!c->rg_ctl) HIPCHK(c, hipMalloc(&c->rg_ctl, sizeof(RidgeCtl)));
+    RidgeCtl h{};
+    h.key = ~0ull;
+    HIPCHK(c, hipMemcpyAsync(c->rg_ctl, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->rg_flags, 0, sizeof(int) * nflags, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (h and staged caller arrays are pageable)
+    RidgePool P{c->rg_pool, c->rg_mask, N, ncat};
+    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
+    int reason = 0, iters = 0;
+    for (int iter = 1; iter <= RG_NITER && !reason; iter++) {
+        if (ncat == 5) {
+            hipLaunchKernelGGL(k_ridge_weights<5>, g, b, 0, c->stream, s, c->p, (const BlockDesc *)c->d_bd, A, P, iter, c->rg_flags, c->nblocks, c->rg_ctl);
+            hipLaunchKernelGGL(k_ridge_tracers<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, P, iter, (const int *)c->rg_flags, c->nblocks);
+        } else {
+            hipLaunchKernelGGL(k_ridge_weights<0>, g, b, 0, c->stream, s, c->p, (const BlockDesc *)c->d_bd, A, P, iter, c->rg_flags, c->nblocks, c->rg_ctl);
+            hipLaunchKernelGGL(k_ridge_tracers<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, P, iter, (const int *)c->rg_flags, c->nblocks);
+        }
+        HIPCHK(c, hipGetLastError());
+        // what the host learns per iteration: the stop key and whether any block repeats
+        HIPCHK(c, hipMemcpyAsync(&h, c->rg_ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        iters = iter;
+        if (h.key != ~0ull) reason = ((h.key >> 40) & 0xf) == 0 ? RG_STOP_AICE0 : RG_STOP_ARDG;
+        else if (!h.any[iter]) break;
+        else if (iter == RG_NITER) reason = RG_STOP_NITER;
+    }
+    if (!reason) {
+        hipLaunchKernelGGL(k_ridge_diag, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, P, c->rg_ctl);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&h, c->rg_ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h.key != ~0ull) reason = RG_STOP_ASUM;
+    }
+    if (reason == RG_STOP_NITER) {          // the first block that still repeats
+        std::vector<int> fl(nb);
+        HIPCHK(c, hipMemcpy(fl.data(), c->rg_flags + (size_t)RG_NITER * nb, sizeof(int) * nb, hipMemcpyDeviceToHost));
+        stop[0] = reason;
+        for (size_t q = 0; q < nb; q++) if (fl[q]) { stop[1] = (int32_t)q + 1; break; }
+    } else if (reason) {
+        const size_t o = (size_t)(h.key & 0xffffffffull);
+        stop[0] = reason; stop[1] = (int32_t)(h.key >> 44) + 1; stop[2] = (int32_t)(o % c->nxb) + 1; stop[3] = (int32_t)(o / c->nxb) + 1;
+    }
+    (void)iters;
+    for (int q = 0; q < NARR; q++)
+        if (staged[q] && arr[q].out) HIPCHK(c, hipMemcpyAsync(arr[q].host, *arr[q].slot, sizeof(double) * arr[q].n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return reason ? EVPK_RIDGE_STOP : 0;
 }
 
 // ---- transport_remap's horizontal_remap (source/ice_transport_remap.F90:309-850) on the resident velocities ----

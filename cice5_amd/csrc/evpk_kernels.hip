@@ -458,6 +458,92 @@ __device__ __forceinline__ double dev_exp(double x) {
 
 constexpr int MAXCAT = 16;
 
+// ridge_itd (ice_mechred.F90:936-1285) of one cell, shared by k_ice_strength and the ridging kernels (evpk_ridge.hip): aicen(n), vicen(n)
+// n = 1..ncat; fills apartic[0..ncat], hrmin / hrmax / hrexp / krdg[1..ncat] and returns aksum.  MRAFT: the optional rafting mask (:1226-1230),
+// written only where aicen > puny.  NC as in k_ice_strength.
+template <int NC, bool MRAFT, class FA, class FV>
+__device__ __forceinline__ double ridge_itd(const DevParams &p, int ncat, double a0, FA aicen, FV vicen, double *apartic, double *hrmin,
+                                            double *hrmax, double *hrexp, double *krdg, double *mraft) {
+    const double puny = 1.0e-11, c0 = 0.0, c1 = 1.0, c2 = 2.0, p5 = 0.5;
+    const double Gstar = 0.15, astar = 0.05, maxraft = 1.0, Hstar = 25.0;                                   // :72-77
+    const double Gstari = c1 / Gstar, astari = c1 / astar;
+    constexpr int NA = NC ? NC : MAXCAT;
+    double Gsum[NA + 2];
+    Gsum[0] = c0;
+    apartic[0] = c0;
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) { apartic[n] = c0; hrmin[n] = c0; hrmax[n] = c0; hrexp[n] = c0; krdg[n] = c1; }
+    Gsum[1] = (a0 > puny) ? a0 : Gsum[0];
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        const double a = aicen(n);
+        Gsum[n + 1] = (a > puny) ? Gsum[n] + a : Gsum[n];
+    }
+    const double work = c1 / Gsum[ncat + 1];
+    _Pragma("unroll")
+    for (int n = 0; n <= ncat; n++) Gsum[n + 1] = Gsum[n + 1] * work;
+    if (p.krdg_partic == 0) {
+        _Pragma("unroll")
+        for (int n = 0; n <= ncat; n++) {
+            const double g1 = Gsum[n + 1], g0 = Gsum[n];
+            if (g1 < Gstar) apartic[n] = Gstari * (g1 - g0) * (c2 - (g0 + g1) * Gstari);
+            else if (g0 < Gstar) apartic[n] = Gstari * (Gstar - g0) * (c2 - (g0 + Gstar) * Gstari);
+        }
+    } else {
+        const double xtmp = c1 / (c1 - dev_exp(-astari));
+        _Pragma("unroll")
+        for (int n = -1; n <= ncat; n++) Gsum[n + 1] = dev_exp(-Gsum[n + 1] * astari) * xtmp;
+        _Pragma("unroll")
+        for (int n = 0; n <= ncat; n++) apartic[n] = Gsum[n] - Gsum[n + 1];
+    }
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        const double a = aicen(n);
+        if (a > puny) {
+            double hi = vicen(n) / a;
+            if (p.krdg_redist == 0) {
+                hrmin[n] = fmin(c2 * hi, hi + maxraft);
+                hrmax[n] = c2 * sqrt(Hstar * hi);
+                hrmax[n] = fmax(hrmax[n], hrmin[n] + puny);
+                const double hrmean = p5 * (hrmin[n] + hrmax[n]);
+                krdg[n] = hrmean / hi;
+            } else {
+                hi = fmax(hi, puny);
+                hrmin[n] = fmin(c2 * hi, hi + maxraft);
+                hrexp[n] = p.mu_rdg * sqrt(hi);
+                krdg[n] = (hrmin[n] + hrexp[n]) / hi;
+                if (MRAFT) {                                                                                // :1226-1230
+                    double m = fmax(c0, copysign(c1, hi + maxraft - hrmin[n]));
+                    const double xt = m * ((c2 * hi + hrexp[n]) / hi - krdg[n]);
+                    m = fmax(c0, copysign(c1, puny - fabs(xt)));
+                    mraft[n] = m;
+                }
+            }
+        }
+    }
+    double aksum = apartic[0];
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) aksum = aksum + apartic[n] * (c1 - c1 / krdg[n]);
+    return aksum;
+}
+
+// compute_tracers (ice_itd.F90:1407-1499) for one tracer of one cell, shared by k_upw_scatter and the ridging kernels: rule 0 Tsfc, 1 area,
+// 2 ice volume, 3 snow volume, 4 d = p1 * aicen, 5 d = p1 * p2 * aicen, 6 d = p1 * vicen (p1, p2: the NEW values of the tracers it hangs on),
+// anything else: 0 (trcrn(:,:,:) = c0, :1401)
+__device__ __forceinline__ double compute_tracer(int rule, double at, double a, double v, double sn, double p1, double p2, bool is_fbri, double Tocnfrz) {
+    const double puny = 1.0e-11;
+    switch (rule) {
+    case 0: return a > puny ? at / a : Tocnfrz;
+    case 1: return a > puny ? at / a : 0.0;
+    case 2: return v > 0.0 ? at / v : (is_fbri ? 1.0 : 0.0);
+    case 3: return sn > 0.0 ? at / sn : 0.0;
+    case 4: { const double dd = p1 * a; return dd > 0.0 ? at / dd : 0.0; }
+    case 5: { const double dd = p1 * p2 * a; return dd > 0.0 ? at / dd : 0.0; }
+    case 6: { const double dd = p1 * v; return dd > 0.0 ? at / dd : 0.0; }
+    default: return 0.0;
+    }
+}
+
 // itd: planes [0..ncat) aicen, [ncat..2 ncat) vicen, [2 ncat] aice0, each mask_elems(s) doubles, index mcell()
 // NC > 0: the number of thickness categories at compile time (NC = 5: the reference's default, ice_domain_size) -- the per-category work
 // arrays then live in registers; NC = 0: any ncat <= MAXCAT, the arrays in scratch memory (864 bytes per lane)
@@ -466,8 +552,8 @@ __global__ void k_ice_strength(Slab s, DevParams p, const double *itd) {
     TILE_SKIP(s.act_any)
     SLAB_IJ_ALL
     const double puny = 1.0e-11, c0 = 0.0, c1 = 1.0, c2 = 2.0, p5 = 0.5, p333 = 1.0 / 3.0;
-    const double Gstar = 0.15, astar = 0.05, maxraft = 1.0, Hstar = 25.0, Pstar = 2.75e4, Cstar = 20.0;     // :72-82
-    double str = c0;                                                                                        // :2183
+    const double Pstar = 2.75e4, Cstar = 20.0;                                                              // :80-82
+    double str = c0;                                                                                       // :2183
     if (p.kstrength != 1) {                                                                                 // :2258-2265
         if (i >= 1 && i <= s.nxl && j >= 1 && j <= s.nyl)
             str = Pstar * FD(s, F_VICE, k) * dev_exp(-Cstar * (c1 - FD(s, F_AICE, k)));
@@ -475,59 +561,12 @@ __global__ void k_ice_strength(Slab s, DevParams p, const double *itd) {
         const size_t np = mask_elems(s);
         const int ncat = NC ? NC : p.ncat;
         const double Cp = p5 * p.gravit * (p.rhow - p.rhoi) * p.rhoi / p.rhow;                              // :68
-        const double Gstari = c1 / Gstar, astari = c1 / astar;
         constexpr int NA = NC ? NC : MAXCAT;
-        double Gsum[NA + 2], apartic[NA + 1], hrmin[NA + 1], hrmax[NA + 1], hrexp[NA + 1], krdg[NA + 1];
+        double apartic[NA + 1], hrmin[NA + 1], hrmax[NA + 1], hrexp[NA + 1], krdg[NA + 1];
         const double a0 = itd[(size_t)(2 * ncat) * np + km];
-        Gsum[0] = c0;
-        apartic[0] = c0;
-        _Pragma("unroll")
-        for (int n = 1; n <= ncat; n++) { apartic[n] = c0; hrmin[n] = c0; hrmax[n] = c0; hrexp[n] = c0; krdg[n] = c1; }
-        Gsum[1] = (a0 > puny) ? a0 : Gsum[0];
-        _Pragma("unroll")
-        for (int n = 1; n <= ncat; n++) {
-            const double a = itd[(size_t)(n - 1) * np + km];
-            Gsum[n + 1] = (a > puny) ? Gsum[n] + a : Gsum[n];
-        }
-        const double work = c1 / Gsum[ncat + 1];
-        _Pragma("unroll")
-        for (int n = 0; n <= ncat; n++) Gsum[n + 1] = Gsum[n + 1] * work;
-        if (p.krdg_partic == 0) {
-            _Pragma("unroll")
-            for (int n = 0; n <= ncat; n++) {
-                const double g1 = Gsum[n + 1], g0 = Gsum[n];
-                if (g1 < Gstar) apartic[n] = Gstari * (g1 - g0) * (c2 - (g0 + g1) * Gstari);
-                else if (g0 < Gstar) apartic[n] = Gstari * (Gstar - g0) * (c2 - (g0 + Gstar) * Gstari);
-            }
-        } else {
-            const double xtmp = c1 / (c1 - dev_exp(-astari));
-            _Pragma("unroll")
-            for (int n = -1; n <= ncat; n++) Gsum[n + 1] = dev_exp(-Gsum[n + 1] * astari) * xtmp;
-            _Pragma("unroll")
-            for (int n = 0; n <= ncat; n++) apartic[n] = Gsum[n] - Gsum[n + 1];
-        }
-        _Pragma("unroll")
-        for (int n = 1; n <= ncat; n++) {
-            const double a = itd[(size_t)(n - 1) * np + km];
-            if (a > puny) {
-                double hi = itd[(size_t)(ncat + n - 1) * np + km] / a;
-                if (p.krdg_redist == 0) {
-                    hrmin[n] = fmin(c2 * hi, hi + maxraft);
-                    hrmax[n] = c2 * sqrt(Hstar * hi);
-                    hrmax[n] = fmax(hrmax[n], hrmin[n] + puny);
-                    const double hrmean = p5 * (hrmin[n] + hrmax[n]);
-                    krdg[n] = hrmean / hi;
-                } else {
-                    hi = fmax(hi, puny);
-                    hrmin[n] = fmin(c2 * hi, hi + maxraft);
-                    hrexp[n] = p.mu_rdg * sqrt(hi);
-                    krdg[n] = (hrmin[n] + hrexp[n]) / hi;
-                }
-            }
-        }
-        double aksum = apartic[0];
-        _Pragma("unroll")
-        for (int n = 1; n <= ncat; n++) aksum = aksum + apartic[n] * (c1 - c1 / krdg[n]);
+        const double aksum = ridge_itd<NC, false>(p, ncat, a0, [&](int n) { return itd[(size_t)(n - 1) * np + km]; },
+                                                  [&](int n) { return itd[(size_t)(ncat + n - 1) * np + km]; }, apartic, hrmin, hrmax, hrexp, krdg,
+                                                  (double *)nullptr);
         double sacc = c0;
         _Pragma("unroll")
         for (int n = 1; n <= ncat; n++) {
@@ -2662,21 +2701,11 @@ __global__ void k_upw_scatter(Slab s, const BlockDesc *bd, int nxb, int nyb, Upw
         }
     }
     u.aicen[bc] = a; u.vicen[bc] = v; u.vsnon[bc] = sn;
-    const double puny = 1.0e-11;
     for (int it = 0; it < u.ntrcr; it++) t[(size_t)it * nn] = 0.0;                   // trcrn(:,:,:) = c0 (ice_itd.F90:1405)
     for (int it = 0; it < u.ntrcr; it++) {
         const double at = atl[it];
-        double r = 0.0;
-        switch (u.rule[it]) {
-        case 0: r = a > puny ? at / a : u.Tocnfrz; break;
-        case 1: r = a > puny ? at / a : 0.0; break;
-        case 2: r = v > 0.0 ? at / v : ((it + 1 == u.nt_fbri) ? 1.0 : 0.0); break;
-        case 3: r = sn > 0.0 ? at / sn : 0.0; break;
-        case 4: { const double dd = t[(size_t)(u.d1[it] - 1) * nn] * a; r = dd > 0.0 ? at / dd : 0.0; } break;
-        case 5: { const double dd = t[(size_t)(u.d1[it] - 1) * nn] * t[(size_t)(u.d2[it] - 1) * nn] * a; r = dd > 0.0 ? at / dd : 0.0; } break;
-        case 6: { const double dd = t[(size_t)(u.d1[it] - 1) * nn] * v; r = dd > 0.0 ? at / dd : 0.0; } break;
-        default: r = 0.0;
-        }
+        const double p1 = u.d1[it] ? t[(size_t)(u.d1[it] - 1) * nn] : 0.0, p2 = u.d2[it] ? t[(size_t)(u.d2[it] - 1) * nn] : 0.0;
+        const double r = compute_tracer(u.rule[it], at, a, v, sn, p1, p2, it + 1 == u.nt_fbri, u.Tocnfrz);
         t[(size_t)it * nn] = r;
     }
 }

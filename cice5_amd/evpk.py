@@ -95,9 +95,22 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_unpin_host", "evpk_connect", "evpk_device_check", "evpk_restart_write", "evpk_restart_read",
            "evpk_transport_upwind", "evpk_remap_init", "evpk_transport_remap", "evpk_transport_remap_state",
            "evpk_eap_init", "evpk_eap_upload", "evpk_eap_download", "evpk_halo_update", "evpk_halo_update_stress",
-           "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped"]
+           "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
+RIDGE_STOP = 13
+RIDGE_STOP_REASONS = {1: "aice0 < -puny", 2: "ardg > aicen + puny", 3: "20 ridging iterations exceeded", 4: "|asum - 1| > puny"}
+RIDGE_TRACER_FIELDS = ["nt_qsno", "nslyr", "nt_alvl", "nt_vlvl", "nt_apnd", "nt_hpnd", "nt_fbri", "tr_pond_cesm", "tr_pond_lvl", "tr_pond_topo"]
+RIDGE_DIAG_2D = ["dardg1dt", "dardg2dt", "dvirdgdt", "opening", "fpond", "fresh", "fhocn"]
+RIDGE_DIAG_3D = ["dardg1ndt", "dardg2ndt", "dvirdgndt", "aparticn", "krdgn", "araftn", "vraftn", "aredistn", "vredistn"]
+
+
+class RidgeTracers(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in RIDGE_TRACER_FIELDS]
+
+
+class RidgeDiag(ct.Structure):
+    _fields_ = [(n, c_f64p) for n in RIDGE_DIAG_2D + RIDGE_DIAG_3D]
 
 _lib = None
 
@@ -151,6 +164,8 @@ def lib():
         L.evpk_eap_init.argtypes = [ctxp, ct.c_int32, ct.c_int32, ct.c_int32] + [c_f64p] * 6
         L.evpk_eap_upload.argtypes = [ctxp, ct.POINTER(EapState)]
         L.evpk_eap_download.argtypes = [ctxp, ct.POINTER(EapState)]
+        L.evpk_ridge_ice.argtypes = ([ctxp, ct.c_double] + [ct.c_int32] * 4 + [c_i32p, ct.POINTER(RidgeTracers)] + [c_f64p] * 8 +
+                                     [ct.POINTER(RidgeDiag), c_i32p])
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -413,6 +428,33 @@ class Context:
         if rc not in (0, REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS):
             self._chk(rc, "evpk_transport_remap_state")
         return int(rc)
+
+    def ridge_ice(self, dt: float, ndtd: int, aice0, aicen, vicen, vsnon, trcrn, ntrcr: int, trcr_depend, tracers, hin_max,
+                  rdg_conv=None, rdg_shear=None, diag=None):
+        """evpk_ridge_ice (ridge_ice, ice_mechred.F90:101-746): aice0 (nb, ny, nx), aicen / vicen / vsnon (nb, ncat, ny, nx), trcrn
+        (nb, ncat, ntrcr_dim, ny, nx) in place on the listed cells (physical cells with tmask).  tracers: dict of RIDGE_TRACER_FIELDS
+        (absent = 0); hin_max: (ncat + 1,); rdg_conv / rdg_shear None: the planes the last evp / eap left on the device; diag: dict of
+        the arrays of RIDGE_DIAG_2D (nb, ny, nx) / RIDGE_DIAG_3D (nb, ncat, ny, nx) that are wanted, or None.
+        Returns None, or (reason, block, i, j) for the reference's l_stop cases (RIDGE_STOP_REASONS); raises on a refusal."""
+        ncat = int(aicen.shape[1])
+        dep = np.ascontiguousarray(trcr_depend, dtype=np.int32)
+        hin = np.ascontiguousarray(hin_max, dtype=np.float64)
+        assert hin.shape == (ncat + 1,)
+        rt = RidgeTracers(**{k: int(tracers.get(k, 0)) for k in RIDGE_TRACER_FIELDS})
+        rd = None
+        if diag is not None:
+            rd = RidgeDiag()
+            for k in RIDGE_DIAG_2D + RIDGE_DIAG_3D:
+                setattr(rd, k, _p64(diag.get(k)))
+        stop = np.zeros(4, dtype=np.int32)
+        ntrcr_dim = int(trcrn.shape[2]) if trcrn is not None else 0
+        rc = self._L.evpk_ridge_ice(self._ctx, float(dt), int(ndtd), ncat, int(ntrcr), ntrcr_dim, _p32(dep) if ntrcr else None, ct.byref(rt),
+                                    _p64(hin), _p64(rdg_conv), _p64(rdg_shear), _p64(aice0), _p64(aicen), _p64(vicen), _p64(vsnon),
+                                    _p64(trcrn), ct.byref(rd) if rd is not None else None, _p32(stop))
+        if rc == RIDGE_STOP:
+            return tuple(int(v) for v in stop)
+        self._chk(rc, "evpk_ridge_ice")
+        return None
 
     def eap_init(self, tables):
         """evpk_eap_init: the six lookup tables of init_eap, each [na_yield][ny_yield][nx_yield]; the context then runs eap(dt)"""

@@ -98,6 +98,19 @@
          type (c_ptr) :: s11 = c_null_ptr, s12 = c_null_ptr, s22 = c_null_ptr
       end type evpk_eap_state
 
+      ! evpk_ridge_tracers, evpk_ridge_diag (include/evpk.h): the ice_state tracer indices ridge_shift reads (1-based, 0 = not in
+      ! use) and the optional history / flux arrays of ridge_ice (ice_mechred.F90:164-189)
+      type, bind(C) :: evpk_ridge_tracers
+         integer (c_int32_t) :: nt_qsno = 0, nslyr = 0, nt_alvl = 0, nt_vlvl = 0, nt_apnd = 0, nt_hpnd = 0, nt_fbri = 0
+         integer (c_int32_t) :: tr_pond_cesm = 0, tr_pond_lvl = 0, tr_pond_topo = 0
+      end type evpk_ridge_tracers
+      type, bind(C) :: evpk_ridge_diag
+         type (c_ptr) :: dardg1dt = c_null_ptr, dardg2dt = c_null_ptr, dvirdgdt = c_null_ptr, opening = c_null_ptr
+         type (c_ptr) :: fpond = c_null_ptr, fresh = c_null_ptr, fhocn = c_null_ptr
+         type (c_ptr) :: dardg1ndt = c_null_ptr, dardg2ndt = c_null_ptr, dvirdgndt = c_null_ptr, aparticn = c_null_ptr
+         type (c_ptr) :: krdgn = c_null_ptr, araftn = c_null_ptr, vraftn = c_null_ptr, aredistn = c_null_ptr, vredistn = c_null_ptr
+      end type evpk_ridge_diag
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -106,9 +119,11 @@
                 evpk_halo_update, evpk_halo_update_stress, evpk_transport_upwind_state, &
                 evpk_transport_upwind, evpk_remap_init, evpk_transport_remap, evpk_transport_remap_state, &
                 EVPK_REMAP_BAD_DEPARTURE, EVPK_REMAP_NEGATIVE_MASS, &
-                evpk_eap_state, evpk_eap_init, evpk_eap_upload, evpk_eap_download
+                evpk_eap_state, evpk_eap_init, evpk_eap_upload, evpk_eap_download, &
+                evpk_ridge_tracers, evpk_ridge_diag, evpk_ridge_ice, EVPK_RIDGE_STOP
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
+      integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
 
       interface
          integer (c_int) function evpk_get_unique_id (id) bind(C, name='evpk_get_unique_id')
@@ -243,6 +258,17 @@
             type (c_ptr), value :: ctx, trcr_depend, aice0, aicen, vicen, vsnon, trcrn
             real (c_double), value :: dt, Tocnfrz
             integer (c_int32_t), value :: ncat, ntrcr, ntrcr_dim, nt_Tsfc, nt_alvl, nt_apnd, nt_fbri, tr_pond_cesm, tr_pond_lvl, tr_pond_topo
+         end function
+         ! ridge_ice (ice_mechred.F90:101-746) for every block: the call of step_ridge (ice_step_mod.F90:1285-1305).  rdg_conv,
+         ! rdg_shear = c_null_ptr: the planes the last evp / eap left on the device; stop(4): reason, block, i, j
+         integer (c_int) function evpk_ridge_ice (ctx, dt, ndtd, ncat, ntrcr, ntrcr_dim, trcr_depend, t, hin_max, rdg_conv, rdg_shear, &
+               aice0, aicen, vicen, vsnon, trcrn, diag, stop) bind(C, name='evpk_ridge_ice')
+            import :: c_int, c_ptr, c_double, c_int32_t, evpk_ridge_tracers
+            type (c_ptr), value :: ctx, trcr_depend, hin_max, rdg_conv, rdg_shear, aice0, aicen, vicen, vsnon, trcrn, diag
+            real (c_double), value :: dt
+            integer (c_int32_t), value :: ndtd, ncat, ntrcr, ntrcr_dim
+            type (evpk_ridge_tracers), intent(in) :: t
+            integer (c_int32_t), intent(out) :: stop(4)
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then
          ! mm(nx_block,ny_block,0:ncat,max_blocks), tm(nx_block,ny_block,ntrace,ncat,max_blocks) advanced in place

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define EVPK_VERSION 5
+#define EVPK_VERSION 6
 
 /* boundary types: ice_domain.F90 domain_nml ew_boundary_type / ns_boundary_type */
 enum { EVPK_BND_CYCLIC = 0, EVPK_BND_OPEN = 1, EVPK_BND_CLOSED = 2, EVPK_BND_TRIPOLE = 3 };
@@ -303,6 +303,46 @@ int evpk_transport_remap_state(evpk_ctx *c, double dt, int32_t ncat, int32_t ntr
                                double rhos_lfresh, double *aice0, double *aicen, double *vicen, double *vsnon, double *trcrn,
                                const int32_t *tracer_type, const int32_t *depend, const int32_t *has_dependents,
                                int32_t integral_order, int32_t l_dp_midpt);
+
+/* ridge_ice (source/ice_mechred.F90:101-746), the call of step_ridge (ice_step_mod.F90:1285-1305), on the device:
+ * asum_ridging, ridge_prep, ridge_itd, ridge_shift with compute_tracers, ridge_check and the diagnostics, for every block of the
+ * context.  cleanup_itd and aggregate, the rest of step_ridge / step_dynamics, stay with the host.
+ *   dt, ndtd                         the dynamics time step and the number of dynamics subcycles (fresh / fhocn average over ndtd * dt)
+ *   ncat, ntrcr, ntrcr_dim, trcr_depend, aice0, aicen, vicen, vsnon, trcrn    as for evpk_transport_upwind_state (host arrays, page-locked
+ *                                    arrays or device pointers)
+ *   t                                the ice_state tracer indices ridge_shift reads, 1-based, 0 = not in use; nslyr snow layers from nt_qsno
+ *   hin_max(0:ncat)                  the category boundaries (ice_itd); hin_max(ncat) is taken as 1e8 inside the call, as ridge_prep sets it
+ *                                    (:864) -- the caller's array is not written
+ *   rdg_conv, rdg_shear              block arrays, or both NULL: the planes the last evp / eap left on the device
+ *   diag                             may be NULL, and so may every member; out members are written on listed cells only
+ * The cell list is step_ridge's: physical cells with tmask, block by block.  Listed cells are rewritten; ghost cells and unlisted cells
+ * keep the caller's values (the reference zeroes trcrn of a whole category slice inside compute_tracers, ice_itd.F90:1401, and calls
+ * bound_state afterwards).  krdg_partic, krdg_redist, mu_rdg, rhos come from evpk_params; fsnowrdg, Cs, Gstar, astar, maxraft are the
+ * module parameters (:66-83).  Iteration is per block, as ridge_check's flag is per ridge_ice call: while one cell of a block has
+ * |asum - 1| >= puny every listed cell of the block ridges again.  compute_tracers runs without nt_Tsfc: a surface temperature is an
+ * ordinary area tracer here and is 0, not Tocnfrz, in a category left with aicen <= puny (cleanup_itd's zap_small_areas resets it).
+ * exp() is the fixed algorithm of ice_strength on the device.
+ * Returns 0; EVPK_RIDGE_STOP with stop[] = {reason, block (1-based), i, j} for the reference's l_stop cases -- 1: aice0 < -puny (:1583),
+ * 2: ardg > aicen + puny (:1656), 3: 20 iterations exceeded (:453; i = j = 0), 4: |asum - 1| > puny at the end (:729) -- the failing cell
+ * that comes first in (block, j, i) order at the earliest iteration; the state arrays are then undefined (the reference aborts); or 1
+ * with evpk_last_error: krdg_redist == 0 (ridge_shift reads hrmax with the index of the compressed list of ridging cells, :1724-1725,
+ * :1860-1866, so the reference's result depends on which other cells of the block ridge), aerosol tracers (none can be passed),
+ * nranks > 1 (follow-up), ntrcr > 32, ncat > 16. */
+typedef struct {            /* 1-based tracer indices of ice_state, 0 = not in use */
+    int32_t nt_qsno, nslyr, nt_alvl, nt_vlvl, nt_apnd, nt_hpnd, nt_fbri;
+    int32_t tr_pond_cesm, tr_pond_lvl, tr_pond_topo;
+} evpk_ridge_tracers;
+typedef struct {            /* every member may be NULL */
+    double *dardg1dt, *dardg2dt, *dvirdgdt, *opening;       /* out, (nx_block,ny_block,nblocks), listed cells only */
+    double *fpond, *fresh, *fhocn;                          /* in/out: incremented as :693-720 */
+    double *dardg1ndt, *dardg2ndt, *dvirdgndt, *aparticn, *krdgn, *araftn, *vraftn, *aredistn, *vredistn; /* (nx_block,ny_block,ncat,nblocks) */
+} evpk_ridge_diag;
+#define EVPK_RIDGE_STOP 13
+int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim,
+                   const int32_t *trcr_depend, const evpk_ridge_tracers *t, const double *hin_max /* 0:ncat */,
+                   const double *rdg_conv, const double *rdg_shear,   /* NULL: the planes the last evp / eap left on the device */
+                   double *aice0, double *aicen, double *vicen, double *vsnon, double *trcrn,
+                   evpk_ridge_diag *diag, int32_t stop[4] /* out: reason, block, i, j */);
 
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared
