@@ -20,6 +20,15 @@ eyc = 0.36
 a_min = 0.001
 m_min = 0.01
 
+# cleanup_itd (source/ice_itd.F90:1514-1769): drivers/auscom/ice_constants.F90:28,61-68,91,103 and source/ice_therm_shared.F90:35
+# (Tocnfrz is a namelist variable under AusCOM; -1.8 is the non-AusCOM parameter value)
+Tocnfrz = -1.8
+ice_ref_salinity = 5.0
+hs_min = 1.0e-4
+cp_ice = 2106.0
+Lfresh = 2.835e6 - 2.501e6          # Lsub - Lvap
+Tmin = -100.0
+
 # Hibler (1979) strength, source/ice_mechred.F90:80-82
 Pstar = 2.75e4
 Cstar = 20.0

@@ -32,6 +32,7 @@
 #include "evpk_kernels.hip"
 #include "evpk_remap.hip"
 #include "evpk_ridge.hip"
+#include "evpk_itd.hip"
 #include "evpk_eap.hip"
 
 using namespace evpk;
@@ -342,6 +343,9 @@ struct evpk_ctx {
     int *rg_flags = nullptr;
     RidgeCtl *rg_ctl = nullptr;
     size_t rg_pool_n = 0, rg_stage_n = 0, rg_mask_n = 0, rg_flags_n = 0;
+    // evpk_cleanup_itd: the per-block masks of the boundaries at which a block shifts, the stop key
+    unsigned *itd_bmask = nullptr; size_t itd_bmask_n = 0;
+    unsigned long long *itd_key = nullptr;
     // EAP (kdyn = 2): set by evpk_eap_init -- the subcycle loop then runs stress_eap / stepu / stepa (evpk_eap.hip)
     bool eap = false;
     EapDev E{};
@@ -1304,7 +1308,7 @@ static void destroy_impl(evpk_ctx *c) {
     if (c->relay) { c->relay->close_(); delete c->relay; }
     if (c->ipc) { if (c->stream2) (void)hipStreamSynchronize(c->stream2); c->ipc->close_(); delete c->ipc; }
     void *ptrs[] = {c->itd, c->stage_itd, c->d_zflags, c->d_zrows, c->s.F, c->s.tmask, c->s.umask, c->s.iceumask, c->s.cmask, c->s.tmphm, c->d_bd, c->stage, c->d_flags,
-                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_stage, c->rg_mask, c->rg_flags, c->rg_ctl, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
+                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_stage, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -3536,6 +3540,212 @@ extern "C" int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat
         if (staged[q] && arr[q].out) HIPCHK(c, hipMemcpyAsync(arr[q].host, *arr[q].slot, sizeof(double) * arr[q].n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return reason ? EVPK_RIDGE_STOP : 0;
+}
+
+// ---- cleanup_itd and aggregate (source/ice_itd.F90:1514-1769, :246-458) on the caller's state arrays: the rest of step_ridge / step_dynamics
+// (kernels in evpk_itd.hip) ----
+// the per-tracer tables of ItdArgs: how aicen * trcrn is built (shift_ice :919-975, aggregate :348-433) and compute_tracers (:1407-1499), their
+// branches in the reference's order
+static int itd_tables(evpk_ctx *c, const char *who, ItdArgs &A, int32_t ntrcr, const int32_t *trcr_depend, const evpk_itd_tracers *t) {
+    const int nts[] = {t->nt_Tsfc, t->nt_qice, t->nt_qsno, t->nt_alvl, t->nt_apnd, t->nt_hpnd, t->nt_fbri};
+    for (int q : nts) if (q < 0 || q > ntrcr) FAIL(c, "%s: tracer index %d not in 0..ntrcr = %d", who, q, ntrcr);
+    if (t->nilyr < 0 || (t->nilyr > 0 && (t->nt_qice < 1 || t->nt_qice + t->nilyr - 1 > ntrcr))) FAIL(c, "%s: nt_qice / nilyr beyond ntrcr", who);
+    if (t->nslyr < 0 || (t->nslyr > 0 && (t->nt_qsno < 1 || t->nt_qsno + t->nslyr - 1 > ntrcr))) FAIL(c, "%s: nt_qsno / nslyr beyond ntrcr", who);
+    if (t->tr_pond_topo && (t->nt_apnd < 1 || t->nt_hpnd < 1)) FAIL(c, "%s: tr_pond_topo without nt_apnd / nt_hpnd", who);
+    if (t->tr_pond_lvl && t->nt_apnd > 0 && t->nt_alvl < 1) FAIL(c, "%s: tr_pond_lvl without nt_alvl", who);
+    A.nt_Tsfc = t->nt_Tsfc; A.nt_qice = t->nt_qice; A.nilyr = t->nilyr; A.nt_qsno = t->nt_qsno; A.nslyr = t->nslyr; A.nt_alvl = t->nt_alvl;
+    A.nt_apnd = t->nt_apnd; A.nt_hpnd = t->nt_hpnd; A.nt_fbri = t->nt_fbri; A.tr_pond_topo = t->tr_pond_topo ? 1 : 0; A.tr_brine = t->tr_brine ? 1 : 0;
+    const bool pond_at = t->tr_pond_cesm || t->tr_pond_topo;
+    for (int it = 1; it <= ntrcr; it++) {
+        const int dep = trcr_depend[it - 1], k = it - 1;
+        A.acc[k] = -1; A.rule[k] = -1; A.d1[k] = 0; A.d2[k] = 0; A.slot[k] = 0;
+        if (dep == 0) { A.acc[k] = 0; A.rule[k] = 1; }
+        else if (dep == 1) { A.acc[k] = 1; A.rule[k] = 2; }
+        else if (dep == 2) { A.acc[k] = 2; A.rule[k] = 3; }
+        else if (t->nt_alvl > 0 && dep == 2 + t->nt_alvl) { A.acc[k] = 3; A.rule[k] = 4; A.d1[k] = 1; }
+        else if (t->nt_apnd > 0 && dep == 2 + t->nt_apnd && pond_at) { A.acc[k] = 4; A.rule[k] = 4; A.d1[k] = 2; }
+        else if (t->nt_apnd > 0 && dep == 2 + t->nt_apnd && t->tr_pond_lvl) { A.acc[k] = 5; A.rule[k] = 5; A.d1[k] = 1; A.d2[k] = 2; }
+        else if (t->nt_fbri > 0 && dep == 2 + t->nt_fbri) { A.acc[k] = 6; A.rule[k] = 6; A.d1[k] = 3; }
+        if (it == t->nt_Tsfc) A.rule[k] = 0;            // compute_tracers asks for nt_Tsfc first (:1408)
+        if (it == t->nt_alvl) A.slot[k] = 1;
+        else if (it == t->nt_apnd) A.slot[k] = 2;
+        else if (it == t->nt_fbri) A.slot[k] = 3;
+    }
+    return 0;
+}
+
+// the caller's arrays of one call: in place where the device sees them, else through a staging copy (up, and down again at the end)
+struct ItdArr { void *host; size_t bytes; void **slot; bool out; bool staged; };
+static int itd_stage_in(evpk_ctx *c, ItdArr *arr, int n) {
+    size_t need = 0;
+    for (int q = 0; q < n; q++) {
+        *arr[q].slot = (arr[q].host && arr[q].bytes) ? mapped_alias(arr[q].host, arr[q].bytes) : nullptr;
+        arr[q].staged = arr[q].host && arr[q].bytes && !*arr[q].slot;
+        if (arr[q].staged) need += (arr[q].bytes + 7) / 8;
+    }
+    if (c->rg_stage_n < need) {
+        if (c->rg_stage) (void)hipFree(c->rg_stage);
+        c->rg_stage = nullptr; c->rg_stage_n = 0;
+        HIPCHK(c, hipMalloc(&c->rg_stage, sizeof(double) * need));
+        c->rg_stage_n = need;
+    }
+    double *q2 = c->rg_stage;
+    for (int q = 0; q < n; q++)
+        if (arr[q].staged) {
+            HIPCHK(c, hipMemcpyAsync(q2, arr[q].host, arr[q].bytes, hipMemcpyHostToDevice, c->stream));
+            *arr[q].slot = q2; q2 += (arr[q].bytes + 7) / 8;
+        }
+    return 0;
+}
+static int itd_stage_out(evpk_ctx *c, ItdArr *arr, int n) {
+    for (int q = 0; q < n; q++)
+        if (arr[q].staged && arr[q].out) HIPCHK(c, hipMemcpyAsync(arr[q].host, *arr[q].slot, arr[q].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int evpk_cleanup_itd(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
+                                const evpk_itd_tracers *t, const double *hin_max, const evpk_itd_constants *k, int32_t tr_aero, int32_t nbtrcr,
+                                int32_t heat_capacity, double *aicen, double *vicen, double *vsnon, double *trcrn, double *aice0, double *aice,
+                                double *fpond, double *fresh, double *fsalt, double *fhocn, int32_t *first_ice, int32_t stop[4]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = 0;
+    if (c->nranks > 1) FAIL(c, "evpk_cleanup_itd: nranks = %d: more than one rank is not supported yet", c->nranks);
+    if (!t || !hin_max || !k || !aice0 || !aice || !aicen || !vicen || !vsnon || !stop || ntrcr < 0 || ntrcr_dim < ntrcr ||
+        (ntrcr > 0 && (!trcrn || !trcr_depend)))
+        FAIL(c, "evpk_cleanup_itd: a required argument is missing");
+    if (!c->connected) FAIL(c, "evpk_cleanup_itd: the context is not connected yet (evpk_connect)");
+    if (!c->have_params) FAIL(c, "evpk_cleanup_itd: evpk_set_params has not been called (rhoi, rhos)");
+    if (!(dt > 0.0)) FAIL(c, "evpk_cleanup_itd: dt = %g", dt);
+    if (ncat < 1 || ncat > MAXCAT) FAIL(c, "evpk_cleanup_itd: ncat = %d not in 1..%d", ncat, MAXCAT);
+    if (ntrcr > RG_MAXT) FAIL(c, "evpk_cleanup_itd: ntrcr = %d exceeds %d", ntrcr, RG_MAXT);
+    if (tr_aero) FAIL(c, "evpk_cleanup_itd: aerosol tracers (tr_aero) are not supported: faero_ocn cannot be passed");
+    if (nbtrcr > 0) FAIL(c, "evpk_cleanup_itd: nbtrcr = %d: bgc tracers are not supported: flux_bio cannot be passed", nbtrcr);
+    if (!heat_capacity) FAIL(c, "evpk_cleanup_itd: heat_capacity = .false. (zerolayer_check) is not supported");
+    if (k->puny != 1.0e-11) FAIL(c, "evpk_cleanup_itd: puny = %g: compute_tracers on the device is built with 1e-11", k->puny);
+    if (c->nblocks >= 65536) FAIL(c, "evpk_cleanup_itd: %d blocks exceed the stop key", c->nblocks);
+    ItdArgs A{};
+    if (itd_tables(c, "evpk_cleanup_itd", A, ntrcr, trcr_depend, t)) return 1;
+    if (ntrcr > 0 && t->nt_Tsfc < 1) FAIL(c, "evpk_cleanup_itd: nt_Tsfc is required (zap_small_areas resets it)");
+    if (!c->nblocks) return 0;
+    Slab &s = c->s;
+    HIPCHK(c, hipSetDevice(c->device));
+    A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
+    A.dt = dt; A.Tocnfrz = k->Tocnfrz; A.salinity = k->ice_ref_salinity; A.hs_min = k->hs_min; A.cp_ice = k->cp_ice; A.Lfresh = k->Lfresh;
+    A.Tmin = k->Tmin; A.puny = k->puny; A.rhoi = c->p.rhoi; A.rhos = c->p.rhos;
+    for (int n = 0; n <= ncat; n++) A.hin_max[n] = hin_max[n];
+    const size_t nblk = (size_t)c->nyb * c->nxb, nb = (size_t)c->nblocks, N = nb * nblk, d8 = sizeof(double);
+    ItdArr arr[] = {
+        {aicen, N * ncat * d8, (void **)&A.aicen, true}, {vicen, N * ncat * d8, (void **)&A.vicen, true}, {vsnon, N * ncat * d8, (void **)&A.vsnon, true},
+        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim * d8, (void **)&A.trcrn, true}, {aice0, N * d8, (void **)&A.aice0, true},
+        {aice, N * d8, (void **)&A.aice, true}, {fpond, N * d8, (void **)&A.fpond, true}, {fresh, N * d8, (void **)&A.fresh, true},
+        {fsalt, N * d8, (void **)&A.fsalt, true}, {fhocn, N * d8, (void **)&A.fhocn, true},
+        {first_ice, N * ncat * sizeof(int32_t), (void **)&A.first_ice, true}};
+    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
+    if (itd_stage_in(c, arr, NARR)) return 1;
+    if (c->itd_bmask_n < nb) {
+        if (c->itd_bmask) (void)hipFree(c->itd_bmask);
+        c->itd_bmask = nullptr; c->itd_bmask_n = 0;
+        HIPCHK(c, hipMalloc(&c->itd_bmask, sizeof(unsigned) * nb));
+        c->itd_bmask_n = nb;
+    }
+    if (!c->itd_key) HIPCHK(c, hipMalloc(&c->itd_key, sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->itd_bmask, 0, sizeof(unsigned) * nb, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->itd_key, 0xff, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
+    if (ncat == 5) {
+        hipLaunchKernelGGL(k_itd_scan<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, c->itd_bmask, c->itd_key);
+        hipLaunchKernelGGL(k_itd_shift<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask);
+        hipLaunchKernelGGL(k_itd_zap<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask, c->itd_key);
+    } else {
+        hipLaunchKernelGGL(k_itd_scan<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, c->itd_bmask, c->itd_key);
+        hipLaunchKernelGGL(k_itd_shift<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask);
+        hipLaunchKernelGGL(k_itd_zap<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask, c->itd_key);
+    }
+    HIPCHK(c, hipGetLastError());
+    unsigned long long key = ~0ull;
+    HIPCHK(c, hipMemcpyAsync(&key, c->itd_key, sizeof(key), hipMemcpyDeviceToHost, c->stream));
+    if (itd_stage_out(c, arr, NARR)) return 1;
+    if (key == ~0ull) return 0;
+    const int stage = (int)((key >> 40) & 0xff), sub = (int)((key >> 32) & 0xff);
+    const unsigned code = (unsigned)(key & 0xffffffffull);
+    const bool rebin = stage >= 1 && stage < 2 * ncat;
+    const size_t o = (stage == 0 || rebin) ? (size_t)(0xffffffffu - code) : (size_t)code;
+    stop[0] = stage == 0 ? ITD_STOP_BOUNDS : rebin ? ITD_STOP_NEG_DAICE + sub : stage == 2 * ncat ? ITD_STOP_NEG_AICEN : ITD_STOP_EXCESS;
+    stop[1] = (int32_t)(key >> 48) + 1; stop[2] = (int32_t)(o % c->nxb) + 1; stop[3] = (int32_t)(o / c->nxb) + 1;
+    return EVPK_ITD_STOP;
+}
+
+// bound_state (ice_state.F90:173-238): ice_HaloUpdate, centre scalar, of aicen, trcrn(1:ntrcr), vicen, vsnon on the device -- the planes go
+// through the scratch state planes and the general update, as evpk_halo_update's do (fill 0 next to an eliminated land block)
+static int itd_bound_state(evpk_ctx *c, const ItdArgs &A) {
+    Slab &s = c->s;
+    const size_t nn = (size_t)c->nyb * c->nxb;
+    struct Pl { double *p; size_t bstride; };
+    std::vector<Pl> pl;
+    for (int n = 0; n < A.ncat; n++) pl.push_back({A.aicen + (size_t)n * nn, (size_t)A.ncat * nn});
+    for (int n = 0; n < A.ncat; n++)
+        for (int it = 0; it < A.ntrcr; it++) pl.push_back({A.trcrn + ((size_t)n * A.ntrcr_dim + it) * nn, (size_t)A.ncat * A.ntrcr_dim * nn});
+    for (int n = 0; n < A.ncat; n++) pl.push_back({A.vicen + (size_t)n * nn, (size_t)A.ncat * nn});
+    for (int n = 0; n < A.ncat; n++) pl.push_back({A.vsnon + (size_t)n * nn, (size_t)A.ncat * nn});
+    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
+    const int chunk = std::min(c->max_nf, (int)NSTATE), np = (int)pl.size();
+    for (int k0 = 0; k0 < np; k0 += chunk) {
+        const int nf = std::min(chunk, np - k0);
+        for (int q = 0; q < nf; q++) {
+            if (!c->full_cover) hipLaunchKernelGGL(k_fill_plane, grid2d(s, B2D), B2D, 0, c->stream, s, (int)F_STATE2 + q, 0.0);
+            LAUNCH_BLOCKS(k_gather_fs, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)pl[k0 + q].p, pl[k0 + q].bstride, (int)F_STATE2 + q);
+        }
+        if (halo(c, F_STATE2, nf, false, false, 0.0)) return 1;
+        for (int q = 0; q < nf; q++)
+            LAUNCH_BLOCKS(k_scatter_halo, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (int)F_STATE2 + q, pl[k0 + q].p, pl[k0 + q].bstride, 0.0,
+                          c->ew == EVPK_BND_CYCLIC ? 1 : 0, c->ns == EVPK_BND_TRIPOLE ? 1 : 0, 0, 0, -1);
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
+                              const evpk_itd_tracers *t, int32_t nt_iage, double Tocnfrz, double *aicen, double *vicen, double *vsnon, double *trcrn,
+                              double *aice, double *vice, double *vsno, double *aice0, double *trcr, double *daidtd, double *dvidtd,
+                              double *dagedtd) {
+    if (!c) return 1;
+    if (c->nranks > 1) FAIL(c, "evpk_aggregate: nranks = %d: more than one rank is not supported yet", c->nranks);
+    if (!t || !aice0 || !aice || !vice || !vsno || !aicen || !vicen || !vsnon || ntrcr < 0 || ntrcr_dim < ntrcr ||
+        (ntrcr > 0 && (!trcrn || !trcr_depend || !trcr)))
+        FAIL(c, "evpk_aggregate: a required argument is missing");
+    if (!c->connected) FAIL(c, "evpk_aggregate: the context is not connected yet (evpk_connect)");
+    if (!(dt > 0.0)) FAIL(c, "evpk_aggregate: dt = %g", dt);
+    if (bound != 0 && bound != 1) FAIL(c, "evpk_aggregate: bound = %d", bound);
+    if (ncat < 1 || ncat > MAXCAT) FAIL(c, "evpk_aggregate: ncat = %d not in 1..%d", ncat, MAXCAT);
+    if (ntrcr > RG_MAXT) FAIL(c, "evpk_aggregate: ntrcr = %d exceeds %d", ntrcr, RG_MAXT);
+    if (nt_iage < 0 || nt_iage > ntrcr) FAIL(c, "evpk_aggregate: nt_iage = %d not in 0..ntrcr = %d", nt_iage, ntrcr);
+    ItdArgs A{};
+    if (itd_tables(c, "evpk_aggregate", A, ntrcr, trcr_depend, t)) return 1;
+    if (!c->nblocks) return 0;
+    Slab &s = c->s;
+    HIPCHK(c, hipSetDevice(c->device));
+    A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nt_iage = nt_iage;
+    A.dt = dt; A.Tocnfrz = Tocnfrz; A.puny = 1.0e-11;
+    const size_t nblk = (size_t)c->nyb * c->nxb, nb = (size_t)c->nblocks, N = nb * nblk, d8 = sizeof(double);
+    const bool bnd = bound != 0;
+    ItdArr arr[] = {
+        {aicen, N * ncat * d8, (void **)&A.aicen, bnd}, {vicen, N * ncat * d8, (void **)&A.vicen, bnd}, {vsnon, N * ncat * d8, (void **)&A.vsnon, bnd},
+        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim * d8, (void **)&A.trcrn, bnd}, {aice0, N * d8, (void **)&A.aice0, true},
+        {aice, N * d8, (void **)&A.aice, true}, {vice, N * d8, (void **)&A.vice, true}, {vsno, N * d8, (void **)&A.vsno, true},
+        {ntrcr ? trcr : nullptr, N * ntrcr_dim * d8, (void **)&A.trcr, true}, {daidtd, N * d8, (void **)&A.daidtd, true},
+        {dvidtd, N * d8, (void **)&A.dvidtd, true}, {dagedtd, N * d8, (void **)&A.dagedtd, true}};
+    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
+    if (itd_stage_in(c, arr, NARR)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    if (bnd && itd_bound_state(c, A)) return 1;
+    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
+    if (ncat == 5) hipLaunchKernelGGL(k_itd_aggregate<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
+    else hipLaunchKernelGGL(k_itd_aggregate<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
+    HIPCHK(c, hipGetLastError());
+    if (itd_stage_out(c, arr, NARR)) return 1;
+    return xp_check(c);
 }
 
 // ---- transport_remap's horizontal_remap (source/ice_transport_remap.F90:309-850) on the resident velocities ----

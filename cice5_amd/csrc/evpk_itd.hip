@@ -1,0 +1,474 @@
+// evpk_itd.hip -- cleanup_itd (source/ice_itd.F90:1514-1769: aggregate_area, the area check, rebin with shift_ice and compute_tracers,
+// zap_small_areas I / II with zap_snow, zap_snow_temperature, the flux increments) and aggregate (:246-458) with the tendency lines of
+// step_dynamics (ice_step_mod.F90:1183-1189) on the device, on the caller's block arrays as they are.  Included by evpk_api.hip (one
+// translation unit).
+//
+// One thread per cell of the block arrays.  rebin's shiftflag is one flag per BLOCK and per category boundary -- 2 (ncat - 1) boundaries,
+// first upward, then downward: when any listed cell of a block (physical, aice > puny) shifts at a boundary, shift_ice runs for every
+// listed cell of the block, which rewrites all its tracers as (aicen * trcrn) / aicen and resets categories with aicen <= puny, and
+// compute_tracers zeroes the tracers of every other cell of the block (:1401).  A cell's own donor decisions depend on its own aicen /
+// vicen / hicen only, and a pass of shift_ice in which it is no donor leaves those unchanged (hicen is recomputed from the same operands;
+// the one exception, hicen(1) = hin_max(0) after the category-1 adjustment, is read at the very first boundary only).  Hence three kernels:
+//   k_itd_scan   every cell: aggregate_area (aice, aice0); listed cells with tmask: the area check and a replay of rebin's area / volume part,
+//                which ORs the boundaries at which the cell shifts into bmask[block] and records the reference's l_stop cases
+//   k_itd_shift  physical ocean cells of the blocks with bmask != 0 (the others leave at once): the boundaries of bmask[block] with the
+//                tracers -- the kernel that needs the registers (old and new state, parents, one tracer of every category)
+//   k_itd_zap    physical ocean cells: zap I / II, the snow-temperature zap and the flux increments on the state rebin left; a cell that
+//                zaps nothing writes nothing -- the common case reads aicen, vicen, vsnon, aice, aice0 and the snow enthalpies
+// A stop is one 64-bit key, the smallest wins: block | stage (0 the area check, 1 + q boundary q in rebin's order, then zap I, zap II) |
+// sub (shift_ice's four checks in their order; zap I: the category) | cell -- where the reference's loop does not exit (:1648-1655,
+// :1040-1126) the cell field counts down so that the LAST failing cell wins, in zap_small_areas (which returns) it counts up.
+// Same operation order as the Fortran, -ffp-contract=off: bit-comparable with the reference (tests/golden/ref_itd_*.npz).
+#pragma once
+
+namespace evpk {
+
+enum { ITD_STOP_BOUNDS = 1, ITD_STOP_NEG_DAICE = 2, ITD_STOP_NEG_DVICE = 3, ITD_STOP_DAICE = 4, ITD_STOP_DVICE = 5, ITD_STOP_NEG_AICEN = 6,
+       ITD_STOP_EXCESS = 7 };
+
+struct ItdArgs {
+    double *aicen, *vicen, *vsnon, *trcrn, *aice0, *aice;       // (nb, ncat, ny, nx) x 3, (nb, ncat, ntrcr_dim, ny, nx), (nb, ny, nx) x 2
+    double *fpond, *fresh, *fsalt, *fhocn;                      // (nb, ny, nx) or nullptr
+    int32_t *first_ice;                                         // (nb, ncat, ny, nx) or nullptr
+    // aggregate only
+    double *vice, *vsno, *trcr, *daidtd, *dvidtd, *dagedtd;
+    int ncat, ntrcr, ntrcr_dim, nxb, nyb;
+    int nt_Tsfc, nt_qice, nilyr, nt_qsno, nslyr, nt_alvl, nt_apnd, nt_hpnd, nt_fbri, nt_iage, tr_pond_topo, tr_brine;
+    double dt, Tocnfrz, salinity, hs_min, cp_ice, Lfresh, Tmin, puny, rhoi, rhos;
+    double hin_max[MAXCAT + 1];
+    // per tracer (0-based), as RidgeArgs: acc how aicen * trcrn is built (0 area, 1 ice volume, 2 snow volume, 3 aicen * alvl, 4 aicen * apnd,
+    // 5 aicen * alvl * apnd, 6 vicen * fbri, -1 no rule); rule, d1, d2: compute_tracer's rule (0: nt_Tsfc) and the parent slots + 1 (slot 0
+    // alvl, 1 apnd, 2 fbri); slot: the slot this tracer fills + 1
+    signed char acc[RG_MAXT], rule[RG_MAXT], d1[RG_MAXT], d2[RG_MAXT], slot[RG_MAXT];
+};
+
+__device__ __forceinline__ unsigned long long itd_key(int b, int stage, int sub, unsigned cellcode) {
+    return ((unsigned long long)b << 48) | ((unsigned long long)stage << 40) | ((unsigned long long)sub << 32) | (unsigned long long)cellcode;
+}
+
+// boundary q of rebin's sequence (0 .. 2 (ncat - 1) - 1): the Fortran boundary n, the donor and the receiver category (1-based)
+__device__ __forceinline__ void itd_boundary(int ncat, int q, bool &up, int &n, int &nd, int &nr) {
+    up = q < ncat - 1;
+    n = up ? q + 1 : 2 * (ncat - 1) - q;
+    nd = up ? n : n + 1;
+    nr = up ? n + 1 : n;
+}
+
+// shift_ice's range checks of one donor cell (:994-1033): may reset daice / dvice; returns -1 or the first failing check 0 .. 3 in the order
+// of the error loops (:1040-1126)
+__device__ __forceinline__ int itd_check(double &daice, double &dvice, double a, double v, double puny) {
+    const double c0 = 0.0, c1 = 1.0;
+    bool na = false, nv = false, ga = false, gv = false;
+    if (daice < c0) { if (daice > -puny * a) { daice = c0; dvice = c0; } else na = true; }
+    if (dvice < c0) { if (dvice > -puny * v) { daice = c0; dvice = c0; } else nv = true; }
+    if (daice > a * (c1 - puny)) { if (daice < a * (c1 + puny)) { daice = a; dvice = v; } else ga = true; }
+    if (dvice > v * (c1 - puny)) { if (dvice < v * (c1 + puny)) { daice = a; dvice = v; } else gv = true; }
+    return na ? 0 : nv ? 1 : ga ? 2 : gv ? 3 : -1;
+}
+
+__device__ __forceinline__ bool itd_ocean(const Slab &s, const BlockDesc &d, int i, int j) {
+    int si, sj;
+    return ridge_listed(s, d, i, j, si, sj);
+}
+
+template <int NC>
+__global__ void __launch_bounds__(64) k_itd_scan(Slab s, const BlockDesc *bd, ItdArgs A, unsigned *bmask, unsigned long long *key) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    const int j = blockIdx.y + 1;
+    const int b = blockIdx.z;
+    if (i > A.nxb) return;
+    const double puny = A.puny, c0 = 0.0, c1 = 1.0;
+    const int ncat = NC ? NC : A.ncat;
+    constexpr int NA = NC ? NC : MAXCAT;
+    const size_t nn = (size_t)A.nyb * A.nxb, o = (size_t)(j - 1) * A.nxb + (i - 1), ci = (size_t)b * nn + o;
+    double a[NA + 2], v[NA + 2], h[NA + 2];
+    double aice = c0;                                                                                       // aggregate_area (:489-506)
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        const size_t bc = ((size_t)b * ncat + (n - 1)) * nn + o;
+        a[n] = A.aicen[bc];
+        aice = aice + a[n];
+    }
+    A.aice[ci] = aice;
+    A.aice0[ci] = fmax(c1 - aice, c0);
+    if (!itd_ocean(s, bd[b], i, j)) return;
+    if (aice > c1 + puny || aice < -puny) { atomicMin(key, itd_key(b, 0, 0, 0xffffffffu - (unsigned)o)); return; }      // :1650
+    if (!(aice > puny)) return;
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        v[n] = A.vicen[((size_t)b * ncat + (n - 1)) * nn + o];
+        h[n] = a[n] > puny ? v[n] / a[n] : c0;                                                              // :590-594
+    }
+    if (a[1] > puny && h[1] <= A.hin_max[0] && A.hin_max[0] > c0) { a[1] = v[1] / A.hin_max[0]; h[1] = A.hin_max[0]; }      // :605-610
+    unsigned bits = 0;
+    _Pragma("unroll")
+    for (int q = 0; q < 2 * (ncat - 1); q++) {
+        bool up; int n, nd, nr;
+        itd_boundary(ncat, q, up, n, nd, nr);
+        if (!(a[nd] > puny && (up ? h[nd] > A.hin_max[n] : h[nd] <= A.hin_max[n]))) continue;               // :632-633, :687-688
+        bits |= 1u << q;
+        double daice = a[nd], dvice = v[nd];
+        const int bad = itd_check(daice, dvice, a[nd], v[nd], puny);
+        if (bad >= 0) { atomicMin(key, itd_key(b, 1 + q, bad, 0xffffffffu - (unsigned)o)); break; }
+        if (daice > c0) {                                                                                   // :1162-1166
+            a[nd] = a[nd] - daice; a[nr] = a[nr] + daice;
+            v[nd] = v[nd] - dvice; v[nr] = v[nr] + dvice;
+        }
+        _Pragma("unroll")
+        for (int m = 1; m <= ncat; m++) h[m] = a[m] > puny ? v[m] / a[m] : c0;                              // :1227-1231
+    }
+    if (bits) atomicOr(&bmask[b], bits);
+}
+template __global__ void __launch_bounds__(64) k_itd_scan<0>(Slab, const BlockDesc *, ItdArgs, unsigned *, unsigned long long *);
+template __global__ void __launch_bounds__(64) k_itd_scan<5>(Slab, const BlockDesc *, ItdArgs, unsigned *, unsigned long long *);
+
+// aicen * trcrn with shift_ice's association (:919-975, :1191-1208): the base, then alvl, apnd / fbri, then the tracer
+__device__ __forceinline__ double itd_product(int acc, double a, double v, double sn, double alvl, double apnd, double fbri, double t) {
+    switch (acc) {
+    case 0: return a * t;
+    case 1: return v * t;
+    case 2: return sn * t;
+    case 3: return a * alvl * t;
+    case 4: return a * apnd * t;
+    case 5: return a * alvl * apnd * t;
+    case 6: return v * fbri * t;
+    default: return 0.0;
+    }
+}
+
+// one call of shift_ice as a listed cell sees it: atrcrn from the old state, the transfer nd -> nr if the cell is a donor (nd > 0),
+// compute_tracers on the new state -- one tracer at a time, the old and new values of the tracers that others hang on in registers
+template <int NC>
+__device__ __forceinline__ void itd_shift_tracers(const ItdArgs &A, int ncat, double *t0 /* trcrn of (b, category 1, tracer 1, cell) */, size_t nn,
+                                                  const double *ao, const double *vo, const double *so, const double *an, const double *vn,
+                                                  const double *sn, int nd, int nr, double daice, double dvice, double dvsnow) {
+    constexpr int NA = NC ? NC : MAXCAT;
+    double oldP[3][NA + 1], newP[3][NA + 1];
+    const size_t cs = (size_t)A.ntrcr_dim * nn;                 // category stride
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        const double *t = t0 + (size_t)(n - 1) * cs;
+        oldP[0][n] = A.nt_alvl ? t[(size_t)(A.nt_alvl - 1) * nn] : 0.0;
+        oldP[1][n] = A.nt_apnd ? t[(size_t)(A.nt_apnd - 1) * nn] : 0.0;
+        oldP[2][n] = A.nt_fbri ? t[(size_t)(A.nt_fbri - 1) * nn] : 0.0;
+        newP[0][n] = 0.0; newP[1][n] = 0.0; newP[2][n] = 0.0;          // (a parent that comes later in the table is still 0, :1401)
+    }
+    for (int it = 0; it < A.ntrcr; it++) {
+        const int acc = A.acc[it], rule = A.rule[it], d1 = A.d1[it], d2 = A.d2[it], sl = A.slot[it];
+        double told[NA + 1], atr[NA + 1];
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) {
+            told[n] = t0[(size_t)(n - 1) * cs + (size_t)it * nn];
+            atr[n] = itd_product(acc, ao[n], vo[n], so[n], oldP[0][n], oldP[1][n], oldP[2][n], told[n]);
+        }
+        if (nd > 0) {
+            double dat = 0.0;
+            _Pragma("unroll")
+            for (int n = 1; n <= ncat; n++)
+                if (n == nd) dat = itd_product(acc, daice, dvice, dvsnow, oldP[0][n], oldP[1][n], oldP[2][n], told[n]);
+            if (acc >= 0) {
+                _Pragma("unroll")
+                for (int n = 1; n <= ncat; n++) {
+                    if (n == nd) atr[n] = atr[n] - dat;
+                    if (n == nr) atr[n] = atr[n] + dat;
+                }
+            }
+        }
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) {
+            const double p1 = d1 == 1 ? newP[0][n] : d1 == 2 ? newP[1][n] : d1 == 3 ? newP[2][n] : 0.0;
+            const double p2 = d2 == 1 ? newP[0][n] : d2 == 2 ? newP[1][n] : d2 == 3 ? newP[2][n] : 0.0;
+            const double r = compute_tracer(rule, atr[n], an[n], vn[n], sn[n], p1, p2, it + 1 == A.nt_fbri, A.Tocnfrz);
+            if (sl == 1) newP[0][n] = r;
+            else if (sl == 2) newP[1][n] = r;
+            else if (sl == 3) newP[2][n] = r;
+            t0[(size_t)(n - 1) * cs + (size_t)it * nn] = r;
+        }
+    }
+}
+
+template <int NC>
+__global__ void __launch_bounds__(64) k_itd_shift(Slab s, const BlockDesc *bd, ItdArgs A, const unsigned *bmask) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    const int j = blockIdx.y + 1;
+    const int b = blockIdx.z;
+    if (i > A.nxb) return;
+    const unsigned bm = bmask[b];
+    if (!bm) return;                                      // the common case: no cell of the block shifts
+    if (!itd_ocean(s, bd[b], i, j)) return;
+    const double puny = A.puny, c0 = 0.0;
+    const int ncat = NC ? NC : A.ncat;
+    constexpr int NA = NC ? NC : MAXCAT;
+    const size_t nn = (size_t)A.nyb * A.nxb, o = (size_t)(j - 1) * A.nxb + (i - 1), ci = (size_t)b * nn + o;
+    const size_t cs = (size_t)A.ntrcr_dim * nn;
+    double *t0 = A.trcrn + (size_t)b * ncat * cs + o;
+    double a[NA + 2], v[NA + 2], sn[NA + 2], h[NA + 2];
+    const double aice = A.aice[ci];                       // (k_itd_scan's)
+    if (!(aice > puny)) {                                 // an unlisted cell of a block that shifts: trcrn(:,:,:) = c0 (:1401)
+        for (int n = 0; n < ncat; n++)
+            for (int it = 0; it < A.ntrcr; it++) t0[(size_t)n * cs + (size_t)it * nn] = c0;
+        return;
+    }
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        const size_t bc = ((size_t)b * ncat + (n - 1)) * nn + o;
+        a[n] = A.aicen[bc]; v[n] = A.vicen[bc]; sn[n] = A.vsnon[bc];
+    }
+    unsigned dirty = 0;                                   // bit n - 1: aicen / vicen / vsnon of category n changed
+    {                                                     // a listed cell: rebin (:578-726)
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) h[n] = a[n] > puny ? v[n] / a[n] : c0;
+        if (a[1] > puny && h[1] <= A.hin_max[0] && A.hin_max[0] > c0) { a[1] = v[1] / A.hin_max[0]; h[1] = A.hin_max[0]; dirty |= 1u; }
+        {
+            _Pragma("unroll")
+            for (int q = 0; q < 2 * (ncat - 1); q++) {
+                if (!(bm & (1u << q))) continue;
+                bool up; int n, nd, nr;
+                itd_boundary(ncat, q, up, n, nd, nr);
+                double ao[NA + 2], vo[NA + 2], so[NA + 2];
+                _Pragma("unroll")
+                for (int m = 1; m <= ncat; m++) { ao[m] = a[m]; vo[m] = v[m]; so[m] = sn[m]; }
+                double daice = c0, dvice = c0, dvsnow = c0;
+                bool donor = a[nd] > puny && (up ? h[nd] > A.hin_max[n] : h[nd] <= A.hin_max[n]);
+                if (donor) {
+                    daice = a[nd]; dvice = v[nd];
+                    if (itd_check(daice, dvice, a[nd], v[nd], puny) >= 0) return;       // a stop (k_itd_scan has recorded it): the state is undefined
+                    donor = daice > c0;                                                // :1137
+                }
+                if (donor) {                                                           // :1153-1171
+                    const double worka = daice / a[nd];
+                    a[nd] = a[nd] - daice; a[nr] = a[nr] + daice;
+                    v[nd] = v[nd] - dvice; v[nr] = v[nr] + dvice;
+                    dvsnow = sn[nd] * worka;
+                    sn[nd] = sn[nd] - dvsnow; sn[nr] = sn[nr] + dvsnow;
+                    dirty |= (1u << (nd - 1)) | (1u << (nr - 1));
+                }
+                if (A.ntrcr > 0) itd_shift_tracers<NC>(A, ncat, t0, nn, ao, vo, so, a, v, sn, donor ? nd : 0, nr, daice, dvice, dvsnow);
+                _Pragma("unroll")
+                for (int m = 1; m <= ncat; m++) h[m] = a[m] > puny ? v[m] / a[m] : c0;
+            }
+        }
+    }
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        if (!(dirty & (1u << (n - 1)))) continue;
+        const size_t bc = ((size_t)b * ncat + (n - 1)) * nn + o;
+        A.aicen[bc] = a[n]; A.vicen[bc] = v[n]; A.vsnon[bc] = sn[n];
+    }
+}
+template __global__ void __launch_bounds__(64) k_itd_shift<0>(Slab, const BlockDesc *, ItdArgs, const unsigned *);
+template __global__ void __launch_bounds__(64) k_itd_shift<5>(Slab, const BlockDesc *, ItdArgs, const unsigned *);
+
+// zap_small_areas I / II, zap_snow_temperature and the flux increments of a physical ocean cell, on the state rebin left
+template <int NC>
+__global__ void __launch_bounds__(64) k_itd_zap(Slab s, const BlockDesc *bd, ItdArgs A, const unsigned *bmask, unsigned long long *key) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    const int j = blockIdx.y + 1;
+    const int b = blockIdx.z;
+    if (i > A.nxb) return;
+    if (!itd_ocean(s, bd[b], i, j)) return;
+    const double puny = A.puny, c0 = 0.0, c1 = 1.0, p001 = 0.001;
+    const int ncat = NC ? NC : A.ncat;
+    constexpr int NA = NC ? NC : MAXCAT;
+    const size_t nn = (size_t)A.nyb * A.nxb, o = (size_t)(j - 1) * A.nxb + (i - 1), ci = (size_t)b * nn + o;
+    const size_t cs = (size_t)A.ntrcr_dim * nn;
+    double *t0 = A.trcrn + (size_t)b * ncat * cs + o;
+    double a[NA + 2], v[NA + 2], sn[NA + 2];
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        const size_t bc = ((size_t)b * ncat + (n - 1)) * nn + o;
+        a[n] = A.aicen[bc]; v[n] = A.vicen[bc]; sn[n] = A.vsnon[bc];
+    }
+    double aice = A.aice[ci], aice0 = A.aice0[ci];        // (k_itd_scan's: the sums over the state before rebin)
+    unsigned dirty = 0;                                   // bit n - 1: aicen / vicen / vsnon of category n changed
+    // the category-1 adjustment of rebin (:605-610) in a block that does not shift (k_itd_shift has made it in the others)
+    if (!bmask[b] && aice > puny && a[1] > puny && v[1] / a[1] <= A.hin_max[0] && A.hin_max[0] > c0) { a[1] = v[1] / A.hin_max[0]; dirty |= 1u; }
+    double dfpond = c0, dfresh = c0, dfsalt = c0, dfhocn = c0;
+    bool zapped = false;
+    const double dt = A.dt;
+    // zap_small_areas I (:1872-2015)
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        if (a[n] < -puny) { atomicMin(key, itd_key(b, 2 * ncat, n, (unsigned)o)); return; }                   // :1881 (returns: the first one)
+        if (!(fabs(a[n]) != c0 && fabs(a[n]) <= puny)) continue;
+        zapped = true;
+        double *t = t0 + (size_t)(n - 1) * cs;
+        if (A.tr_pond_topo) { const double x = a[n] * t[(size_t)(A.nt_apnd - 1) * nn] * t[(size_t)(A.nt_hpnd - 1) * nn]; dfpond = dfpond - x; }
+        for (int k = 0; k < A.nilyr; k++) {
+            const double x = t[(size_t)(A.nt_qice - 1 + k) * nn] / dt * v[n] / (double)A.nilyr;
+            dfhocn = dfhocn + x;
+        }
+        double x = (A.rhoi * v[n]) / dt;
+        dfresh = dfresh + x;
+        x = A.rhoi * v[n] * A.salinity * p001 / dt;
+        dfsalt = dfsalt + x;
+        aice0 = aice0 + a[n];
+        a[n] = c0; v[n] = c0;
+        for (int k = 0; k < A.nslyr; k++) {                                                                  // zap_snow (:2240-2268)
+            x = t[(size_t)(A.nt_qsno - 1 + k) * nn] / dt * sn[n] / (double)A.nslyr;
+            dfhocn = dfhocn + x;
+        }
+        x = (A.rhos * sn[n]) / dt;
+        dfresh = dfresh + x;
+        sn[n] = c0;
+        dirty |= 1u << (n - 1);
+        // :1947 qice = 0, :1972 Tsfc = Tocnfrz, :2251 qsno = 0, then tracers 2 .. ntrcr: 0, fbri 1 (:1991-2007) -- tracer 1 is not in that loop
+        if (A.nt_Tsfc == 1) t[0] = A.Tocnfrz;
+        else if ((A.nilyr > 0 && A.nt_qice == 1) || (A.nslyr > 0 && A.nt_qsno == 1)) t[0] = c0;
+        for (int it = 1; it < A.ntrcr; it++) t[(size_t)it * nn] = (A.tr_brine && it + 1 == A.nt_fbri) ? c1 : c0;
+        if (A.first_ice) A.first_ice[((size_t)b * ncat + (n - 1)) * nn + o] = 1;
+    }
+    // II (:2022-2164)
+    if (aice > c1 + puny) { atomicMin(key, itd_key(b, 2 * ncat + 1, 0, (unsigned)o)); return; }
+    if (aice > c1 && aice < c1 + puny) {
+        zapped = true;
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) {
+            const double *t = t0 + (size_t)(n - 1) * cs;
+            double x;
+            if (A.tr_pond_topo) {
+                x = a[n] * t[(size_t)(A.nt_apnd - 1) * nn] * t[(size_t)(A.nt_hpnd - 1) * nn] * (aice - c1) / aice;
+                dfpond = dfpond - x;
+            }
+            for (int k = 0; k < A.nilyr; k++) {
+                x = t[(size_t)(A.nt_qice - 1 + k) * nn] * v[n] / (double)A.nilyr * (aice - c1) / aice / dt;
+                dfhocn = dfhocn + x;
+            }
+            for (int k = 0; k < A.nslyr; k++) {
+                x = t[(size_t)(A.nt_qsno - 1 + k) * nn] * sn[n] / (double)A.nslyr * (aice - c1) / aice / dt;
+                dfhocn = dfhocn + x;
+            }
+            x = (A.rhoi * v[n] + A.rhos * sn[n]) * (aice - c1) / aice / dt;
+            dfresh = dfresh + x;
+            x = A.rhoi * v[n] * A.salinity * p001 * (aice - c1) / aice / dt;
+            dfsalt = dfsalt + x;
+            a[n] = a[n] * (c1 / aice); v[n] = v[n] * (c1 / aice); sn[n] = sn[n] * (c1 / aice);
+        }
+        dirty = ~0u;
+        aice = c1; aice0 = c0;
+        A.aice[ci] = aice;
+    }
+    // zap_snow_temperature (:2341-2413)
+    const double rnslyr = (double)A.nslyr;
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        if (!(a[n] > puny)) continue;
+        double *t = t0 + (size_t)(n - 1) * cs;
+        const double hsn = sn[n] / a[n];
+        bool l_zap = false;
+        for (int k = 0; k < A.nslyr; k++) {
+            double zqsn, Tmax;
+            if (hsn > A.hs_min) {
+                zqsn = t[(size_t)(A.nt_qsno - 1 + k) * nn];
+                Tmax = -zqsn * puny * rnslyr / (A.rhos * A.cp_ice * sn[n]);
+            } else {
+                zqsn = -A.rhos * A.Lfresh;
+                Tmax = puny;
+            }
+            const double zTsn = (A.Lfresh + zqsn / A.rhos) / A.cp_ice;
+            if (zTsn < A.Tmin || zTsn > Tmax) l_zap = true;
+        }
+        if (!l_zap) continue;
+        zapped = true;
+        for (int k = 0; k < A.nslyr; k++) {
+            const double x = t[(size_t)(A.nt_qsno - 1 + k) * nn] / dt * sn[n] / (double)A.nslyr;
+            dfhocn = dfhocn + x;
+            t[(size_t)(A.nt_qsno - 1 + k) * nn] = c0;
+        }
+        const double x = (A.rhos * sn[n]) / dt;
+        dfresh = dfresh + x;
+        sn[n] = c0;
+        dirty |= 1u << (n - 1);
+    }
+    if (zapped) A.aice0[ci] = aice0;
+    if (dirty) {
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) {
+            if (!(dirty & (1u << (n - 1)))) continue;
+            const size_t bc = ((size_t)b * ncat + (n - 1)) * nn + o;
+            A.aicen[bc] = a[n]; A.vicen[bc] = v[n]; A.vsnon[bc] = sn[n];
+        }
+    }
+    if (zapped) {                                           // :1741-1748 (adding the zero of a cell that zaps nothing changes nothing)
+        if (A.fpond) A.fpond[ci] = A.fpond[ci] + dfpond;
+        if (A.fresh) A.fresh[ci] = A.fresh[ci] + dfresh;
+        if (A.fsalt) A.fsalt[ci] = A.fsalt[ci] + dfsalt;
+        if (A.fhocn) A.fhocn[ci] = A.fhocn[ci] + dfhocn;
+    }
+}
+template __global__ void __launch_bounds__(64) k_itd_zap<0>(Slab, const BlockDesc *, ItdArgs, const unsigned *, unsigned long long *);
+template __global__ void __launch_bounds__(64) k_itd_zap<5>(Slab, const BlockDesc *, ItdArgs, const unsigned *, unsigned long long *);
+
+// aggregate (:246-458) on every cell of every block, then the tendencies of step_dynamics on the physical cells
+template <int NC>
+__global__ void __launch_bounds__(64) k_itd_aggregate(Slab s, const BlockDesc *bd, ItdArgs A) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    const int j = blockIdx.y + 1;
+    const int b = blockIdx.z;
+    if (i > A.nxb) return;
+    const double c0 = 0.0, c1 = 1.0;
+    const int ncat = NC ? NC : A.ncat;
+    constexpr int NA = NC ? NC : MAXCAT;
+    const BlockDesc d = bd[b];
+    const size_t nn = (size_t)A.nyb * A.nxb, o = (size_t)(j - 1) * A.nxb + (i - 1), ci = (size_t)b * nn + o;
+    const size_t cs = (size_t)A.ntrcr_dim * nn;
+    const int si = d.iglob_lo + (i - d.ilo) - s.i0 + 1, sj = d.jglob_lo + (j - d.jlo) - s.j0 + 1;
+    const bool inslab = si >= 0 && si <= s.nxl + 1 && sj >= 0 && sj <= s.nyl + 1;
+    const bool tm = inslab && s.tmask[mcell(s, si, sj)] != 0;
+    double *tr = A.trcr + (size_t)b * cs + o;
+    double aice = c0, vice = c0, vsno = c0, aice0 = c1;
+    if (tm) {
+        const double *t0 = A.trcrn + (size_t)b * ncat * cs + o;
+        double a[NA + 1], v[NA + 1], sn[NA + 1], P[3][NA + 1], newP[3] = {c0, c0, c0};
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) {
+            const size_t bc = ((size_t)b * ncat + (n - 1)) * nn + o;
+            a[n] = A.aicen[bc]; v[n] = A.vicen[bc]; sn[n] = A.vsnon[bc];
+            aice = aice + a[n]; vice = vice + v[n]; vsno = vsno + sn[n];
+            const double *t = t0 + (size_t)(n - 1) * cs;
+            P[0][n] = A.nt_alvl ? t[(size_t)(A.nt_alvl - 1) * nn] : c0;
+            P[1][n] = A.nt_apnd ? t[(size_t)(A.nt_apnd - 1) * nn] : c0;
+            P[2][n] = A.nt_fbri ? t[(size_t)(A.nt_fbri - 1) * nn] : c0;
+        }
+        aice0 = fmax(c1 - aice, c0);
+        for (int it = 0; it < A.ntrcr; it++) {
+            const int acc = A.acc[it], d1 = A.d1[it], d2 = A.d2[it], sl = A.slot[it];
+            double atr = c0;
+            _Pragma("unroll")
+            for (int n = 1; n <= ncat; n++) {                                                               // :356-431: the tracer first
+                const double t = t0[(size_t)(n - 1) * cs + (size_t)it * nn];
+                double p;
+                switch (acc) {
+                case 0: p = t * a[n]; break;
+                case 1: p = t * v[n]; break;
+                case 2: p = t * sn[n]; break;
+                case 3: p = t * P[0][n] * a[n]; break;
+                case 4: p = t * P[1][n] * a[n]; break;
+                case 5: p = t * P[1][n] * P[0][n] * a[n]; break;
+                case 6: p = t * P[2][n] * v[n]; break;
+                default: p = c0;
+                }
+                if (acc >= 0) atr = atr + p;
+            }
+            const double p1 = d1 == 1 ? newP[0] : d1 == 2 ? newP[1] : d1 == 3 ? newP[2] : c0;
+            const double p2 = d2 == 1 ? newP[0] : d2 == 2 ? newP[1] : d2 == 3 ? newP[2] : c0;
+            const double r = compute_tracer(A.rule[it], atr, aice, vice, vsno, p1, p2, it + 1 == A.nt_fbri, A.Tocnfrz);
+            if (sl == 1) newP[0] = r;
+            else if (sl == 2) newP[1] = r;
+            else if (sl == 3) newP[2] = r;
+            tr[(size_t)it * nn] = r;
+        }
+    } else {
+        for (int it = 0; it < A.ntrcr; it++) tr[(size_t)it * nn] = c0;                                      // trcrn(:,:,:) = c0 (:1401)
+    }
+    A.aice[ci] = aice; A.vice[ci] = vice; A.vsno[ci] = vsno; A.aice0[ci] = aice0;
+    if (i >= d.ilo && i <= d.ihi && j >= d.jlo && j <= d.jhi) {                                             // ice_step_mod.F90:1183-1189
+        if (A.dvidtd) A.dvidtd[ci] = (vice - A.dvidtd[ci]) / A.dt;
+        if (A.daidtd) A.daidtd[ci] = (aice - A.daidtd[ci]) / A.dt;
+        if (A.dagedtd && A.nt_iage > 0) A.dagedtd[ci] = (tr[(size_t)(A.nt_iage - 1) * nn] - A.dagedtd[ci]) / A.dt;
+    }
+}
+template __global__ void __launch_bounds__(64) k_itd_aggregate<0>(Slab, const BlockDesc *, ItdArgs);
+template __global__ void __launch_bounds__(64) k_itd_aggregate<5>(Slab, const BlockDesc *, ItdArgs);
+
+}  // namespace evpk

@@ -95,7 +95,8 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_unpin_host", "evpk_connect", "evpk_device_check", "evpk_restart_write", "evpk_restart_read",
            "evpk_transport_upwind", "evpk_remap_init", "evpk_transport_remap", "evpk_transport_remap_state",
            "evpk_eap_init", "evpk_eap_upload", "evpk_eap_download", "evpk_halo_update", "evpk_halo_update_stress",
-           "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice"]
+           "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
+           "evpk_cleanup_itd", "evpk_aggregate"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -111,6 +112,22 @@ class RidgeTracers(ct.Structure):
 
 class RidgeDiag(ct.Structure):
     _fields_ = [(n, c_f64p) for n in RIDGE_DIAG_2D + RIDGE_DIAG_3D]
+
+
+ITD_STOP = 14
+ITD_STOP_REASONS = {1: "aggregate ice area out of bounds", 2: "shift_ice: negative daice", 3: "shift_ice: negative dvice",
+                    4: "shift_ice: daice > aicen", 5: "shift_ice: dvice > vicen", 6: "zap ice: negative ice area", 7: "zap ice: excess ice area"}
+ITD_TRACER_FIELDS = ["nt_Tsfc", "nt_qice", "nilyr", "nt_qsno", "nslyr", "nt_alvl", "nt_apnd", "nt_hpnd", "nt_fbri", "tr_pond_cesm", "tr_pond_lvl",
+                     "tr_pond_topo", "tr_brine"]
+ITD_CONSTANT_FIELDS = ["Tocnfrz", "ice_ref_salinity", "hs_min", "cp_ice", "Lfresh", "Tmin", "puny"]
+
+
+class ItdTracers(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ITD_TRACER_FIELDS]
+
+
+class ItdConstants(ct.Structure):
+    _fields_ = [(n, ct.c_double) for n in ITD_CONSTANT_FIELDS]
 
 _lib = None
 
@@ -166,6 +183,10 @@ def lib():
         L.evpk_eap_download.argtypes = [ctxp, ct.POINTER(EapState)]
         L.evpk_ridge_ice.argtypes = ([ctxp, ct.c_double] + [ct.c_int32] * 4 + [c_i32p, ct.POINTER(RidgeTracers)] + [c_f64p] * 8 +
                                      [ct.POINTER(RidgeDiag), c_i32p])
+        L.evpk_cleanup_itd.argtypes = ([ctxp, ct.c_double] + [ct.c_int32] * 3 + [c_i32p, ct.POINTER(ItdTracers), c_f64p, ct.POINTER(ItdConstants)] +
+                                       [ct.c_int32] * 3 + [c_f64p] * 10 + [c_i32p, c_i32p])
+        L.evpk_aggregate.argtypes = ([ctxp, ct.c_double] + [ct.c_int32] * 4 + [c_i32p, ct.POINTER(ItdTracers), ct.c_int32, ct.c_double] +
+                                     [c_f64p] * 12)
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -236,6 +257,10 @@ def host_is_mapped(a: np.ndarray) -> bool:
 def _p64(a: Optional[np.ndarray]):
     if a is None:
         return None
+    if hasattr(a, "data_ptr"):          # a torch tensor in device (or page-locked) memory: the library takes the pointer as it is
+        if str(a.dtype) != "torch.float64" or not a.is_contiguous():
+            raise TypeError("expected a contiguous float64 tensor")
+        return ct.cast(a.data_ptr(), c_f64p)
     if a.dtype != np.float64 or not a.flags.c_contiguous:
         raise TypeError("expected a C-contiguous float64 block array")
     return a.ctypes.data_as(c_f64p)
@@ -244,6 +269,10 @@ def _p64(a: Optional[np.ndarray]):
 def _p32(a: Optional[np.ndarray]):
     if a is None:
         return None
+    if hasattr(a, "data_ptr"):
+        if str(a.dtype) != "torch.int32" or not a.is_contiguous():
+            raise TypeError("expected a contiguous int32 tensor")
+        return ct.cast(a.data_ptr(), c_i32p)
     if a.dtype != np.int32 or not a.flags.c_contiguous:
         raise TypeError("expected a C-contiguous int32 block array")
     return a.ctypes.data_as(c_i32p)
@@ -455,6 +484,50 @@ class Context:
             return tuple(int(v) for v in stop)
         self._chk(rc, "evpk_ridge_ice")
         return None
+
+    def cleanup_itd(self, dt: float, aicen, vicen, vsnon, trcrn, aice0, aice, ntrcr: int, trcr_depend, tracers, hin_max, constants=None,
+                    fluxes=None, first_ice=None, tr_aero=False, nbtrcr=0, heat_capacity=True):
+        """evpk_cleanup_itd (cleanup_itd, ice_itd.F90:1514-1769; dt = dt * ndtd of step_ridge): aicen / vicen / vsnon (nb, ncat, ny, nx), trcrn
+        (nb, ncat, ntrcr_dim, ny, nx) in place on the physical ocean cells, aice0 / aice (nb, ny, nx) on every cell.  tracers: dict of
+        ITD_TRACER_FIELDS (absent = 0); hin_max: (ncat + 1,); constants: dict of ITD_CONSTANT_FIELDS (absent: cice5_amd.constants);
+        fluxes: dict with any of fpond, fresh, fsalt, fhocn (nb, ny, nx), incremented; first_ice: int32 (nb, ncat, ny, nx) or None.
+        Returns None, or (reason, block, i, j) for the reference's l_stop cases (ITD_STOP_REASONS); raises on a refusal."""
+        from . import constants as C
+        ncat = int(aicen.shape[1])
+        dep = np.ascontiguousarray(trcr_depend, dtype=np.int32)
+        hin = np.ascontiguousarray(hin_max, dtype=np.float64)
+        assert hin.shape == (ncat + 1,)
+        it = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        ik = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
+        fl = fluxes or {}
+        stop = np.zeros(4, dtype=np.int32)
+        ntrcr_dim = int(trcrn.shape[2]) if trcrn is not None else 0
+        rc = self._L.evpk_cleanup_itd(self._ctx, float(dt), ncat, int(ntrcr), ntrcr_dim, _p32(dep) if ntrcr else None, ct.byref(it), _p64(hin),
+                                      ct.byref(ik), int(bool(tr_aero)), int(nbtrcr), int(bool(heat_capacity)), _p64(aicen), _p64(vicen),
+                                      _p64(vsnon), _p64(trcrn), _p64(aice0), _p64(aice), _p64(fl.get("fpond")), _p64(fl.get("fresh")),
+                                      _p64(fl.get("fsalt")), _p64(fl.get("fhocn")), _p32(first_ice), _p32(stop))
+        if rc == ITD_STOP:
+            return tuple(int(v) for v in stop)
+        self._chk(rc, "evpk_cleanup_itd")
+        return None
+
+    def aggregate(self, dt: float, aicen, vicen, vsnon, trcrn, aice, vice, vsno, aice0, trcr, ntrcr: int, trcr_depend, tracers, bound=False,
+                  daidtd=None, dvidtd=None, dagedtd=None, Tocnfrz=None):
+        """evpk_aggregate: bound_state (bound = True: the ghost cells of aicen, vicen, vsnon, trcrn are rewritten), aggregate
+        (ice_itd.F90:246-458) on every cell -- aice, vice, vsno, aice0 (nb, ny, nx), trcr (nb, ntrcr_dim, ny, nx) -- and the tendencies of
+        step_dynamics on physical cells: daidtd, dvidtd, dagedtd in / out (on entry the pre-dynamics aice, vice, age), each may be None;
+        tracers: dict of ITD_TRACER_FIELDS plus nt_iage."""
+        from . import constants as C
+        ncat = int(aicen.shape[1])
+        dep = np.ascontiguousarray(trcr_depend, dtype=np.int32)
+        it = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        ntrcr_dim = int(trcrn.shape[2]) if trcrn is not None else 0
+        assert trcr is None or trcr.shape[1] == ntrcr_dim
+        rc = self._L.evpk_aggregate(self._ctx, float(dt), int(bool(bound)), ncat, int(ntrcr), ntrcr_dim, _p32(dep) if ntrcr else None, ct.byref(it),
+                                    int(tracers.get("nt_iage", 0)), float(C.Tocnfrz if Tocnfrz is None else Tocnfrz), _p64(aicen), _p64(vicen),
+                                    _p64(vsnon), _p64(trcrn), _p64(aice), _p64(vice), _p64(vsno), _p64(aice0), _p64(trcr), _p64(daidtd),
+                                    _p64(dvidtd), _p64(dagedtd))
+        self._chk(rc, "evpk_aggregate")
 
     def eap_init(self, tables):
         """evpk_eap_init: the six lookup tables of init_eap, each [na_yield][ny_yield][nx_yield]; the context then runs eap(dt)"""

@@ -111,6 +111,16 @@
          type (c_ptr) :: krdgn = c_null_ptr, araftn = c_null_ptr, vraftn = c_null_ptr, aredistn = c_null_ptr, vredistn = c_null_ptr
       end type evpk_ridge_diag
 
+      ! evpk_itd_tracers, evpk_itd_constants (include/evpk.h): the ice_state tracer indices cleanup_itd / aggregate read (1-based, 0 = not
+      ! in use) and the constants of ice_constants / ice_therm_shared that zap_small_areas and zap_snow_temperature read
+      type, bind(C) :: evpk_itd_tracers
+         integer (c_int32_t) :: nt_Tsfc = 0, nt_qice = 0, nilyr = 0, nt_qsno = 0, nslyr = 0, nt_alvl = 0, nt_apnd = 0, nt_hpnd = 0, nt_fbri = 0
+         integer (c_int32_t) :: tr_pond_cesm = 0, tr_pond_lvl = 0, tr_pond_topo = 0, tr_brine = 0
+      end type evpk_itd_tracers
+      type, bind(C) :: evpk_itd_constants
+         real (c_double) :: Tocnfrz, ice_ref_salinity, hs_min, cp_ice, Lfresh, Tmin, puny
+      end type evpk_itd_constants
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -120,10 +130,12 @@
                 evpk_transport_upwind, evpk_remap_init, evpk_transport_remap, evpk_transport_remap_state, &
                 EVPK_REMAP_BAD_DEPARTURE, EVPK_REMAP_NEGATIVE_MASS, &
                 evpk_eap_state, evpk_eap_init, evpk_eap_upload, evpk_eap_download, &
-                evpk_ridge_tracers, evpk_ridge_diag, evpk_ridge_ice, EVPK_RIDGE_STOP
+                evpk_ridge_tracers, evpk_ridge_diag, evpk_ridge_ice, EVPK_RIDGE_STOP, &
+                evpk_itd_tracers, evpk_itd_constants, evpk_cleanup_itd, evpk_aggregate, EVPK_ITD_STOP
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
+      integer (c_int), parameter :: EVPK_ITD_STOP = 14
 
       interface
          integer (c_int) function evpk_get_unique_id (id) bind(C, name='evpk_get_unique_id')
@@ -269,6 +281,29 @@
             integer (c_int32_t), value :: ndtd, ncat, ntrcr, ntrcr_dim
             type (evpk_ridge_tracers), intent(in) :: t
             integer (c_int32_t), intent(out) :: stop(4)
+         end function
+         ! cleanup_itd (ice_itd.F90:1514-1769) for every block: the call of step_ridge (ice_step_mod.F90:1325-1341), dt = dt * ndtd.  fpond,
+         ! fresh, fsalt, fhocn, first_ice (integer(c_int32_t), 0 / 1) may be c_null_ptr; stop(4): reason, block, i, j
+         integer (c_int) function evpk_cleanup_itd (ctx, dt, ncat, ntrcr, ntrcr_dim, trcr_depend, t, hin_max, k, tr_aero, nbtrcr, &
+               heat_capacity, aicen, vicen, vsnon, trcrn, aice0, aice, fpond, fresh, fsalt, fhocn, first_ice, stop) &
+               bind(C, name='evpk_cleanup_itd')
+            import :: c_int, c_ptr, c_double, c_int32_t, evpk_itd_tracers, evpk_itd_constants
+            type (c_ptr), value :: ctx, trcr_depend, hin_max, aicen, vicen, vsnon, trcrn, aice0, aice, fpond, fresh, fsalt, fhocn, first_ice
+            real (c_double), value :: dt
+            integer (c_int32_t), value :: ncat, ntrcr, ntrcr_dim, tr_aero, nbtrcr, heat_capacity
+            type (evpk_itd_tracers), intent(in) :: t
+            type (evpk_itd_constants), intent(in) :: k
+            integer (c_int32_t), intent(out) :: stop(4)
+         end function
+         ! bound_state (bound = 1), aggregate (ice_itd.F90:246-458) on every cell and the tendencies of step_dynamics
+         ! (ice_step_mod.F90:1152-1189); daidtd, dvidtd, dagedtd may be c_null_ptr
+         integer (c_int) function evpk_aggregate (ctx, dt, bound, ncat, ntrcr, ntrcr_dim, trcr_depend, t, nt_iage, Tocnfrz, aicen, vicen, &
+               vsnon, trcrn, aice, vice, vsno, aice0, trcr, daidtd, dvidtd, dagedtd) bind(C, name='evpk_aggregate')
+            import :: c_int, c_ptr, c_double, c_int32_t, evpk_itd_tracers
+            type (c_ptr), value :: ctx, trcr_depend, aicen, vicen, vsnon, trcrn, aice, vice, vsno, aice0, trcr, daidtd, dvidtd, dagedtd
+            real (c_double), value :: dt, Tocnfrz
+            integer (c_int32_t), value :: bound, ncat, ntrcr, ntrcr_dim, nt_iage
+            type (evpk_itd_tracers), intent(in) :: t
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then
          ! mm(nx_block,ny_block,0:ncat,max_blocks), tm(nx_block,ny_block,ntrace,ncat,max_blocks) advanced in place

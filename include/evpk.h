@@ -306,7 +306,7 @@ int evpk_transport_remap_state(evpk_ctx *c, double dt, int32_t ncat, int32_t ntr
 
 /* ridge_ice (source/ice_mechred.F90:101-746), the call of step_ridge (ice_step_mod.F90:1285-1305), on the device:
  * asum_ridging, ridge_prep, ridge_itd, ridge_shift with compute_tracers, ridge_check and the diagnostics, for every block of the
- * context.  cleanup_itd and aggregate, the rest of step_ridge / step_dynamics, stay with the host.
+ * context.  cleanup_itd and aggregate, the rest of step_ridge / step_dynamics, follow as evpk_cleanup_itd and evpk_aggregate below.
  *   dt, ndtd                         the dynamics time step and the number of dynamics subcycles (fresh / fhocn average over ndtd * dt)
  *   ncat, ntrcr, ntrcr_dim, trcr_depend, aice0, aicen, vicen, vsnon, trcrn    as for evpk_transport_upwind_state (host arrays, page-locked
  *                                    arrays or device pointers)
@@ -343,6 +343,63 @@ int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat, int32_t n
                    const double *rdg_conv, const double *rdg_shear,   /* NULL: the planes the last evp / eap left on the device */
                    double *aice0, double *aicen, double *vicen, double *vsnon, double *trcrn,
                    evpk_ridge_diag *diag, int32_t stop[4] /* out: reason, block, i, j */);
+
+/* The rest of step_ridge / step_dynamics on the device (ice_step_mod.F90:1325-1341, :1152-1189), so that a caller whose state lives in
+ * device or page-locked memory runs evp -> transport -> ridge_ice -> cleanup_itd -> bound_state -> aggregate without leaving the GPU.
+ * Array conventions as evpk_ridge_ice: host arrays, page-locked arrays or device pointers; staged or used in place.
+ *
+ * evpk_cleanup_itd: cleanup_itd (source/ice_itd.F90:1514-1769) with limit_aice = .true. for every block of the context: aggregate_area on
+ * every cell of the block arrays, the area check (:1646-1670), rebin (:516) with shift_ice (:815) and compute_tracers (:1359),
+ * zap_small_areas I and II (:1778) with zap_snow (:2170), zap_snow_temperature (:2274) and the flux increments (:1741-1748).
+ *   dt                               what step_ridge passes: dt * ndtd
+ *   ncat, ntrcr, ntrcr_dim, trcr_depend, aicen, vicen, vsnon, trcrn    as for evpk_ridge_ice; in / out
+ *   t                                the ice_state tracer indices these routines read, 1-based, 0 = not in use; nt_Tsfc is required
+ *   hin_max(0:ncat)                  the category boundaries (ice_itd); hin_max(ncat) is not read
+ *   k                                constants of ice_constants / ice_therm_shared (drivers/auscom/ice_constants.F90, ice_therm_shared.F90:35);
+ *                                    rhoi, rhos come from evpk_params; puny must be 1e-11
+ *   tr_aero, nbtrcr, heat_capacity   the reference's arguments of these names; only 0, 0, 1 are accepted
+ *   aice0, aice                      (nx_block, ny_block, nblocks), out on every cell
+ *   fpond, fresh, fsalt, fhocn       in / out, each may be NULL (not incremented)
+ *   first_ice                        int32 (nx_block, ny_block, ncat, nblocks) or NULL: set to 1 where zap_small_areas zaps a category
+ * rebin's shiftflag is one flag per block and category boundary: when one cell of a block shifts, shift_ice rewrites the tracers of every
+ * cell of the block with aice > puny (as (aicen * trcrn) / aicen) and compute_tracers zeroes those of the others (:1401); the device does
+ * the same per block.  Departures: physical ocean cells (tmask) reproduce the reference bit for bit, that zeroing included; land cells
+ * and ghost cells of aicen, vicen, vsnon, trcrn keep the caller's values (the reference zeroes their tracers in a block that shifts, and
+ * bound_state follows), and the area check and the zaps look at ocean cells only; on a stop the state arrays are undefined (the
+ * reference aborts).
+ * Returns 0; EVPK_ITD_STOP with stop[] = {reason, block (1-based), i, j} for the reference's l_stop cases: the lowest block that stops,
+ * in it the earliest stage in the reference's order (the area check, rebin boundary by boundary -- upward 1 .. ncat-1, then downward --
+ * zap_small_areas), and the cell the reference reports: the loop of the area check (:1648-1655) and the error loops of shift_ice
+ * (:1040-1126) do not exit and report the LAST failing cell in (j, i) order, zap_small_areas returns at the FIRST in (n, j, i) order.
+ * Reasons: 1 aggregate ice area out of bounds (:1650); 2 shift_ice negative daice (:1045), 3 negative dvice (:1066), 4 daice > aicen (:1089),
+ * 5 dvice > vicen (:1112); 6 zap: aicen < -puny (:1881); 7 zap: excess area (:2025).  Inputs can reach 1, 3 (a negative vicen under
+ * aicen > puny, a donor on the downward pass) and 6.  2, 4, 5 cannot be reached from rebin: it sets daice = aicen > puny and
+ * dvice = vicen of the donor, which pass those checks identically; 7 cannot, because aice is checked at :1650 and not recomputed.
+ * Or 1 with evpk_last_error: aerosol tracers, nbtrcr > 0, heat_capacity = .false., nranks > 1 (follow-ups), ntrcr > 32, ncat > 16.
+ *
+ * evpk_aggregate: the second half of step_dynamics.  bound = 1: bound_state (ice_state.F90:173-238) first -- ice_HaloUpdate, centre
+ * scalar, of aicen, trcrn(1:ntrcr), vicen, vsnon (their ghost cells are then in / out; fill 0 next to an eliminated land block) -- then
+ * aggregate (ice_itd.F90:246-458) on every cell of every block, ghost cells included: aice, vice, vsno, aice0 (nx_block, ny_block, nblocks)
+ * and trcr (nx_block, ny_block, ntrcr_dim, nblocks) are written on every cell, tracers 1 .. ntrcr; the category sums run n outer, the products
+ * as written at :356-431.  Then, on physical cells, the tendencies (ice_step_mod.F90:1183-1189): daidtd, dvidtd are in / out -- on entry they
+ * hold the pre-dynamics aice, vice -- and so is dagedtd, computed when nt_iage > 0; each may be NULL. */
+#define EVPK_HAS_CLEANUP_ITD 1
+typedef struct {            /* 1-based tracer indices of ice_state, 0 = not in use; nilyr / nslyr layers from nt_qice / nt_qsno */
+    int32_t nt_Tsfc, nt_qice, nilyr, nt_qsno, nslyr, nt_alvl, nt_apnd, nt_hpnd, nt_fbri;
+    int32_t tr_pond_cesm, tr_pond_lvl, tr_pond_topo, tr_brine;
+} evpk_itd_tracers;
+typedef struct {
+    double Tocnfrz, ice_ref_salinity, hs_min, cp_ice, Lfresh, Tmin, puny;
+} evpk_itd_constants;
+#define EVPK_ITD_STOP 14
+int evpk_cleanup_itd(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
+                     const evpk_itd_tracers *t, const double *hin_max /* 0:ncat */, const evpk_itd_constants *k,
+                     int32_t tr_aero, int32_t nbtrcr, int32_t heat_capacity,
+                     double *aicen, double *vicen, double *vsnon, double *trcrn, double *aice0, double *aice,
+                     double *fpond, double *fresh, double *fsalt, double *fhocn, int32_t *first_ice, int32_t stop[4] /* out: reason, block, i, j */);
+int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
+                   const evpk_itd_tracers *t, int32_t nt_iage, double Tocnfrz, double *aicen, double *vicen, double *vsnon, double *trcrn,
+                   double *aice, double *vice, double *vsno, double *aice0, double *trcr, double *daidtd, double *dvidtd, double *dagedtd);
 
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared
