@@ -346,6 +346,12 @@ struct evpk_ctx {
     // evpk_cleanup_itd: the per-block masks of the boundaries at which a block shifts, the stop key
     unsigned *itd_bmask = nullptr; size_t itd_bmask_n = 0;
     unsigned long long *itd_key = nullptr;
+    // evpk_bound_state: whether the blocks are the uniform tiling k_bound_state's block table assumes (0 not looked at yet, 1 yes, -1 no)
+    int bs_uniform = 0;
+    // evpk_step_dynamics: the pool the caller's pageable arrays of one call are staged into; check_only makes the stage routines return
+    // after their argument checks, before the first copy or launch
+    double *dyn_stage = nullptr; size_t dyn_stage_n = 0;
+    bool check_only = false;
     // EAP (kdyn = 2): set by evpk_eap_init -- the subcycle loop then runs stress_eap / stepu / stepa (evpk_eap.hip)
     bool eap = false;
     EapDev E{};
@@ -1308,7 +1314,7 @@ static void destroy_impl(evpk_ctx *c) {
     if (c->relay) { c->relay->close_(); delete c->relay; }
     if (c->ipc) { if (c->stream2) (void)hipStreamSynchronize(c->stream2); c->ipc->close_(); delete c->ipc; }
     void *ptrs[] = {c->itd, c->stage_itd, c->d_zflags, c->d_zrows, c->s.F, c->s.tmask, c->s.umask, c->s.iceumask, c->s.cmask, c->s.tmphm, c->d_bd, c->stage, c->d_flags,
-                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_stage, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
+                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_stage, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->dyn_stage, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -3302,6 +3308,7 @@ extern "C" int evpk_transport_upwind_state(evpk_ctx *c, double dt, int32_t ncat,
         for (int m : {(int)u.m1[k], (int)u.m2[k], (int)u.d1[k], (int)u.d2[k]})
             if (m > ntrcr) FAIL(c, "evpk_transport_upwind_state: tracer %d hangs on tracer %d, beyond ntrcr", it, m);
     }
+    if (c->check_only) return 0;
     const size_t np = mask_elems(s), nblk = (size_t)c->nyb * c->nxb, nb = (size_t)c->nblocks;
     const int nq = 3 + ntrcr;
     // planes: one input plane, nq output planes of a category
@@ -3411,7 +3418,7 @@ extern "C" int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat
     if (t->nslyr < 0 || (t->nslyr > 0 && (t->nt_qsno < 1 || t->nt_qsno + t->nslyr - 1 > ntrcr))) FAIL(c, "evpk_ridge_ice: nt_qsno / nslyr beyond ntrcr");
     if (t->tr_pond_topo && (t->nt_apnd < 1 || t->nt_hpnd < 1)) FAIL(c, "evpk_ridge_ice: tr_pond_topo without nt_apnd / nt_hpnd");
     if (t->tr_pond_lvl && t->nt_apnd > 0 && t->nt_alvl < 1) FAIL(c, "evpk_ridge_ice: tr_pond_lvl without nt_alvl");
-    if (!c->nblocks) return 0;
+    if (!c->nblocks || c->check_only) return 0;
     Slab &s = c->s;
     HIPCHK(c, hipSetDevice(c->device));
     RidgeArgs A{};
@@ -3576,20 +3583,22 @@ static int itd_tables(evpk_ctx *c, const char *who, ItdArgs &A, int32_t ntrcr, c
 
 // the caller's arrays of one call: in place where the device sees them, else through a staging copy (up, and down again at the end)
 struct ItdArr { void *host; size_t bytes; void **slot; bool out; bool staged; };
-static int itd_stage_in(evpk_ctx *c, ItdArr *arr, int n) {
+static int itd_stage_in(evpk_ctx *c, ItdArr *arr, int n, double **pool_p = nullptr, size_t *pool_n_p = nullptr) {
+    double *&pool = pool_p ? *pool_p : c->rg_stage;
+    size_t &pool_n = pool_n_p ? *pool_n_p : c->rg_stage_n;
     size_t need = 0;
     for (int q = 0; q < n; q++) {
         *arr[q].slot = (arr[q].host && arr[q].bytes) ? mapped_alias(arr[q].host, arr[q].bytes) : nullptr;
         arr[q].staged = arr[q].host && arr[q].bytes && !*arr[q].slot;
         if (arr[q].staged) need += (arr[q].bytes + 7) / 8;
     }
-    if (c->rg_stage_n < need) {
-        if (c->rg_stage) (void)hipFree(c->rg_stage);
-        c->rg_stage = nullptr; c->rg_stage_n = 0;
-        HIPCHK(c, hipMalloc(&c->rg_stage, sizeof(double) * need));
-        c->rg_stage_n = need;
+    if (pool_n < need) {
+        if (pool) (void)hipFree(pool);
+        pool = nullptr; pool_n = 0;
+        HIPCHK(c, hipMalloc(&pool, sizeof(double) * need));
+        pool_n = need;
     }
-    double *q2 = c->rg_stage;
+    double *q2 = pool;
     for (int q = 0; q < n; q++)
         if (arr[q].staged) {
             HIPCHK(c, hipMemcpyAsync(q2, arr[q].host, arr[q].bytes, hipMemcpyHostToDevice, c->stream));
@@ -3627,7 +3636,7 @@ extern "C" int evpk_cleanup_itd(evpk_ctx *c, double dt, int32_t ncat, int32_t nt
     ItdArgs A{};
     if (itd_tables(c, "evpk_cleanup_itd", A, ntrcr, trcr_depend, t)) return 1;
     if (ntrcr > 0 && t->nt_Tsfc < 1) FAIL(c, "evpk_cleanup_itd: nt_Tsfc is required (zap_small_areas resets it)");
-    if (!c->nblocks) return 0;
+    if (!c->nblocks || c->check_only) return 0;
     Slab &s = c->s;
     HIPCHK(c, hipSetDevice(c->device));
     A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
@@ -3706,6 +3715,70 @@ static int itd_bound_state(evpk_ctx *c, const ItdArgs &A) {
     return 0;
 }
 
+// k_bound_state finds the block of a global cell as (column, row) of a uniform tiling: true of what create_blocks makes -- every block
+// starts at a multiple of the block size and is full except in the last column / row
+static int remap_block_map(evpk_ctx *c);
+static bool bound_direct_ok(evpk_ctx *c) {
+    if (!c->bs_uniform) {
+        const int bsx = c->nxb - 2, bsy = c->nyb - 2;
+        bool ok = c->nranks == 1 && c->s.i0 == 1 && c->s.j0 == 1 && c->s.nxl == c->s.nxg && c->s.nyl == c->s.nyg;
+        for (int b = 0; ok && b < c->nblocks; b++) {
+            const BlockDesc &d = c->bd[b];
+            const int ci = (d.iglob_lo - 1) / bsx, cj = (d.jglob_lo - 1) / bsy;
+            ok = d.iglob_lo == ci * bsx + 1 && d.jglob_lo == cj * bsy + 1 && d.ihi - d.ilo + 1 == std::min(bsx, c->s.nxg - ci * bsx) &&
+                 d.jhi - d.jlo + 1 == std::min(bsy, c->s.nyg - cj * bsy);
+        }
+        c->bs_uniform = ok ? 1 : -1;
+    }
+    return c->bs_uniform > 0;
+}
+
+// bound_state in one launch, block array to block array (k_bound_state, evpk_itd.hip): the same cells get the same values as above
+static int itd_bound_direct(evpk_ctx *c, const ItdArgs &A) {
+    if (remap_block_map(c)) return 1;            // (uploaded once per context: it depends on the decomposition only)
+    const size_t nn = (size_t)c->nyb * c->nxb;
+    BsArgs B{};
+    B.aicen = {A.aicen, (size_t)A.ncat * nn}; B.trcrn = {A.trcrn, (size_t)A.ncat * A.ntrcr_dim * nn};
+    B.vicen = {A.vicen, (size_t)A.ncat * nn}; B.vsnon = {A.vsnon, (size_t)A.ncat * nn};
+    B.ncat = A.ncat; B.ntrcr = A.ntrcr; B.ntrcr_dim = A.ntrcr_dim; B.nxb = c->nxb; B.nyb = c->nyb; B.nplanes = A.ncat * (3 + A.ntrcr);
+    B.nxg = c->s.nxg; B.nyg = c->s.nyg; B.bsx = c->nxb - 2; B.bsy = c->nyb - 2; B.nbx = c->bmap_nbx;
+    B.cyclic = c->ew == EVPK_BND_CYCLIC ? 1 : 0; B.tripole = c->ns == EVPK_BND_TRIPOLE ? 1 : 0;
+    if (c->nblocks > 65535) FAIL(c, "evpk_bound_state: %d blocks exceed one launch", c->nblocks);
+    const dim3 g((4 * (c->nxb + c->nyb) + BS_TX - 1) / BS_TX, c->nblocks, (B.nplanes + BS_PG - 1) / BS_PG);
+    LAUNCH_BLOCKS(k_bound_state, g, dim3(BS_TX), 0, c->stream, (const BlockDesc *)c->d_bd, (const int *)c->d_bmap, B);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// EVPK_BOUND_DIRECT=0 (read per call): the plane-by-plane path, the A/B partner and the pinned definition
+static bool bound_direct_env() { return !(getenv("EVPK_BOUND_DIRECT") && atoi(getenv("EVPK_BOUND_DIRECT")) == 0); }
+
+extern "C" int evpk_bound_state(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, double *aicen, double *vicen, double *vsnon,
+                                double *trcrn) {
+    if (!c) return 1;
+    if (c->nranks > 1) FAIL(c, "evpk_bound_state: nranks = %d: more than one rank is not supported yet", c->nranks);
+    if (!aicen || !vicen || !vsnon || ntrcr < 0 || ntrcr_dim < ntrcr || (ntrcr > 0 && !trcrn)) FAIL(c, "evpk_bound_state: a required argument is missing");
+    if (!c->connected) FAIL(c, "evpk_bound_state: the context is not connected yet (evpk_connect)");
+    if (ncat < 1 || ncat > MAXCAT) FAIL(c, "evpk_bound_state: ncat = %d not in 1..%d", ncat, MAXCAT);
+    if (ntrcr > RG_MAXT) FAIL(c, "evpk_bound_state: ntrcr = %d exceeds %d", ntrcr, RG_MAXT);
+    if (!c->nblocks) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool direct = bound_direct_env();
+    if (direct && !bound_direct_ok(c)) FAIL(c, "evpk_bound_state: the blocks are not the uniform tiling of create_blocks (EVPK_BOUND_DIRECT=0 takes the plane-by-plane path)");
+    ItdArgs A{};
+    A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, d8 = sizeof(double);
+    ItdArr arr[] = {
+        {aicen, N * ncat * d8, (void **)&A.aicen, true}, {vicen, N * ncat * d8, (void **)&A.vicen, true}, {vsnon, N * ncat * d8, (void **)&A.vsnon, true},
+        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim * d8, (void **)&A.trcrn, true}};
+    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
+    if (itd_stage_in(c, arr, NARR)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    if (direct ? itd_bound_direct(c, A) : itd_bound_state(c, A)) return 1;
+    if (itd_stage_out(c, arr, NARR)) return 1;
+    return xp_check(c);
+}
+
 extern "C" int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
                               const evpk_itd_tracers *t, int32_t nt_iage, double Tocnfrz, double *aicen, double *vicen, double *vsnon, double *trcrn,
                               double *aice, double *vice, double *vsno, double *aice0, double *trcr, double *daidtd, double *dvidtd,
@@ -3723,7 +3796,7 @@ extern "C" int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t nca
     if (nt_iage < 0 || nt_iage > ntrcr) FAIL(c, "evpk_aggregate: nt_iage = %d not in 0..ntrcr = %d", nt_iage, ntrcr);
     ItdArgs A{};
     if (itd_tables(c, "evpk_aggregate", A, ntrcr, trcr_depend, t)) return 1;
-    if (!c->nblocks) return 0;
+    if (!c->nblocks || c->check_only) return 0;
     Slab &s = c->s;
     HIPCHK(c, hipSetDevice(c->device));
     A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nt_iage = nt_iage;
@@ -3739,7 +3812,7 @@ extern "C" int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t nca
     constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
     if (itd_stage_in(c, arr, NARR)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
-    if (bnd && itd_bound_state(c, A)) return 1;
+    if (bnd && ((bound_direct_env() && bound_direct_ok(c)) ? itd_bound_direct(c, A) : itd_bound_state(c, A))) return 1;
     const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
     if (ncat == 5) hipLaunchKernelGGL(k_itd_aggregate<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
     else hipLaunchKernelGGL(k_itd_aggregate<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
@@ -3856,6 +3929,7 @@ static int remap_impl(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, doub
         }
         if (m != ntrace) FAIL(c, "evpk_transport_remap: the tracer dependencies do not form a forest (%d of %d reached)", m, ntrace);
     }
+    if (c->check_only) return 0;
     Slab &s = c->s;
     HIPCHK(c, hipSetDevice(c->device));
     const int ncp = ncat + 1, ntp = ncat * ntrace;
@@ -4057,6 +4131,100 @@ extern "C" int evpk_transport_remap_state(evpk_ctx *c, double dt, int32_t ncat, 
     st.aice0 = aice0; st.aicen = aicen; st.vicen = vicen; st.vsnon = vsnon; st.trcrn = trcrn;
     st.ncat = ncat; st.ntrcr = ntrcr; st.ntrcr_dim = ntrcr_dim; st.nt_qsno = nt_qsno; st.nslyr = nslyr; st.shift = rhos_lfresh;
     return remap_impl(c, dt, ncat, 2 + ntrcr, nullptr, nullptr, tracer_type, depend, has_dependents, integral_order, l_dp_midpt, 0, &st);
+}
+
+// ---- step_dynamics behind evp / eap (source/ice_step_mod.F90:1126-1192) in one call ----
+// the four entry points in the reference's order on the arrays of x; a stop fills stop[0] with the stage and stop[1..4] with its numbers
+static int dyn_stages(evpk_ctx *c, const evpk_dyn_args &x, evpk_ridge_diag *dg, int32_t stop[5]) {
+    const evpk_itd_tracers &t = x.t;
+    int32_t s4[4] = {0, 0, 0, 0};
+    int rc = 0;
+    if (x.advection == 1)
+        rc = evpk_transport_upwind_state(c, x.dt, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, t.nt_Tsfc, t.nt_alvl, t.nt_apnd, t.nt_fbri, t.tr_pond_cesm,
+                                         t.tr_pond_lvl, t.tr_pond_topo, x.k.Tocnfrz, x.aice0, x.aicen, x.vicen, x.vsnon, x.trcrn);
+    else if (x.advection == 2)
+        rc = evpk_transport_remap_state(c, x.dt, x.ncat, x.ntrcr, x.ntrcr_dim, t.nt_qsno, t.nslyr, x.rhos_lfresh, x.aice0, x.aicen, x.vicen, x.vsnon,
+                                        x.trcrn, x.tracer_type, x.depend, x.has_dependents, x.integral_order, x.l_dp_midpt);
+    if (rc) {
+        if (rc == EVPK_REMAP_BAD_DEPARTURE || rc == EVPK_REMAP_NEGATIVE_MASS) stop[0] = 1;
+        return rc;
+    }
+    if (x.ridge) {
+        const evpk_ridge_tracers rt{t.nt_qsno, t.nslyr, t.nt_alvl, x.nt_vlvl, t.nt_apnd, t.nt_hpnd, t.nt_fbri, t.tr_pond_cesm, t.tr_pond_lvl, t.tr_pond_topo};
+        rc = evpk_ridge_ice(c, x.dt, x.ndtd, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, &rt, x.hin_max, x.rdg_conv, x.rdg_shear, x.aice0, x.aicen,
+                            x.vicen, x.vsnon, x.trcrn, dg, s4);
+        if (rc) {
+            if (rc == EVPK_RIDGE_STOP) { stop[0] = 2; for (int q = 0; q < 4; q++) stop[1 + q] = s4[q]; }
+            return rc;
+        }
+    }
+    rc = evpk_cleanup_itd(c, x.dt * x.ndtd, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, &t, x.hin_max, &x.k, x.tr_aero, x.nbtrcr, x.heat_capacity,
+                          x.aicen, x.vicen, x.vsnon, x.trcrn, x.aice0, x.aice, x.fpond, x.fresh, x.fsalt, x.fhocn, x.first_ice, s4);
+    if (rc) {
+        if (rc == EVPK_ITD_STOP) { stop[0] = 3; for (int q = 0; q < 4; q++) stop[1 + q] = s4[q]; }
+        return rc;
+    }
+    return evpk_aggregate(c, x.dt, 1, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, &t, x.nt_iage, x.k.Tocnfrz, x.aicen, x.vicen, x.vsnon, x.trcrn,
+                          x.aice, x.vice, x.vsno, x.aice0, x.trcr, x.daidtd, x.dvidtd, x.dagedtd);
+}
+
+extern "C" int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t stop[5]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
+    if (c->nranks > 1) FAIL(c, "evpk_step_dynamics: nranks = %d: more than one rank is not supported yet", c->nranks);
+    if (!a || !stop) FAIL(c, "evpk_step_dynamics: a required argument is missing");
+    if (a->advection < 0 || a->advection > 2) FAIL(c, "evpk_step_dynamics: advection = %d not in 0..2", a->advection);
+    if (a->ridge != 0 && a->ridge != 1) FAIL(c, "evpk_step_dynamics: ridge = %d", a->ridge);
+    if (!a->hin_max || !a->aice0 || !a->aicen || !a->vicen || !a->vsnon || !a->aice || !a->vice || !a->vsno || a->ntrcr < 0 || a->ntrcr_dim < a->ntrcr ||
+        (a->ntrcr > 0 && (!a->trcrn || !a->trcr || !a->trcr_depend)))
+        FAIL(c, "evpk_step_dynamics: a required argument is missing");
+    if (!(a->dt > 0.0) || a->ndtd < 1) FAIL(c, "evpk_step_dynamics: dt = %g, ndtd = %d", a->dt, a->ndtd);
+    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "evpk_step_dynamics: ncat = %d not in 1..%d", a->ncat, MAXCAT);
+    if (!c->connected) FAIL(c, "evpk_step_dynamics: the context is not connected yet (evpk_connect)");
+    evpk_ridge_diag dg{};
+    if (a->diag) dg = *a->diag;
+    dg.fpond = a->fpond; dg.fresh = a->fresh; dg.fhocn = a->fhocn;
+    // what the stages refuse, before the first copy: each of them with the caller's own pointers, returning after its checks
+    {
+        int32_t s5[5] = {0, 0, 0, 0, 0};
+        c->check_only = true;
+        const int rc = dyn_stages(c, *a, &dg, s5);
+        c->check_only = false;
+        if (rc) return rc;
+    }
+    if (!c->nblocks) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the union of the caller's arrays, each staged once (or used in place): the stages then see device pointers only
+    evpk_dyn_args x = *a;
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, d8 = sizeof(double), n3 = N * a->ncat * d8;
+    const bool tr = a->ntrcr > 0;
+    ItdArr arr[] = {
+        {a->aice0, N * d8, (void **)&x.aice0, true}, {a->aicen, n3, (void **)&x.aicen, true}, {a->vicen, n3, (void **)&x.vicen, true},
+        {a->vsnon, n3, (void **)&x.vsnon, true}, {tr ? a->trcrn : nullptr, n3 * a->ntrcr_dim, (void **)&x.trcrn, true},
+        {a->aice, N * d8, (void **)&x.aice, true}, {a->vice, N * d8, (void **)&x.vice, true}, {a->vsno, N * d8, (void **)&x.vsno, true},
+        {tr ? a->trcr : nullptr, N * a->ntrcr_dim * d8, (void **)&x.trcr, true},
+        {a->daidtd, N * d8, (void **)&x.daidtd, true}, {a->dvidtd, N * d8, (void **)&x.dvidtd, true}, {a->dagedtd, N * d8, (void **)&x.dagedtd, true},
+        {a->fpond, N * d8, (void **)&x.fpond, true}, {a->fresh, N * d8, (void **)&x.fresh, true}, {a->fsalt, N * d8, (void **)&x.fsalt, true},
+        {a->fhocn, N * d8, (void **)&x.fhocn, true}, {a->first_ice, N * a->ncat * sizeof(int32_t), (void **)&x.first_ice, true},
+        {a->ridge ? const_cast<double *>(a->rdg_conv) : nullptr, N * d8, (void **)&x.rdg_conv, false},
+        {a->ridge ? const_cast<double *>(a->rdg_shear) : nullptr, N * d8, (void **)&x.rdg_shear, false},
+        {dg.dardg1dt, N * d8, (void **)&dg.dardg1dt, true}, {dg.dardg2dt, N * d8, (void **)&dg.dardg2dt, true}, {dg.dvirdgdt, N * d8, (void **)&dg.dvirdgdt, true},
+        {dg.opening, N * d8, (void **)&dg.opening, true}, {dg.dardg1ndt, n3, (void **)&dg.dardg1ndt, true}, {dg.dardg2ndt, n3, (void **)&dg.dardg2ndt, true},
+        {dg.dvirdgndt, n3, (void **)&dg.dvirdgndt, true}, {dg.aparticn, n3, (void **)&dg.aparticn, true}, {dg.krdgn, n3, (void **)&dg.krdgn, true},
+        {dg.araftn, n3, (void **)&dg.araftn, true}, {dg.vraftn, n3, (void **)&dg.vraftn, true}, {dg.aredistn, n3, (void **)&dg.aredistn, true},
+        {dg.vredistn, n3, (void **)&dg.vredistn, true}};
+    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
+    if (!a->ridge)          // (the diagnostics belong to ridge_ice alone)
+        for (int q = 19; q < NARR; q++) arr[q].host = nullptr;
+    if (itd_stage_in(c, arr, NARR, &c->dyn_stage, &c->dyn_stage_n)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    dg.fpond = x.fpond; dg.fresh = x.fresh; dg.fhocn = x.fhocn;
+    const int rc = dyn_stages(c, x, &dg, stop);
+    if (rc == 1) return 1;
+    const std::string keep = c->err;
+    if (itd_stage_out(c, arr, NARR)) return 1;
+    if (rc) c->err = keep;
+    return rc;
 }
 
 extern "C" int evpk_calibrate(evpk_ctx *c, int32_t nrep) {

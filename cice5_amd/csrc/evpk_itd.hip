@@ -471,4 +471,87 @@ __global__ void __launch_bounds__(64) k_itd_aggregate(Slab s, const BlockDesc *b
 template __global__ void __launch_bounds__(64) k_itd_aggregate<0>(Slab, const BlockDesc *, ItdArgs);
 template __global__ void __launch_bounds__(64) k_itd_aggregate<5>(Slab, const BlockDesc *, ItdArgs);
 
+// ---- bound_state (ice_state.F90:173-238) in one launch, block array to block array ----
+// What k_gather_fs -> halo(centre, scalar, fill 0) -> k_scatter_halo leave in the caller's aicen, trcrn(1:ntrcr), vicen, vsnon, without
+// the slab in between.  Only the non-physical cells of a block can change, and of those only the ring around the physical cells and the
+// outermost row / column of the array: a thread takes one such cell of one block, classifies it once -- keep, fill, or copy from a
+// physical cell of another (or the same) block, found through the E-W wrap resp. the fold onto row ny_global and the block table -- and
+// then moves a group of BS_PG planes, loads ahead of stores.
+// In place in a single launch: a source is always a PHYSICAL cell and a destination never is, so no thread reads what another writes.
+// One rank only (the slab is the whole domain, global index = slab index); blocks are uniform (create_blocks), which the host verifies.
+constexpr int BS_PG = 8;            // planes per thread: 75 planes of a 5 x 12 state make 10 groups
+constexpr int BS_TX = 128;
+struct BsArr { double *base; size_t bstride; };          // blocks `bstride` doubles apart
+struct BsArgs {
+    BsArr aicen, trcrn, vicen, vsnon;                    // planes per block: ncat, ncat * ntrcr_dim, ncat, ncat
+    int ncat, ntrcr, ntrcr_dim, nxb, nyb, nplanes;       // nplanes = ncat * (3 + ntrcr)
+    int nxg, nyg, bsx, bsy, nbx;                         // bmap[((gj - 1) / bsy) * nbx + (gi - 1) / bsx]: the block of a global cell, -1 eliminated
+    int cyclic, tripole;
+};
+
+__global__ void __launch_bounds__(BS_TX) k_bound_state(const BlockDesc *bd, const int *bmap, BsArgs A) {
+    const int t = blockIdx.x * BS_TX + threadIdx.x, b = blockIdx.y;
+    const int nxb = A.nxb, nyb = A.nyb;
+    const BlockDesc d = bd[b];
+    // the candidate cells: four rows (array bottom, array top, above and below the physical cells) over all columns, then four columns
+    // over the rows those four have not taken; a row / column that coincides with the array's edge is listed once
+    int i, j;
+    if (t < 4 * nxb) {
+        const int r = t / nxb;
+        i = t - r * nxb + 1;
+        j = r == 0 ? 1 : r == 1 ? nyb : r == 2 ? d.jhi + 1 : d.jlo - 1;
+        if (r >= 2 && (j <= 1 || j >= nyb)) return;
+    } else {
+        const int u = t - 4 * nxb;
+        if (u >= 4 * nyb) return;
+        const int r = u / nyb;
+        j = u - r * nyb + 1;
+        i = r == 0 ? 1 : r == 1 ? nxb : r == 2 ? d.ihi + 1 : d.ilo - 1;
+        if (r >= 2 && (i <= 1 || i >= nxb)) return;
+        if (j == 1 || j == nyb || j == d.jhi + 1 || j == d.jlo - 1) return;
+    }
+    if (i >= d.ilo && i <= d.ihi && j >= d.jlo && j <= d.jhi) return;          // physical cells are never written
+    // k_scatter_halo's classification (top_row_too = 0, stress = 0)
+    const bool edge = (i == 1 || i == nxb || j == 1 || j == nyb);
+    const bool padding = (i > d.ihi + 1 || j > d.jhi + 1);
+    const int gi = d.iglob_lo + (i - d.ilo), gj = d.jglob_lo + (j - d.jlo);
+    const bool has_src = !padding && ((gi >= 1 && gi <= A.nxg) || A.cyclic) && ((gj >= 1 && gj <= A.nyg) || (A.tripole && gj == A.nyg + 1));
+    if (!has_src && !edge) return;                                              // keeps the caller's value
+    const size_t nn = (size_t)nyb * nxb;
+    const size_t dcell = (size_t)(j - 1) * nxb + (i - 1);
+    int sb = -1;
+    size_t scell = 0;
+    if (has_src) {
+        int si = gi, sj = gj;
+        if (si < 1) si += A.nxg;
+        if (si > A.nxg) si -= A.nxg;
+        if (sj == A.nyg + 1) { si = A.nxg - si + 1; sj = A.nyg; }              // centre fold: ghost(g, ny + 1) = top(nx - g + 1, ny)
+        sb = bmap[((sj - 1) / A.bsy) * A.nbx + (si - 1) / A.bsx];
+        if (sb >= 0) {
+            const BlockDesc e = bd[sb];
+            scell = (size_t)(e.jlo + (sj - e.jglob_lo) - 1) * nxb + (e.ilo + (si - e.iglob_lo) - 1);
+        }
+    }
+    const int p0 = blockIdx.z * BS_PG;
+    const int c1 = A.ncat, c2 = c1 + A.ncat * A.ntrcr, c3 = c2 + A.ncat;
+    double v[BS_PG];
+    double *dst[BS_PG];
+#pragma unroll
+    for (int q = 0; q < BS_PG; q++) {
+        const int p = p0 + q;
+        v[q] = 0.0; dst[q] = nullptr;
+        if (p < A.nplanes) {
+            const BsArr a = p < c1 ? A.aicen : p < c2 ? A.trcrn : p < c3 ? A.vicen : A.vsnon;
+            int pp;
+            if (p < c1) pp = p;
+            else if (p < c2) { const int r = p - c1, n = r / A.ntrcr; pp = n * A.ntrcr_dim + (r - n * A.ntrcr); }
+            else pp = p < c3 ? p - c2 : p - c3;
+            dst[q] = a.base + (size_t)b * a.bstride + (size_t)pp * nn + dcell;
+            if (sb >= 0) v[q] = a.base[(size_t)sb * a.bstride + (size_t)pp * nn + scell];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < BS_PG; q++) if (dst[q]) *dst[q] = v[q];
+}
+
 }  // namespace evpk

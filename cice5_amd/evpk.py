@@ -96,7 +96,7 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_transport_upwind", "evpk_remap_init", "evpk_transport_remap", "evpk_transport_remap_state",
            "evpk_eap_init", "evpk_eap_upload", "evpk_eap_download", "evpk_halo_update", "evpk_halo_update_stress",
            "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
-           "evpk_cleanup_itd", "evpk_aggregate"]
+           "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -128,6 +128,43 @@ class ItdTracers(ct.Structure):
 
 class ItdConstants(ct.Structure):
     _fields_ = [(n, ct.c_double) for n in ITD_CONSTANT_FIELDS]
+
+
+class DynArgs(ct.Structure):
+    """evpk_dyn_args (include/evpk.h), member for member"""
+    _fields_ = ([("advection", ct.c_int32), ("ridge", ct.c_int32), ("dt", ct.c_double), ("ndtd", ct.c_int32),
+                 ("ncat", ct.c_int32), ("ntrcr", ct.c_int32), ("ntrcr_dim", ct.c_int32), ("trcr_depend", c_i32p),
+                 ("t", ItdTracers), ("nt_vlvl", ct.c_int32), ("nt_iage", ct.c_int32),
+                 ("hin_max", c_f64p), ("k", ItdConstants),
+                 ("tr_aero", ct.c_int32), ("nbtrcr", ct.c_int32), ("heat_capacity", ct.c_int32),
+                 ("tracer_type", c_i32p), ("depend", c_i32p), ("has_dependents", c_i32p),
+                 ("integral_order", ct.c_int32), ("l_dp_midpt", ct.c_int32), ("rhos_lfresh", ct.c_double)] +
+                [(n, c_f64p) for n in ("aice0", "aicen", "vicen", "vsnon", "trcrn", "aice", "vice", "vsno", "trcr", "daidtd", "dvidtd", "dagedtd",
+                                       "fpond", "fresh", "fsalt", "fhocn")] +
+                [("first_ice", c_i32p), ("rdg_conv", c_f64p), ("rdg_shear", c_f64p), ("diag", ct.POINTER(RidgeDiag))])
+
+
+DYN_STAGES = {1: "transport", 2: "ridge_ice", 3: "cleanup_itd"}
+
+
+def remap_tracer_tables(trcr_depend):
+    """tracer_type, depend, has_dependents of transport_remap as init_transport builds them from trcr_depend
+    (ice_transport_driver.F90:90-118): hice and hsno first (type 1, no parent); a tracer of the area is type 1, one that hangs on a
+    tracer that itself hangs on ice or snow volume is type 3, every other type 2; depend is trcr_depend itself (2 + the parent's
+    tracer index is its position behind hice, hsno)."""
+    dep = [int(d) for d in trcr_depend]
+    depend = [0, 0] + dep
+    ttype = [1, 1]
+    for d in dep:
+        ttype.append(1 if d == 0 else (3 if d > 2 and dep[d - 3] > 0 else 2))
+    has = [0] * len(depend)
+    for nt, d in enumerate(depend):
+        if d > 0:
+            if d > nt + 1:
+                raise EvpkError(f"remap transport: tracer {nt + 1} depends on tracer {d}: must have nt2 > nt1")
+            has[d - 1] = 1
+    return (np.array(ttype, dtype=np.int32), np.array(depend, dtype=np.int32), np.array(has, dtype=np.int32))
+
 
 _lib = None
 
@@ -187,6 +224,8 @@ def lib():
                                        [ct.c_int32] * 3 + [c_f64p] * 10 + [c_i32p, c_i32p])
         L.evpk_aggregate.argtypes = ([ctxp, ct.c_double] + [ct.c_int32] * 4 + [c_i32p, ct.POINTER(ItdTracers), ct.c_int32, ct.c_double] +
                                      [c_f64p] * 12)
+        L.evpk_bound_state.argtypes = [ctxp] + [ct.c_int32] * 3 + [c_f64p] * 4
+        L.evpk_step_dynamics.argtypes = [ctxp, ct.POINTER(DynArgs), c_i32p]
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -333,7 +372,9 @@ class Context:
 
     def _chk(self, rc, what):
         if rc:
-            raise EvpkError(f"{what}: " + self._L.evpk_last_error(self._ctx).decode())
+            e = EvpkError(f"{what}: " + self._L.evpk_last_error(self._ctx).decode())
+            e.rc = int(rc)
+            raise e
 
     def connect(self, unique_id: bytes):
         """evpk_connect: the collective half of the start (communicator / peer mapping)."""
@@ -528,6 +569,69 @@ class Context:
                                     _p64(vsnon), _p64(trcrn), _p64(aice), _p64(vice), _p64(vsno), _p64(aice0), _p64(trcr), _p64(daidtd),
                                     _p64(dvidtd), _p64(dagedtd))
         self._chk(rc, "evpk_aggregate")
+
+    def bound_state(self, aicen, vicen, vsnon, trcrn, ntrcr: int):
+        """evpk_bound_state (bound_state, ice_state.F90:173-238): the ghost cells of aicen / vicen / vsnon (nb, ncat, ny, nx) and of tracers
+        1 .. ntrcr of trcrn (nb, ncat, ntrcr_dim, ny, nx; None when ntrcr == 0) in place, one launch"""
+        ntrcr_dim = int(trcrn.shape[2]) if trcrn is not None else 0
+        self._chk(self._L.evpk_bound_state(self._ctx, int(aicen.shape[1]), int(ntrcr), ntrcr_dim, _p64(aicen), _p64(vicen), _p64(vsnon),
+                                           _p64(trcrn)), "evpk_bound_state")
+
+    def step_dynamics(self, dt: float, ndtd: int, aice0, aicen, vicen, vsnon, trcrn, aice, vice, vsno, trcr, ntrcr: int, trcr_depend, tracers,
+                      hin_max, advection=0, ridge=True, constants=None, fluxes=None, first_ice=None, daidtd=None, dvidtd=None, dagedtd=None,
+                      rdg_conv=None, rdg_shear=None, diag=None, tracer_type=None, depend=None, has_dependents=None, integral_order=3,
+                      l_dp_midpt=True, rhos_lfresh=None, tr_aero=False, nbtrcr=0, heat_capacity=True):
+        """evpk_step_dynamics: everything of step_dynamics behind evp / eap in one call, the arrays staged once -- advection (0 none, 1
+        transport_upwind, 2 transport_remap; also 'none' / 'upwind' / 'remap'), ridge_ice (ridge), cleanup_itd(dt * ndtd),
+        bound_state and aggregate with the tendencies.  Arrays and keywords as for ridge_ice / cleanup_itd / aggregate; tracers: dict of
+        ITD_TRACER_FIELDS plus nt_vlvl, nt_iage; tracer_type / depend / has_dependents default to remap_tracer_tables(trcr_depend),
+        rhos_lfresh to rhos * Lfresh of cice5_amd.constants.
+        Returns None, or (code, stage, reason, block, i, j) when a stage stops (code: REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS,
+        RIDGE_STOP, ITD_STOP; stage: DYN_STAGES); raises on a refusal, which leaves every array untouched."""
+        from . import constants as C
+        adv = {"none": 0, "upwind": 1, "remap": 2}.get(advection, advection)
+        a = DynArgs()
+        a.advection, a.ridge, a.dt, a.ndtd = int(adv), int(ridge), float(dt), int(ndtd)
+        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
+        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
+        dep = np.ascontiguousarray(trcr_depend, dtype=np.int32)
+        a.trcr_depend = _p32(dep) if ntrcr else None
+        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        a.nt_vlvl, a.nt_iage = int(tracers.get("nt_vlvl", 0)), int(tracers.get("nt_iage", 0))
+        hin = np.ascontiguousarray(hin_max, dtype=np.float64)
+        assert hin.shape == (a.ncat + 1,) or aicen is None
+        a.hin_max = _p64(hin)
+        a.k = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
+        a.tr_aero, a.nbtrcr, a.heat_capacity = int(bool(tr_aero)), int(nbtrcr), int(bool(heat_capacity))
+        keep = [dep, hin]
+        if adv == 2:
+            if tracer_type is None:
+                tracer_type, depend, has_dependents = remap_tracer_tables(dep[:int(ntrcr)])
+            tt, dp, hd = (np.ascontiguousarray(v, dtype=np.int32) for v in (tracer_type, depend, has_dependents))
+            keep += [tt, dp, hd]
+            a.tracer_type, a.depend, a.has_dependents = _p32(tt), _p32(dp), _p32(hd)
+        a.integral_order, a.l_dp_midpt = int(integral_order), int(bool(l_dp_midpt))
+        a.rhos_lfresh = float(C.rhos * C.Lfresh if rhos_lfresh is None else rhos_lfresh)
+        fl = fluxes or {}
+        for n, v in (("aice0", aice0), ("aicen", aicen), ("vicen", vicen), ("vsnon", vsnon), ("trcrn", trcrn), ("aice", aice), ("vice", vice),
+                     ("vsno", vsno), ("trcr", trcr), ("daidtd", daidtd), ("dvidtd", dvidtd), ("dagedtd", dagedtd), ("fpond", fl.get("fpond")),
+                     ("fresh", fl.get("fresh")), ("fsalt", fl.get("fsalt")), ("fhocn", fl.get("fhocn")), ("rdg_conv", rdg_conv),
+                     ("rdg_shear", rdg_shear)):
+            setattr(a, n, _p64(v))
+        a.first_ice = _p32(first_ice)
+        rd = None
+        if diag is not None:
+            rd = RidgeDiag()
+            for k in RIDGE_DIAG_2D + RIDGE_DIAG_3D:
+                setattr(rd, k, _p64(diag.get(k)))
+            a.diag = ct.pointer(rd)
+        stop = np.zeros(5, dtype=np.int32)
+        rc = self._L.evpk_step_dynamics(self._ctx, ct.byref(a), _p32(stop))
+        del keep
+        if rc in (REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS, RIDGE_STOP, ITD_STOP):
+            return (int(rc),) + tuple(int(v) for v in stop)
+        self._chk(rc, "evpk_step_dynamics")
+        return None
 
     def eap_init(self, tables):
         """evpk_eap_init: the six lookup tables of init_eap, each [na_yield][ny_yield][nx_yield]; the context then runs eap(dt)"""

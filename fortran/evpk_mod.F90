@@ -121,6 +121,30 @@
          real (c_double) :: Tocnfrz, ice_ref_salinity, hs_min, cp_ice, Lfresh, Tmin, puny
       end type evpk_itd_constants
 
+      ! evpk_dyn_args (include/evpk.h): the arguments of evpk_step_dynamics, one struct of borrowed pointers, member for member
+      type, bind(C) :: evpk_dyn_args
+         integer (c_int32_t) :: advection = 0           ! 0 none, 1 transport_upwind, 2 transport_remap
+         integer (c_int32_t) :: ridge = 1
+         real (c_double) :: dt
+         integer (c_int32_t) :: ndtd = 1
+         integer (c_int32_t) :: ncat, ntrcr, ntrcr_dim
+         type (c_ptr) :: trcr_depend = c_null_ptr
+         type (evpk_itd_tracers) :: t
+         integer (c_int32_t) :: nt_vlvl = 0, nt_iage = 0
+         type (c_ptr) :: hin_max = c_null_ptr
+         type (evpk_itd_constants) :: k
+         integer (c_int32_t) :: tr_aero = 0, nbtrcr = 0, heat_capacity = 1
+         type (c_ptr) :: tracer_type = c_null_ptr, depend = c_null_ptr, has_dependents = c_null_ptr
+         integer (c_int32_t) :: integral_order = 3, l_dp_midpt = 1
+         real (c_double) :: rhos_lfresh
+         type (c_ptr) :: aice0 = c_null_ptr, aicen = c_null_ptr, vicen = c_null_ptr, vsnon = c_null_ptr, trcrn = c_null_ptr
+         type (c_ptr) :: aice = c_null_ptr, vice = c_null_ptr, vsno = c_null_ptr, trcr = c_null_ptr
+         type (c_ptr) :: daidtd = c_null_ptr, dvidtd = c_null_ptr, dagedtd = c_null_ptr
+         type (c_ptr) :: fpond = c_null_ptr, fresh = c_null_ptr, fsalt = c_null_ptr, fhocn = c_null_ptr, first_ice = c_null_ptr
+         type (c_ptr) :: rdg_conv = c_null_ptr, rdg_shear = c_null_ptr
+         type (c_ptr) :: diag = c_null_ptr              ! c_loc of an evpk_ridge_diag, or c_null_ptr
+      end type evpk_dyn_args
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -131,7 +155,8 @@
                 EVPK_REMAP_BAD_DEPARTURE, EVPK_REMAP_NEGATIVE_MASS, &
                 evpk_eap_state, evpk_eap_init, evpk_eap_upload, evpk_eap_download, &
                 evpk_ridge_tracers, evpk_ridge_diag, evpk_ridge_ice, EVPK_RIDGE_STOP, &
-                evpk_itd_tracers, evpk_itd_constants, evpk_cleanup_itd, evpk_aggregate, EVPK_ITD_STOP
+                evpk_itd_tracers, evpk_itd_constants, evpk_cleanup_itd, evpk_aggregate, EVPK_ITD_STOP, &
+                evpk_dyn_args, evpk_bound_state, evpk_step_dynamics
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
@@ -304,6 +329,20 @@
             real (c_double), value :: dt, Tocnfrz
             integer (c_int32_t), value :: bound, ncat, ntrcr, ntrcr_dim, nt_iage
             type (evpk_itd_tracers), intent(in) :: t
+         end function
+         ! bound_state (ice_state.F90:173-238) alone, one launch between the block arrays; trcrn may be c_null_ptr when ntrcr = 0
+         integer (c_int) function evpk_bound_state (ctx, ncat, ntrcr, ntrcr_dim, aicen, vicen, vsnon, trcrn) bind(C, name='evpk_bound_state')
+            import :: c_int, c_ptr, c_int32_t
+            type (c_ptr), value :: ctx, aicen, vicen, vsnon, trcrn
+            integer (c_int32_t), value :: ncat, ntrcr, ntrcr_dim
+         end function
+         ! everything of step_dynamics behind evp / eap (ice_step_mod.F90:1126-1192) in one call, the arrays staged once;
+         ! stop(5): stage (1 transport, 2 ridge, 3 cleanup), reason, block, i, j
+         integer (c_int) function evpk_step_dynamics (ctx, a, stop) bind(C, name='evpk_step_dynamics')
+            import :: c_int, c_ptr, c_int32_t, evpk_dyn_args
+            type (c_ptr), value :: ctx
+            type (evpk_dyn_args), intent(in) :: a
+            integer (c_int32_t), intent(out) :: stop(5)
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then
          ! mm(nx_block,ny_block,0:ncat,max_blocks), tm(nx_block,ny_block,ntrace,ncat,max_blocks) advanced in place

@@ -42,6 +42,7 @@
       public :: evpk_bound_seconds, evpk_loop_seconds
       public :: evpk_download_all, evpk_sparse_io
       public :: evpk_horizontal_remap, evpk_eap, evpk_transport_remap_core
+      public :: evpk_context      ! the libevpk context of this rank, for the modules that call the library beside this one (ice_step_dyn)
       save
 
       ! .true. (default): every array the reference's evp leaves modified comes back every call.  .false. (with
@@ -193,6 +194,11 @@
 ! The reference declares its module arrays without TARGET (ice_state.F90, ice_flux.F90, ice_grid.F90), so C_LOC cannot be
 ! applied to them directly.  Passed to an assumed-size TARGET dummy (sequence association: a contiguous whole array is
 ! passed by address, no copy) their address can be taken; the arrays live as long as the run.
+
+      ! c_null_ptr until the first evp (the context is created there)
+      type (c_ptr) function evpk_context ()
+      evpk_context = ctx
+      end function evpk_context
 
       type (c_ptr) function loc_r8 (a)
       real (kind=dbl_kind), dimension (*), intent(in), target :: a

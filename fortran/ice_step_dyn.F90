@@ -1,0 +1,182 @@
+!=======================================================================
+! Everything of step_dynamics behind evp / eap on the device, in one library call.
+!
+! In the reference's step_dynamics (source/ice_step_mod.F90) the lines from the transport call through the tendency loop
+! (:1126-1192: transport_upwind | transport_remap, the step_ridge loop, bound_state, aggregate, daidtd / dvidtd / dagedtd)
+! become
+!     use ice_step_dyn, only: evpk_step_dynamics_core
+!     call evpk_step_dynamics_core (dt, ndtd)
+! It runs over the reference's own module arrays (ice_state, ice_flux, ice_itd, ice_zbgc_shared) and stages each of them once:
+! the four separate entry points would copy the category state up and down once each.  This module only marshals arguments;
+! what the call computes is evpk_step_dynamics (include/evpk.h).
+!
+! ice_transport_driver keeps tracer_type, depend and has_dependents private, so they are rebuilt here from trcr_depend by the
+! rule of init_transport (ice_transport_driver.F90:90-118).  integral_order and l_dp_midpt are private there too: optional
+! arguments with the reference's values (3, .true.).
+!=======================================================================
+
+      module ice_step_dyn
+
+      use ice_kinds_mod
+      use, intrinsic :: iso_c_binding
+      use evpk_mod
+
+      implicit none
+      private
+      public :: evpk_step_dynamics_core
+
+      contains
+
+!=======================================================================
+
+      subroutine evpk_step_dynamics_core (dt, ndtd, integral_order, l_dp_midpt)
+
+      use ice_blocks, only: nx_block, ny_block
+      use ice_constants, only: rhos, Lfresh, Tocnfrz, ice_ref_salinity, hs_min, cp_ice, puny
+      use ice_domain_size, only: ncat, nilyr, nslyr, max_ntrcr, max_blocks
+      use ice_dyn_evp, only: evpk_context
+      use ice_exit, only: abort_ice
+      use ice_fileunits, only: nu_diag
+      use ice_flux, only: rdg_conv, rdg_shear, dardg1dt, dardg2dt, dvirdgdt, opening, fpond, fresh, fsalt, fhocn, &
+          aparticn, krdgn, aredistn, vredistn, dardg1ndt, dardg2ndt, dvirdgndt, araftn, vraftn, daidtd, dvidtd, dagedtd
+      use ice_grid, only: dxu, dyu, hm
+      use ice_itd, only: hin_max
+      use ice_state, only: aice0, aicen, vicen, vsnon, trcrn, aice, vice, vsno, trcr, ntrcr, trcr_depend, &
+          nt_Tsfc, nt_qice, nt_qsno, nt_alvl, nt_vlvl, nt_apnd, nt_hpnd, nt_fbri, nt_iage, &
+          tr_iage, tr_lvl, tr_pond_cesm, tr_pond_lvl, tr_pond_topo, tr_brine, tr_aero, nbtrcr
+      use ice_therm_shared, only: heat_capacity, Tmin
+      use ice_transport_driver, only: advection
+      use ice_zbgc_shared, only: first_ice
+
+      real (kind=dbl_kind), intent(in) :: dt                 ! time step
+      integer (kind=int_kind), intent(in) :: ndtd            ! number of dynamics subcycles
+      integer (kind=int_kind), intent(in), optional :: integral_order
+      logical (kind=log_kind), intent(in), optional :: l_dp_midpt
+
+      type (evpk_dyn_args) :: a
+      type (evpk_ridge_diag), target :: dg
+      type (c_ptr) :: ctx
+      integer (c_int32_t), dimension (max_ntrcr+2), target :: dep_trcr, ttype, dep, has
+      real (c_double), dimension (0:ncat), target :: hin
+      integer (c_int32_t), dimension (:,:,:,:), allocatable, target, save :: first_i      ! LOGICAL is not C-interoperable
+      integer (c_int32_t) :: stop(5)
+      integer (c_int) :: rc
+      integer (kind=int_kind) :: nt, k, ntrace
+      logical (kind=log_kind), save :: first = .true.
+      character (len=16), parameter :: stage(3) = (/ 'transport       ', 'ridge_ice       ', 'cleanup_itd     ' /)
+
+      ctx = evpk_context ()
+      if (.not. c_associated(ctx)) call abort_ice('step_dynamics: no velocities on the device: evp has not run yet')
+
+      a%advection = 2
+      if (trim(advection) == 'upwind') a%advection = 1
+      if (a%advection == 2 .and. first) then
+         rc = evpk_remap_init (ctx, loc_r8(dxu), loc_r8(dyu), loc_r8(hm))
+         if (rc /= 0) call abort_ice('step_dynamics: evpk_remap_init: '//trim(evpk_error_string(ctx)))
+         first = .false.
+      endif
+      a%ridge = 1
+      a%dt = dt
+      a%ndtd = int(ndtd, c_int32_t)
+      a%ncat = int(ncat, c_int32_t)
+      a%ntrcr = int(ntrcr, c_int32_t)
+      a%ntrcr_dim = int(max_ntrcr, c_int32_t)
+      dep_trcr = 0
+      dep_trcr(1:ntrcr) = trcr_depend(1:ntrcr)
+      a%trcr_depend = c_loc(dep_trcr)
+
+      ! the tracer indices the stages read, 1-based, 0 = not in use
+      a%t%nt_Tsfc = int(nt_Tsfc, c_int32_t)
+      a%t%nt_qice = int(nt_qice, c_int32_t);  a%t%nilyr = int(nilyr, c_int32_t)
+      a%t%nt_qsno = int(nt_qsno, c_int32_t);  a%t%nslyr = int(nslyr, c_int32_t)
+      if (tr_lvl) then
+         a%t%nt_alvl = int(nt_alvl, c_int32_t);  a%nt_vlvl = int(nt_vlvl, c_int32_t)
+      endif
+      if (tr_pond_cesm .or. tr_pond_lvl .or. tr_pond_topo) then
+         a%t%nt_apnd = int(nt_apnd, c_int32_t);  a%t%nt_hpnd = int(nt_hpnd, c_int32_t)
+      endif
+      if (tr_brine) a%t%nt_fbri = int(nt_fbri, c_int32_t)
+      if (tr_iage) a%nt_iage = int(nt_iage, c_int32_t)
+      a%t%tr_pond_cesm = merge(1_c_int32_t, 0_c_int32_t, tr_pond_cesm)
+      a%t%tr_pond_lvl  = merge(1_c_int32_t, 0_c_int32_t, tr_pond_lvl)
+      a%t%tr_pond_topo = merge(1_c_int32_t, 0_c_int32_t, tr_pond_topo)
+      a%t%tr_brine     = merge(1_c_int32_t, 0_c_int32_t, tr_brine)
+
+      hin(0:ncat) = hin_max(0:ncat)
+      a%hin_max = c_loc(hin)
+      a%k%Tocnfrz = Tocnfrz;  a%k%ice_ref_salinity = ice_ref_salinity;  a%k%hs_min = hs_min;  a%k%cp_ice = cp_ice
+      a%k%Lfresh = Lfresh;  a%k%Tmin = Tmin;  a%k%puny = puny
+      ! aerosols, bgc tracers and the zero-layer model are refused by the library, with its message
+      a%tr_aero = merge(1_c_int32_t, 0_c_int32_t, tr_aero)
+      a%nbtrcr = int(nbtrcr, c_int32_t)
+      a%heat_capacity = merge(1_c_int32_t, 0_c_int32_t, heat_capacity)
+
+      ! init_transport's rule (ice_transport_driver.F90:90-118): hice and hsno first, without a parent; a tracer of the area has none
+      ! either (type 1), one that hangs on a tracer with a parent of its own is type 3, every other type 2; has_dependents from depend
+      ntrace = 2 + ntrcr
+      dep = 0;  ttype = 1;  has = 0
+      k = 2
+      do nt = 1, ntrcr
+         dep(k+nt) = int(trcr_depend(nt), c_int32_t)
+         ttype(k+nt) = 2
+         if (trcr_depend(nt) == 0) then
+            ttype(k+nt) = 1
+         elseif (trcr_depend(nt) > 2) then
+            if (trcr_depend(trcr_depend(nt)-2) > 0) ttype(k+nt) = 3
+         endif
+      enddo
+      do nt = 1, ntrace
+         if (dep(nt) > 0) then
+            if (dep(nt) > nt) then
+               write (nu_diag,*) 'Tracer nt2 =', nt, ' depends on tracer nt1 =', dep(nt)
+               call abort_ice ('ice: remap transport: Must have nt2 > nt1')
+            endif
+            has(dep(nt)) = 1
+         endif
+      enddo
+      a%tracer_type = c_loc(ttype);  a%depend = c_loc(dep);  a%has_dependents = c_loc(has)
+      if (present(integral_order)) a%integral_order = int(integral_order, c_int32_t)
+      if (present(l_dp_midpt)) a%l_dp_midpt = merge(1_c_int32_t, 0_c_int32_t, l_dp_midpt)
+      a%rhos_lfresh = rhos*Lfresh
+
+      ! the module arrays: (nx_block, ny_block, [max_ntrcr,] [ncat,] max_blocks), the first nblocks blocks are used
+      a%aice0 = loc_r8(aice0);  a%aicen = loc_r8(aicen);  a%vicen = loc_r8(vicen);  a%vsnon = loc_r8(vsnon);  a%trcrn = loc_r8(trcrn)
+      a%aice = loc_r8(aice);  a%vice = loc_r8(vice);  a%vsno = loc_r8(vsno);  a%trcr = loc_r8(trcr)
+      a%daidtd = loc_r8(daidtd);  a%dvidtd = loc_r8(dvidtd)
+      if (tr_iage) a%dagedtd = loc_r8(dagedtd)
+      a%fpond = loc_r8(fpond);  a%fresh = loc_r8(fresh);  a%fsalt = loc_r8(fsalt);  a%fhocn = loc_r8(fhocn)
+      a%rdg_conv = loc_r8(rdg_conv);  a%rdg_shear = loc_r8(rdg_shear)
+      if (.not. allocated(first_i)) allocate (first_i(nx_block,ny_block,ncat,max_blocks))
+      first_i = merge(1_c_int32_t, 0_c_int32_t, first_ice)
+      a%first_ice = c_loc(first_i)
+      dg%dardg1dt = loc_r8(dardg1dt);  dg%dardg2dt = loc_r8(dardg2dt);  dg%dvirdgdt = loc_r8(dvirdgdt);  dg%opening = loc_r8(opening)
+      dg%dardg1ndt = loc_r8(dardg1ndt);  dg%dardg2ndt = loc_r8(dardg2ndt);  dg%dvirdgndt = loc_r8(dvirdgndt)
+      dg%aparticn = loc_r8(aparticn);  dg%krdgn = loc_r8(krdgn);  dg%araftn = loc_r8(araftn);  dg%vraftn = loc_r8(vraftn)
+      dg%aredistn = loc_r8(aredistn);  dg%vredistn = loc_r8(vredistn)
+      a%diag = c_loc(dg)
+
+      rc = evpk_step_dynamics (ctx, a, stop)
+      if (rc == EVPK_REMAP_BAD_DEPARTURE) call abort_ice('remap transport: bad departure points')
+      if (rc == EVPK_REMAP_NEGATIVE_MASS) call abort_ice('remap transport: negative area')
+      if (rc == EVPK_RIDGE_STOP .or. rc == EVPK_ITD_STOP) then
+         write (nu_diag,*) 'step_dynamics: ', trim(stage(stop(1))), ' stops: reason, iblk, i, j =', stop(2:5)
+         if (rc == EVPK_RIDGE_STOP) call abort_ice ('ice: Ridging error')
+         call abort_ice ('ice: ITD cleanup error in step_ridge')
+      endif
+      if (rc /= 0) call abort_ice('step_dynamics: evpk_step_dynamics: '//trim(evpk_error_string(ctx)))
+      first_ice = first_i /= 0
+
+      end subroutine evpk_step_dynamics_core
+
+!=======================================================================
+
+! The reference declares its module arrays without TARGET, so C_LOC cannot be applied to them directly; passed to an
+! assumed-size TARGET dummy (sequence association: a contiguous whole array is passed by address, no copy) their address can be
+! taken.  The arrays live as long as the run.
+
+      type (c_ptr) function loc_r8 (a)
+      real (kind=dbl_kind), dimension (*), intent(in), target :: a
+      loc_r8 = c_loc(a)
+      end function loc_r8
+
+      end module ice_step_dyn

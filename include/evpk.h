@@ -401,6 +401,52 @@ int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t 
                    const evpk_itd_tracers *t, int32_t nt_iage, double Tocnfrz, double *aicen, double *vicen, double *vsnon, double *trcrn,
                    double *aice, double *vice, double *vsno, double *aice0, double *trcr, double *daidtd, double *dvidtd, double *dagedtd);
 
+/* everything of step_dynamics behind evp / eap (ice_step_mod.F90:1126-1192) in one call, on state staged once.
+ *
+ * evpk_bound_state: bound_state (ice_state.F90:173-238) alone -- ice_HaloUpdate, centre scalar, fill 0, of aicen, trcrn(1:ntrcr), vicen,
+ * vsnon, in ONE launch that works directly between the block arrays (k_bound_state): a ghost cell with a source takes the value of the
+ * physical cell it mirrors (through the E-W wrap, or the fold onto row ny_global on a tripole grid; 0 where that cell lies in an
+ * eliminated land block), a cell without one takes 0 on the outermost row / column of the array and keeps the caller's value elsewhere;
+ * physical cells and the tracer slots ntrcr + 1 .. ntrcr_dim are never written.  Arrays as for evpk_aggregate; trcrn may be NULL when
+ * ntrcr == 0.  evpk_aggregate(bound = 1) takes the same path.  EVPK_BOUND_DIRECT=0 (read per call) keeps the plane-by-plane path through
+ * the slab, which defines the result.  Returns 1 with evpk_last_error: nranks > 1, ncat > 16, ntrcr > 32.
+ *
+ * evpk_step_dynamics: [evpk_transport_upwind_state | evpk_transport_remap_state](dt), [evpk_ridge_ice(dt, ndtd)],
+ * evpk_cleanup_itd(dt * ndtd), evpk_aggregate(bound = 1, dt), bit for bit, with every caller array the device cannot see copied up at
+ * most once and down at most once per call (page-locked and device arrays are used in place).  Every block ridges and then every block
+ * cleans up, which equals the reference's per-block step_ridge: neither looks beyond its block.  The members are the arguments of those
+ * four entry points under their names there; one struct of borrowed pointers:
+ *   advection                        0: none (the state is already transported), 1: transport_upwind, 2: transport_remap
+ *   ridge                            0 / 1: ridge_ice
+ *   tracer_type .. rhos_lfresh       read when advection == 2
+ *   fpond, fresh, fsalt, fhocn, first_ice   in / out, each may be NULL; shared by ridge_ice and cleanup_itd, as the module arrays are
+ *   rdg_conv, rdg_shear              both NULL: the planes evp / eap left on the device
+ *   diag                             may be NULL; its fpond / fresh / fhocn members are ignored in favour of the ones above
+ * A stop of a stage returns that stage's code (EVPK_REMAP_BAD_DEPARTURE, EVPK_REMAP_NEGATIVE_MASS, EVPK_RIDGE_STOP, EVPK_ITD_STOP) with
+ * stop[0] = the stage (1 transport, 2 ridge, 3 cleanup) and stop[1..4] that stage's four numbers (0 for transport); later stages do not
+ * run and the arrays are undefined.  A refused call (return 1 with evpk_last_error: nranks > 1, advection / ridge out of range, a
+ * missing pointer, anything one of the stages refuses) is refused before the first copy and touches nothing. */
+#define EVPK_HAS_STEP_DYNAMICS 1
+int evpk_bound_state(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim,
+                     double *aicen, double *vicen, double *vsnon, double *trcrn);
+typedef struct {
+    int32_t advection;
+    int32_t ridge;
+    double dt; int32_t ndtd;
+    int32_t ncat, ntrcr, ntrcr_dim; const int32_t *trcr_depend;
+    evpk_itd_tracers t; int32_t nt_vlvl, nt_iage;
+    const double *hin_max; evpk_itd_constants k;
+    int32_t tr_aero, nbtrcr, heat_capacity;                   /* as for evpk_cleanup_itd: only 0, 0, 1 are accepted */
+    const int32_t *tracer_type, *depend, *has_dependents; int32_t integral_order, l_dp_midpt; double rhos_lfresh;
+    double *aice0, *aicen, *vicen, *vsnon, *trcrn;            /* in / out */
+    double *aice, *vice, *vsno, *trcr;                        /* out */
+    double *daidtd, *dvidtd, *dagedtd;                        /* in / out, may be NULL */
+    double *fpond, *fresh, *fsalt, *fhocn; int32_t *first_ice;
+    const double *rdg_conv, *rdg_shear;
+    evpk_ridge_diag *diag;
+} evpk_dyn_args;
+int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t stop[5] /* out: stage, reason, block, i, j */);
+
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared
  * (:79-80), stress_eap (:1052-1467) with update_stress_rdg (:1474-1658) takes the place of stress, stepa (:1664-1787, with
