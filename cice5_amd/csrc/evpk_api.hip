@@ -326,31 +326,31 @@ struct evpk_ctx {
     long long tuned_icellt = -1, tuned1_icellt = -1;
     int slots2 = 512;                // resident 256-thread workgroups of k_subcycle2p on the whole chip
     int nsimd = 1024;                // SIMDs of the chip (4 per CU)
-    double *tp_a = nullptr, *tp_b = nullptr, *tp_stage = nullptr;   // transport_upwind: two scratch planes, staging of the work array
-    size_t tp_stage_n = 0;
+    double *tp_a = nullptr, *tp_b = nullptr;              // transport_upwind: two scratch planes
+    // the pool the caller's pageable arrays of one call are staged into (stage_in): call_stage for a single entry point, dyn_stage for
+    // evpk_step_dynamics, which holds it across the entry points it calls
+    double *call_stage = nullptr, *dyn_stage = nullptr; size_t call_stage_n = 0, dyn_stage_n = 0;
     // transport_remap: grid planes (dxu, dyu, hm), the plane pool of one call shape, its pointer tables, the error word
-    double *rm_grid = nullptr, *rm_pool = nullptr, *rm_stage = nullptr;
+    double *rm_grid = nullptr, *rm_pool = nullptr;
     double **rm_tab = nullptr;
     signed char *rm_sgn = nullptr;
     unsigned *rm_bad = nullptr;
     int *d_bmap = nullptr; int bmap_nbx = 0;              // remap_block_map
     double *uw_pool = nullptr; size_t uw_pool_n = 0;      // evpk_transport_upwind_state: one input + 3 + ntrcr output planes
     double **uw_tab = nullptr; signed char *uw_sgn = nullptr;
-    size_t rm_pool_n = 0, rm_stage_n = 0, rm_tab_n = 0;
-    // evpk_ridge_ice: the planes that pass between its kernels, the ridging masks, the per-iteration block flags, the control words, staging
-    double *rg_pool = nullptr, *rg_stage = nullptr;
+    size_t rm_pool_n = 0, rm_tab_n = 0, rm_sgn_n = 0;
+    // evpk_ridge_ice: the planes that pass between its kernels, the ridging masks, the per-iteration block flags, the control words
+    double *rg_pool = nullptr;
     unsigned *rg_mask = nullptr;
     int *rg_flags = nullptr;
     RidgeCtl *rg_ctl = nullptr;
-    size_t rg_pool_n = 0, rg_stage_n = 0, rg_mask_n = 0, rg_flags_n = 0;
+    size_t rg_pool_n = 0, rg_mask_n = 0, rg_flags_n = 0;
     // evpk_cleanup_itd: the per-block masks of the boundaries at which a block shifts, the stop key
     unsigned *itd_bmask = nullptr; size_t itd_bmask_n = 0;
     unsigned long long *itd_key = nullptr;
     // evpk_bound_state: whether the blocks are the uniform tiling k_bound_state's block table assumes (0 not looked at yet, 1 yes, -1 no)
     int bs_uniform = 0;
-    // evpk_step_dynamics: the pool the caller's pageable arrays of one call are staged into; check_only makes the stage routines return
-    // after their argument checks, before the first copy or launch
-    double *dyn_stage = nullptr; size_t dyn_stage_n = 0;
+    // evpk_step_dynamics: check_only makes the stage routines return after their argument checks, before the first copy or launch
     bool check_only = false;
     // EAP (kdyn = 2): set by evpk_eap_init -- the subcycle loop then runs stress_eap / stepu / stepa (evpk_eap.hip)
     bool eap = false;
@@ -596,6 +596,50 @@ static void *mapped_alias(const void *host, size_t bytes, bool *host_in_place = 
     if (hipPointerGetAttributes(&at, host) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     if (at.type == hipMemoryTypeDevice) return const_cast<void *>(host);
     return nullptr;
+}
+
+// a device buffer of the context that only grows: at least `need` elements behind p afterwards (n counts them); a new buffer loses the
+// old contents and is zeroed on c->stream if asked
+template <class T> static hipError_t grow(evpk_ctx *c, T *&p, size_t &n, size_t need, bool zero = false) {
+    if (n >= need) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr; n = 0;
+    const hipError_t e = hipMalloc(&p, sizeof(T) * need);
+    if (e != hipSuccess) return e;
+    n = need;
+    return zero ? hipMemsetAsync(p, 0, sizeof(T) * need, c->stream) : hipSuccess;
+}
+
+// the caller's arrays of one call: in place where the device sees them (mapped_alias, array by array), else through a staging copy -- up
+// into one pool, and down again at the end if the array is an output.  A NULL or empty array gets a null device pointer.
+struct HostArr {
+    void *host; size_t bytes; void **slot; bool out; bool staged = false;
+    template <class T, class U> HostArr(T *h, size_t count, U **dev, bool o) : host((void *)h), bytes(sizeof(T) * count), slot((void **)dev), out(o) {}
+};
+// (the upward copies are asynchronous on c->stream: the caller synchronises once, with whatever else it sends from pageable memory)
+static int stage_in(evpk_ctx *c, std::vector<HostArr> &arr, bool dyn = false) {
+    size_t need = 0;
+    for (HostArr &a : arr) {
+        *a.slot = (a.host && a.bytes) ? mapped_alias(a.host, a.bytes) : nullptr;
+        a.staged = a.host && a.bytes && !*a.slot;
+        if (a.staged) need += (a.bytes + 7) / 8;
+    }
+    double *&pool = dyn ? c->dyn_stage : c->call_stage;
+    HIPCHK(c, grow(c, pool, dyn ? c->dyn_stage_n : c->call_stage_n, need));
+    double *q = pool;
+    for (HostArr &a : arr)
+        if (a.staged) {
+            HIPCHK(c, hipMemcpyAsync(q, a.host, a.bytes, hipMemcpyHostToDevice, c->stream));
+            *a.slot = q; q += (a.bytes + 7) / 8;
+        }
+    return 0;
+}
+// the outputs back to the caller and the one synchronisation that ends a call
+static int stage_out(evpk_ctx *c, const std::vector<HostArr> &arr) {
+    for (const HostArr &a : arr)
+        if (a.staged && a.out) HIPCHK(c, hipMemcpyAsync(a.host, *a.slot, a.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 // ---- host<->device transfer of one field -------------------------------------------------
@@ -1200,6 +1244,15 @@ template <class F> static inline void with_bool(bool flag, F &&f) {
 template <class F> static inline void with_bool(bool flag1, bool flag2, F &&f) {
     with_bool(flag1, [&](auto B1) { with_bool(flag2, [&](auto B2) { f(B1, B2); }); });
 }
+// the ridging and ITD kernels are built for five categories (<5>) and for any number (<0>): inside f, decltype(NC)::value is that argument
+template <class F> static inline void with_ncat(int ncat, F &&f) {
+    if (ncat == 5) f(std::integral_constant<int, 5>{}); else f(std::integral_constant<int, 0>{});
+}
+
+// a knob that is on unless the environment sets it to 0 (read per call)
+static bool env_on(const char *name) { const char *v = getenv(name); return !(v && atoi(v) == 0); }
+// one workgroup row per row of a caller's block array, one grid layer per local block (LAUNCH_BLOCKS)
+static inline dim3 block_grid(const evpk_ctx *c) { return dim3((c->nxb + 63) / 64, c->nyb, c->nblocks); }
 
 // workgroups of a launch (or of one part of it: strips, band, mirror slab) rounded up to a multiple of 8: XCD remap in the kernels
 static inline int xcd_round(int nwg) { return (nwg + 7) & ~7; }
@@ -1314,7 +1367,7 @@ static void destroy_impl(evpk_ctx *c) {
     if (c->relay) { c->relay->close_(); delete c->relay; }
     if (c->ipc) { if (c->stream2) (void)hipStreamSynchronize(c->stream2); c->ipc->close_(); delete c->ipc; }
     void *ptrs[] = {c->itd, c->stage_itd, c->d_zflags, c->d_zrows, c->s.F, c->s.tmask, c->s.umask, c->s.iceumask, c->s.cmask, c->s.tmphm, c->d_bd, c->stage, c->d_flags,
-                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->tp_stage, c->rm_grid, c->rm_pool, c->rm_stage, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_stage, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->dyn_stage, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
+                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->call_stage, c->rm_grid, c->rm_pool, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->dyn_stage, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -3025,19 +3078,39 @@ extern "C" int evpk_principal_stress(evpk_ctx *c, double *sig1, double *sig2) {
 }
 
 // ---- ice_HaloUpdate / ice_HaloUpdate_stress of a caller's block array on the device (SURVEY S8 row a3 as an entry point) ----
-static int halo_io_ptr(evpk_ctx *c, const double *host, size_t n, double **dev, bool *staged, double **pool, size_t *pool_n, bool upload) {
-    *dev = (double *)mapped_alias(host, sizeof(double) * n);
-    *staged = (*dev == nullptr);
-    if (*staged) {
-        if (*pool_n < n) {
-            if (*pool) (void)hipFree(*pool);
-            *pool = nullptr; *pool_n = 0;
-            HIPCHK(c, hipMalloc(pool, sizeof(double) * n));
-            *pool_n = n;
+// planes of the caller's block arrays (p: the plane of block 0, bstride: doubles from block to block) through the scratch state planes
+// and the general update, max_nf planes at a time; field_loc / field_type as evpk_halo_update's
+struct BlockPlane { double *p; size_t bstride; };
+static int block_planes_halo(evpk_ctx *c, const std::vector<BlockPlane> &pl, int field_loc, int field_type, double fill) {
+    Slab &s = c->s;
+    const dim3 b(64), g = block_grid(c);
+    const bool necorner = (field_loc == 2), vector = (field_type != 1);
+    const int loc_x = field_loc == 4 ? 2 : field_loc == 3 ? 3 : -1;            // k_fold_apply's codes for E face / N face
+    const int chunk = std::min(c->max_nf, (int)NSTATE), np = (int)pl.size();
+    for (int k0 = 0; k0 < np; k0 += chunk) {
+        const int nf = std::min(chunk, np - k0);
+        for (int q = 0; q < nf; q++) {
+            if (!c->full_cover) hipLaunchKernelGGL(k_fill_plane, grid2d(s, B2D), B2D, 0, c->stream, s, (int)F_STATE2 + q, fill);
+            LAUNCH_BLOCKS(k_gather_fs, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)pl[k0 + q].p, pl[k0 + q].bstride, (int)F_STATE2 + q);
         }
-        if (upload) HIPCHK(c, hipMemcpyAsync(*pool, host, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-        *dev = *pool;
+        if (halo(c, F_STATE2, nf, necorner, vector, fill, -1, nullptr, false, -1, 0, loc_x)) return 1;
+        for (int q = 0; q < nf; q++)
+            LAUNCH_BLOCKS(k_scatter_halo, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (int)F_STATE2 + q, pl[k0 + q].p, pl[k0 + q].bstride, fill,
+                          c->ew == EVPK_BND_CYCLIC ? 1 : 0, c->ns == EVPK_BND_TRIPOLE ? 1 : 0, (field_loc == 2 || field_loc == 3) ? 1 : 0, 0, -1);
     }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// which ghost cells border an eliminated land block: the coverage of the slab in plane f, halo-updated like any centre scalar (1 beyond an
+// open / closed boundary: no neighbour at all).  fcov = f, or -1 where no block is missing and the plane is not written
+static int cover_plane(evpk_ctx *c, int f, int &fcov) {
+    fcov = -1;
+    if (c->full_cover && c->nranks == 1) return 0;     // (collective: another rank may have an eliminated block where this one has none)
+    hipLaunchKernelGGL(k_fill_plane, grid2d(c->s, B2D), B2D, 0, c->stream, c->s, f, 0.0);
+    LAUNCH_BLOCKS(k_cover_f, block_grid(c), dim3(64), 0, c->stream, c->s, c->d_bd, c->nxb, c->nyb, f);
+    if (halo(c, f, 1, false, false, 1.0)) return 1;
+    fcov = f;
     return 0;
 }
 
@@ -3046,32 +3119,16 @@ extern "C" int evpk_halo_update(evpk_ctx *c, double *a, int32_t nz, int32_t fiel
     if (!c || !a) return 1;
     if (!c->connected) FAIL(c, "evpk_halo_update: the context is not connected yet (evpk_connect)");
     if (nz < 0 || field_loc < 1 || field_loc > 4 || field_type < 1 || field_type > 3) FAIL(c, "evpk_halo_update: bad nz / field_loc / field_type");
-    Slab &s = c->s;
     HIPCHK(c, hipSetDevice(c->device));
     const int np = nz > 0 ? nz : 1;
     const size_t nblk = (size_t)c->nyb * c->nxb, n = (size_t)c->nblocks * np * nblk;
-    double *dev = nullptr; bool staged = false;
-    if (halo_io_ptr(c, a, n, &dev, &staged, &c->tp_stage, &c->tp_stage_n, true)) return 1;
-    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
-    const bool necorner = (field_loc == 2), vector = (field_type != 1);
-    const int loc_x = field_loc == 4 ? 2 : field_loc == 3 ? 3 : -1;            // k_fold_apply's codes for E face / N face
-    const int chunk = std::min(c->max_nf, (int)NSTATE);
-    for (int k0 = 0; k0 < np; k0 += chunk) {
-        const int nf = std::min(chunk, np - k0);
-        for (int q = 0; q < nf; q++) {
-            if (!c->full_cover) hipLaunchKernelGGL(k_fill_plane, grid2d(s, B2D), B2D, 0, c->stream, s, (int)F_STATE2 + q, fill);
-            LAUNCH_BLOCKS(k_gather_fs, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)(dev + (size_t)(k0 + q) * nblk),
-                               (size_t)np * nblk, (int)F_STATE2 + q);
-        }
-        if (halo(c, F_STATE2, nf, necorner, vector, fill, -1, nullptr, false, -1, 0, loc_x)) return 1;
-        for (int q = 0; q < nf; q++)
-            LAUNCH_BLOCKS(k_scatter_halo, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (int)F_STATE2 + q, dev + (size_t)(k0 + q) * nblk,
-                               (size_t)np * nblk, fill, c->ew == EVPK_BND_CYCLIC ? 1 : 0, c->ns == EVPK_BND_TRIPOLE ? 1 : 0,
-                               (field_loc == 2 || field_loc == 3) ? 1 : 0, 0, -1);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (staged) HIPCHK(c, hipMemcpyAsync(a, dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double *dev = nullptr;
+    std::vector<HostArr> arr = {{a, n, &dev, true}};
+    if (stage_in(c, arr)) return 1;
+    std::vector<BlockPlane> pl;
+    for (int k = 0; k < np; k++) pl.push_back({dev + (size_t)k * nblk, (size_t)np * nblk});
+    if (block_planes_halo(c, pl, field_loc, field_type, fill)) return 1;
+    if (stage_out(c, arr)) return 1;
     return xp_check(c);
 }
 
@@ -3082,40 +3139,25 @@ extern "C" int evpk_halo_update_stress(evpk_ctx *c, double *a1, const double *a2
     Slab &s = c->s;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nblk = (size_t)c->nyb * c->nxb, n = (size_t)c->nblocks * nblk;
-    // both arrays through one staging pool when they are plain host memory: [a1 | a2]
-    double *d1 = (double *)mapped_alias(a1, sizeof(double) * n), *d2 = (double *)mapped_alias(a2, sizeof(double) * n);
-    const bool staged1 = (d1 == nullptr), staged2 = (d2 == nullptr);
-    if (staged1 || staged2) {
-        if (c->tp_stage_n < 2 * n) {
-            if (c->tp_stage) (void)hipFree(c->tp_stage);
-            c->tp_stage = nullptr; c->tp_stage_n = 0;
-            HIPCHK(c, hipMalloc(&c->tp_stage, sizeof(double) * 2 * n));
-            c->tp_stage_n = 2 * n;
-        }
-        if (staged1) { HIPCHK(c, hipMemcpyAsync(c->tp_stage, a1, sizeof(double) * n, hipMemcpyHostToDevice, c->stream)); d1 = c->tp_stage; }
-        if (staged2) { HIPCHK(c, hipMemcpyAsync(c->tp_stage + n, a2, sizeof(double) * n, hipMemcpyHostToDevice, c->stream)); d2 = c->tp_stage + n; }
-    }
-    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
+    double *d1 = nullptr;
+    const double *d2 = nullptr;
+    std::vector<HostArr> arr = {{a1, n, &d1, true}, {a2, n, &d2, false}};
+    if (stage_in(c, arr)) return 1;
+    const dim3 b(64), g = block_grid(c);
     const int fA = F_STATE2, fB = F_STATE2 + 1, fC = F_STATE2 + 2;
-    int fcov = -1;
-    if (!c->full_cover || c->nranks > 1) {     // (collective: another rank may have an eliminated block where this one has none)
-        // which ghost cells border an eliminated land block: the coverage of the slab, halo-updated like any centre scalar
-        // (beyond an open / closed boundary there is no neighbour at all: 1 = leave alone)
-        hipLaunchKernelGGL(k_fill_plane, grid2d(s, B2D), B2D, 0, c->stream, s, fC, 0.0);
-        LAUNCH_BLOCKS(k_cover_f, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, fC);
-        if (halo(c, fC, 1, false, false, 1.0)) return 1;
+    int fcov;
+    if (cover_plane(c, fC, fcov)) return 1;
+    if (fcov >= 0) {
         hipLaunchKernelGGL(k_fill_plane, grid2d(s, B2D), B2D, 0, c->stream, s, fA, 0.0);
         hipLaunchKernelGGL(k_fill_plane, grid2d(s, B2D), B2D, 0, c->stream, s, fB, 0.0);
-        fcov = fC;
     }
     LAUNCH_BLOCKS(k_gather_fs, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)d1, nblk, fA);
-    LAUNCH_BLOCKS(k_gather_fs, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)d2, nblk, fB);
+    LAUNCH_BLOCKS(k_gather_fs, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, d2, nblk, fB);
     if (c->ns == EVPK_BND_TRIPOLE && halo(c, fA, 1, false, false, 0.0, fB)) return 1;
     LAUNCH_BLOCKS(k_scatter_halo, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, fA, d1, nblk, 0.0, c->ew == EVPK_BND_CYCLIC ? 1 : 0,
                        c->ns == EVPK_BND_TRIPOLE ? 1 : 0, 0, 1, fcov);
     HIPCHK(c, hipGetLastError());
-    if (staged1) HIPCHK(c, hipMemcpyAsync(a1, d1, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stage_out(c, arr)) return 1;
     return xp_check(c);
 }
 
@@ -3213,6 +3255,14 @@ extern "C" int evpk_restart_read(evpk_ctx *c, const char *path, int64_t byte_off
 }
 
 // ---- transport_upwind (source/ice_transport_driver.F90:634-772) on the resident velocities -------------
+// edge velocities and their halo updates (:688-708): E face / N face vectors, in the sig1 / sig2 planes (scratch between calls of
+// evpk_principal_stress, which rewrites them whole)
+static int edge_velocities(evpk_ctx *c) {
+    hipLaunchKernelGGL(k_edge_vel, grid2d(c->s, B2D), B2D, 0, c->stream, c->s, c->cur ? (int)F_STATE1 : (int)F_STATE0, (int)F_SIG1, (int)F_SIG2);
+    if (halo(c, F_SIG1, 1, false, true, 0.0, -1, nullptr, false, -1, 0, 2)) return 1;
+    return halo(c, F_SIG2, 1, false, true, 0.0, -1, nullptr, false, -1, 0, 3);
+}
+
 extern "C" int evpk_transport_upwind(evpk_ctx *c, double dt, int32_t narr, double *works) {
     if (c && c->idle) return 0;       // a rank without a block column: in no exchange, nothing to compute
     if (!c || !works || narr < 1) return 1;
@@ -3220,8 +3270,6 @@ extern "C" int evpk_transport_upwind(evpk_ctx *c, double dt, int32_t narr, doubl
     if (!c->have_lengths) FAIL(c, "evpk_transport_upwind needs HTN and HTE in evpk_geom");
     Slab &s = c->s;
     HIPCHK(c, hipSetDevice(c->device));
-    const dim3 g2 = grid2d(s, B2D);
-    const int SB = c->cur ? F_STATE1 : F_STATE0;
     const size_t np = mask_elems(s), nblk = (size_t)c->nyb * c->nxb, n = (size_t)c->nblocks * narr * nblk;
     if (!c->tp_a) {
         HIPCHK(c, hipMalloc(&c->tp_a, sizeof(double) * np));
@@ -3229,25 +3277,11 @@ extern "C" int evpk_transport_upwind(evpk_ctx *c, double dt, int32_t narr, doubl
         HIPCHK(c, hipMemsetAsync(c->tp_a, 0, sizeof(double) * np, c->stream));
         HIPCHK(c, hipMemsetAsync(c->tp_b, 0, sizeof(double) * np, c->stream));
     }
-    // edge velocities and their halo updates (:688-708): E face / N face vectors, in the sig1 / sig2 planes (scratch between
-    // calls of evpk_principal_stress, which rewrites them whole)
-    hipLaunchKernelGGL(k_edge_vel, g2, B2D, 0, c->stream, s, SB, (int)F_SIG1, (int)F_SIG2);
-    if (halo(c, F_SIG1, 1, false, true, 0.0, -1, nullptr, false, -1, 0, 2)) return 1;
-    if (halo(c, F_SIG2, 1, false, true, 0.0, -1, nullptr, false, -1, 0, 3)) return 1;
-    // the work array: in place where the caller's memory is visible to the device, else through a staging copy
-    double *dev = (double *)mapped_alias(works, sizeof(double) * n);
-    const bool staged = (dev == nullptr);
-    if (staged) {
-        if (c->tp_stage_n < n) {
-            if (c->tp_stage) (void)hipFree(c->tp_stage);
-            c->tp_stage = nullptr; c->tp_stage_n = 0;
-            HIPCHK(c, hipMalloc(&c->tp_stage, sizeof(double) * n));
-            c->tp_stage_n = n;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->tp_stage, works, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-        dev = c->tp_stage;
-    }
-    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
+    if (edge_velocities(c)) return 1;
+    double *dev = nullptr;
+    std::vector<HostArr> arr = {{works, n, &dev, true}};
+    if (stage_in(c, arr)) return 1;
+    const dim3 b(64), g = block_grid(c);
     for (int a = 0; a < narr; a++) {       // upwind_field (:1667-1687), one array at a time through two scratch planes
         LAUNCH_BLOCKS(k_gather_plane, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)(dev + (size_t)a * nblk),
                            (size_t)narr * nblk, c->tp_a);
@@ -3257,27 +3291,15 @@ extern "C" int evpk_transport_upwind(evpk_ctx *c, double dt, int32_t narr, doubl
                            dev + (size_t)a * nblk, (size_t)narr * nblk);
     }
     HIPCHK(c, hipGetLastError());
-    if (staged) HIPCHK(c, hipMemcpyAsync(works, c->tp_stage, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stage_out(c, arr)) return 1;
     return xp_check(c);
 }
 
 static int planes_halo(evpk_ctx *c, double **d_list, const signed char *d_sgn, int n, bool vector);
 
-// ---- transport_upwind with the state transforms (state_to_work, work_to_state + compute_tracers, bound_state) -----------------
-extern "C" int evpk_transport_upwind_state(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
-                                           int32_t nt_Tsfc, int32_t nt_alvl, int32_t nt_apnd, int32_t nt_fbri, int32_t tr_pond_cesm,
-                                           int32_t tr_pond_lvl, int32_t tr_pond_topo, double Tocnfrz, double *aice0, double *aicen, double *vicen,
-                                           double *vsnon, double *trcrn) {
-    if (c && c->idle) return 0;       // a rank without a block column: in no exchange, nothing to compute
-    if (!c || !aice0 || !aicen || !vicen || !vsnon || ncat < 1 || ntrcr < 0 || ntrcr_dim < ntrcr || (ntrcr > 0 && (!trcrn || !trcr_depend))) return 1;
-    if (!c->uploaded) FAIL(c, "evpk_transport_upwind_state: no velocities on the device (run evp first)");
-    if (!c->have_lengths) FAIL(c, "evpk_transport_upwind_state needs HTN and HTE in evpk_geom");
-    if (ntrcr > UW_MAXT) FAIL(c, "evpk_transport_upwind_state: ntrcr = %d exceeds %d", ntrcr, UW_MAXT);
-    Slab &s = c->s;
-    HIPCHK(c, hipSetDevice(c->device));
-    UpwState u{};
-    u.ncat = ncat; u.ntrcr = ntrcr; u.ntrcr_dim = ntrcr_dim; u.nt_Tsfc = nt_Tsfc; u.nt_fbri = nt_fbri; u.Tocnfrz = Tocnfrz;
+// the per-tracer tables of UpwState from trcr_depend: tracer INDICES (1-based, 0 = none), not the slots of tracer_tables
+static int upw_tables(evpk_ctx *c, UpwState &u, int32_t ntrcr, const int32_t *trcr_depend, int32_t nt_Tsfc, int32_t nt_alvl, int32_t nt_apnd,
+                      int32_t nt_fbri, int32_t tr_pond_cesm, int32_t tr_pond_lvl, int32_t tr_pond_topo) {
     for (int it = 1; it <= ntrcr; it++) {
         const int dep = trcr_depend[it - 1], k = it - 1;
         // state_to_work (:1435-1497), its branches in the reference's order (the pond branch as written: `a .and. cesm .or. topo`)
@@ -3308,69 +3330,51 @@ extern "C" int evpk_transport_upwind_state(evpk_ctx *c, double dt, int32_t ncat,
         for (int m : {(int)u.m1[k], (int)u.m2[k], (int)u.d1[k], (int)u.d2[k]})
             if (m > ntrcr) FAIL(c, "evpk_transport_upwind_state: tracer %d hangs on tracer %d, beyond ntrcr", it, m);
     }
+    return 0;
+}
+
+// ---- transport_upwind with the state transforms (state_to_work, work_to_state + compute_tracers, bound_state) -----------------
+extern "C" int evpk_transport_upwind_state(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
+                                           int32_t nt_Tsfc, int32_t nt_alvl, int32_t nt_apnd, int32_t nt_fbri, int32_t tr_pond_cesm,
+                                           int32_t tr_pond_lvl, int32_t tr_pond_topo, double Tocnfrz, double *aice0, double *aicen, double *vicen,
+                                           double *vsnon, double *trcrn) {
+    if (c && c->idle) return 0;       // a rank without a block column: in no exchange, nothing to compute
+    if (!c || !aice0 || !aicen || !vicen || !vsnon || ncat < 1 || ntrcr < 0 || ntrcr_dim < ntrcr || (ntrcr > 0 && (!trcrn || !trcr_depend))) return 1;
+    if (!c->uploaded) FAIL(c, "evpk_transport_upwind_state: no velocities on the device (run evp first)");
+    if (!c->have_lengths) FAIL(c, "evpk_transport_upwind_state needs HTN and HTE in evpk_geom");
+    if (ntrcr > UW_MAXT) FAIL(c, "evpk_transport_upwind_state: ntrcr = %d exceeds %d", ntrcr, UW_MAXT);
+    Slab &s = c->s;
+    HIPCHK(c, hipSetDevice(c->device));
+    UpwState u{};
+    u.ncat = ncat; u.ntrcr = ntrcr; u.ntrcr_dim = ntrcr_dim; u.nt_Tsfc = nt_Tsfc; u.nt_fbri = nt_fbri; u.Tocnfrz = Tocnfrz;
+    if (upw_tables(c, u, ntrcr, trcr_depend, nt_Tsfc, nt_alvl, nt_apnd, nt_fbri, tr_pond_cesm, tr_pond_lvl, tr_pond_topo)) return 1;
     if (c->check_only) return 0;
-    const size_t np = mask_elems(s), nblk = (size_t)c->nyb * c->nxb, nb = (size_t)c->nblocks;
+    const size_t np = mask_elems(s), nblk = (size_t)c->nyb * c->nxb, N = (size_t)c->nblocks * nblk;
     const int nq = 3 + ntrcr;
     // planes: one input plane, nq output planes of a category
-    if (c->uw_pool_n < (size_t)(nq + 1) * np) {
-        if (c->uw_pool) (void)hipFree(c->uw_pool);
-        c->uw_pool = nullptr; c->uw_pool_n = 0;
-        HIPCHK(c, hipMalloc(&c->uw_pool, sizeof(double) * (size_t)(nq + 1) * np));
-        c->uw_pool_n = (size_t)(nq + 1) * np;
-        HIPCHK(c, hipMemsetAsync(c->uw_pool, 0, sizeof(double) * (size_t)(nq + 1) * np, c->stream));
-    }
+    HIPCHK(c, grow(c, c->uw_pool, c->uw_pool_n, (size_t)(nq + 1) * np, true));
     if (!c->uw_tab) { HIPCHK(c, hipMalloc(&c->uw_tab, sizeof(double *) * (UW_MAXT + 4))); HIPCHK(c, hipMalloc(&c->uw_sgn, UW_MAXT + 4)); }
     std::vector<double *> tab(nq);
     for (int q = 0; q < nq; q++) tab[q] = c->uw_pool + (size_t)(q + 1) * np;
     std::vector<signed char> sg(nq, 1);
     HIPCHK(c, hipMemcpyAsync(c->uw_tab, tab.data(), sizeof(double *) * nq, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->uw_sgn, sg.data(), nq, hipMemcpyHostToDevice, c->stream));
-    // the caller's arrays: in place where the device sees them, else through a staging copy
-    double *host5[5] = {aice0, aicen, vicen, vsnon, trcrn};
-    const size_t n5[5] = {nb * nblk, nb * ncat * nblk, nb * ncat * nblk, nb * ncat * nblk, ntrcr ? nb * ncat * ntrcr_dim * nblk : 0};
-    double *dev5[5];
-    bool staged[5];
-    size_t need = 0;
-    for (int q = 0; q < 5; q++) {
-        dev5[q] = (host5[q] && n5[q]) ? (double *)mapped_alias(host5[q], sizeof(double) * n5[q]) : nullptr;
-        staged[q] = host5[q] && n5[q] && !dev5[q];
-        if (staged[q]) need += n5[q];
-    }
-    if (need) {
-        if (c->rm_stage_n < need) {
-            if (c->rm_stage) (void)hipFree(c->rm_stage);
-            c->rm_stage = nullptr; c->rm_stage_n = 0;
-            HIPCHK(c, hipMalloc(&c->rm_stage, sizeof(double) * need));
-            c->rm_stage_n = need;
-        }
-        double *q2 = c->rm_stage;
-        for (int q = 0; q < 5; q++)
-            if (staged[q]) { HIPCHK(c, hipMemcpyAsync(q2, host5[q], sizeof(double) * n5[q], hipMemcpyHostToDevice, c->stream)); dev5[q] = q2; q2 += n5[q]; }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // (tab, sg are pageable host vectors)
-    u.aicen = dev5[1]; u.vicen = dev5[2]; u.vsnon = dev5[3]; u.trcrn = dev5[4];
-    // edge velocities and their halo updates (:688-708), as evpk_transport_upwind
-    const dim3 g2 = grid2d(s, B2D);
-    const int SB = c->cur ? F_STATE1 : F_STATE0;
-    hipLaunchKernelGGL(k_edge_vel, g2, B2D, 0, c->stream, s, SB, (int)F_SIG1, (int)F_SIG2);
-    if (halo(c, F_SIG1, 1, false, true, 0.0, -1, nullptr, false, -1, 0, 2)) return 1;
-    if (halo(c, F_SIG2, 1, false, true, 0.0, -1, nullptr, false, -1, 0, 3)) return 1;
-    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks), gu((s.nxl + 63) / 64, (s.nyl + 3) / 4);
+    double *d_aice0 = nullptr;
+    std::vector<HostArr> arr = {{aice0, N, &d_aice0, true}, {aicen, N * ncat, &u.aicen, true}, {vicen, N * ncat, &u.vicen, true},
+                                {vsnon, N * ncat, &u.vsnon, true}, {trcrn, ntrcr ? N * ncat * ntrcr_dim : 0, &u.trcrn, true}};
+    if (stage_in(c, arr)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (tab, sg and staged caller arrays are pageable)
+    if (edge_velocities(c)) return 1;
+    const dim3 g2 = grid2d(s, B2D), b(64), g = block_grid(c), gu((s.nxl + 63) / 64, (s.nyl + 3) / 4);
     double *pin = c->uw_pool;
     // ghost cells that border an eliminated land block: bound_state's halo update writes its fill (0) into the STATE arrays
-    // there (mpi/ice_boundary.F90 srcBlock == 0), not compute_tracers of an empty cell -- the coverage of the slab, halo-updated
-    // like any centre scalar (1 beyond an open / closed boundary: no neighbour at all), tells k_upw_scatter which they are
-    int fcov = -1;
-    if (!c->full_cover || c->nranks > 1) {     // (collective: another rank may have an eliminated block where this one has none)
-        hipLaunchKernelGGL(k_fill_plane, g2, B2D, 0, c->stream, s, (int)F_WORK1, 0.0);
-        LAUNCH_BLOCKS(k_cover_f, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (int)F_WORK1);
-        if (halo(c, F_WORK1, 1, false, false, 1.0)) return 1;
-        fcov = F_WORK1;
-    }
+    // there (mpi/ice_boundary.F90 srcBlock == 0), not compute_tracers of an empty cell -- the coverage tells k_upw_scatter which they are
+    int fcov;
+    if (cover_plane(c, F_WORK1, fcov)) return 1;
     // aice0: physical cells only (no halo update in the reference)
-    LAUNCH_BLOCKS(k_gather_plane, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)dev5[0], nblk, pin);
+    LAUNCH_BLOCKS(k_gather_plane, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)d_aice0, nblk, pin);
     hipLaunchKernelGGL(k_upwind, gu, B2D, 0, c->stream, s, dt, (int)F_SIG1, (int)F_SIG2, (const double *)pin, tab[0]);
-    LAUNCH_BLOCKS(k_scatter_plane, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)tab[0], dev5[0], nblk);
+    LAUNCH_BLOCKS(k_scatter_plane, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)tab[0], d_aice0, nblk);
     for (int n = 0; n < ncat; n++) {
         for (int q = 0; q < nq; q++) {
             LAUNCH_BLOCKS(k_upw_gather, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, u, n, q, pin);
@@ -3386,10 +3390,38 @@ extern "C" int evpk_transport_upwind_state(evpk_ctx *c, double dt, int32_t ncat,
     if (fcov >= 0 && !(getenv("EVPK_DEBUG_KEEP_COVER") && atoi(getenv("EVPK_DEBUG_KEEP_COVER"))))
         hipLaunchKernelGGL(k_fill_plane, g2, B2D, 0, c->stream, s, (int)F_WORK1, 0.0);
     HIPCHK(c, hipGetLastError());
-    for (int q = 0; q < 5; q++)
-        if (staged[q]) HIPCHK(c, hipMemcpyAsync(host5[q], dev5[q], sizeof(double) * n5[q], hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stage_out(c, arr)) return 1;
     return xp_check(c);
+}
+
+// the per-tracer tables acc / rule / d1 / d2 / slot of RidgeArgs and ItdArgs from trcr_depend: how aicen * trcrn is built (ice_mechred.F90
+// :1456-1513, shift_ice ice_itd.F90:919-975, aggregate :348-433) and compute_tracers (:1407-1499), after the checks of the tracer indices both
+// share.  t.nt_Tsfc > 0: compute_tracers asks for nt_Tsfc first (:1408); nt_vlvl: ridge_ice's own index
+template <class Args> static int tracer_tables(evpk_ctx *c, const char *who, Args &A, int32_t ntrcr, const int32_t *trcr_depend, const evpk_itd_tracers &t,
+                                               int32_t nt_vlvl = 0) {
+    const int nts[] = {t.nt_Tsfc, t.nt_qice, t.nt_qsno, t.nt_alvl, nt_vlvl, t.nt_apnd, t.nt_hpnd, t.nt_fbri};
+    for (int q : nts) if (q < 0 || q > ntrcr) FAIL(c, "%s: tracer index %d not in 0..ntrcr = %d", who, q, ntrcr);
+    if (t.nilyr < 0 || (t.nilyr > 0 && (t.nt_qice < 1 || t.nt_qice + t.nilyr - 1 > ntrcr))) FAIL(c, "%s: nt_qice / nilyr beyond ntrcr", who);
+    if (t.nslyr < 0 || (t.nslyr > 0 && (t.nt_qsno < 1 || t.nt_qsno + t.nslyr - 1 > ntrcr))) FAIL(c, "%s: nt_qsno / nslyr beyond ntrcr", who);
+    if (t.tr_pond_topo && (t.nt_apnd < 1 || t.nt_hpnd < 1)) FAIL(c, "%s: tr_pond_topo without nt_apnd / nt_hpnd", who);
+    if (t.tr_pond_lvl && t.nt_apnd > 0 && t.nt_alvl < 1) FAIL(c, "%s: tr_pond_lvl without nt_alvl", who);
+    const bool pond_at = t.tr_pond_cesm || t.tr_pond_topo;
+    for (int it = 1; it <= ntrcr; it++) {
+        const int dep = trcr_depend[it - 1], k = it - 1;
+        A.acc[k] = -1; A.rule[k] = -1; A.d1[k] = 0; A.d2[k] = 0; A.slot[k] = 0;
+        if (dep == 0) { A.acc[k] = 0; A.rule[k] = 1; }
+        else if (dep == 1) { A.acc[k] = 1; A.rule[k] = 2; }
+        else if (dep == 2) { A.acc[k] = 2; A.rule[k] = 3; }
+        else if (t.nt_alvl > 0 && dep == 2 + t.nt_alvl) { A.acc[k] = 3; A.rule[k] = 4; A.d1[k] = 1; }
+        else if (t.nt_apnd > 0 && dep == 2 + t.nt_apnd && pond_at) { A.acc[k] = 4; A.rule[k] = 4; A.d1[k] = 2; }
+        else if (t.nt_apnd > 0 && dep == 2 + t.nt_apnd && t.tr_pond_lvl) { A.acc[k] = 5; A.rule[k] = 5; A.d1[k] = 1; A.d2[k] = 2; }
+        else if (t.nt_fbri > 0 && dep == 2 + t.nt_fbri) { A.acc[k] = 6; A.rule[k] = 6; A.d1[k] = 3; }
+        if (it == t.nt_Tsfc) A.rule[k] = 0;
+        if (it == t.nt_alvl) A.slot[k] = 1;
+        else if (it == t.nt_apnd) A.slot[k] = 2;
+        else if (it == t.nt_fbri) A.slot[k] = 3;
+    }
+    return 0;
 }
 
 // ---- ridge_ice (source/ice_mechred.F90:101-746) on the caller's state arrays (kernels in evpk_ridge.hip) ----
@@ -3413,93 +3445,39 @@ extern "C" int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat
     if ((rdg_conv == nullptr) != (rdg_shear == nullptr)) FAIL(c, "evpk_ridge_ice: rdg_conv and rdg_shear must both be given or both be NULL");
     if (!rdg_conv && !(c->prepped && c->ksub >= c->p.ndte))
         FAIL(c, "evpk_ridge_ice: rdg_conv = NULL needs the deformation rates of a finished evp / eap on the device");
-    const int nts[] = {t->nt_qsno, t->nt_alvl, t->nt_vlvl, t->nt_apnd, t->nt_hpnd, t->nt_fbri};
-    for (int q : nts) if (q < 0 || q > ntrcr) FAIL(c, "evpk_ridge_ice: tracer index %d not in 0..ntrcr = %d", q, ntrcr);
-    if (t->nslyr < 0 || (t->nslyr > 0 && (t->nt_qsno < 1 || t->nt_qsno + t->nslyr - 1 > ntrcr))) FAIL(c, "evpk_ridge_ice: nt_qsno / nslyr beyond ntrcr");
-    if (t->tr_pond_topo && (t->nt_apnd < 1 || t->nt_hpnd < 1)) FAIL(c, "evpk_ridge_ice: tr_pond_topo without nt_apnd / nt_hpnd");
-    if (t->tr_pond_lvl && t->nt_apnd > 0 && t->nt_alvl < 1) FAIL(c, "evpk_ridge_ice: tr_pond_lvl without nt_alvl");
+    // (ridge_ice's compute_tracers runs without nt_Tsfc: a surface temperature is an ordinary area tracer here)
+    evpk_itd_tracers ti{};
+    ti.nt_qsno = t->nt_qsno; ti.nslyr = t->nslyr; ti.nt_alvl = t->nt_alvl; ti.nt_apnd = t->nt_apnd; ti.nt_hpnd = t->nt_hpnd; ti.nt_fbri = t->nt_fbri;
+    ti.tr_pond_cesm = t->tr_pond_cesm; ti.tr_pond_lvl = t->tr_pond_lvl; ti.tr_pond_topo = t->tr_pond_topo;
+    RidgeArgs A{};
+    if (tracer_tables(c, "evpk_ridge_ice", A, ntrcr, trcr_depend, ti, t->nt_vlvl)) return 1;
     if (!c->nblocks || c->check_only) return 0;
     Slab &s = c->s;
     HIPCHK(c, hipSetDevice(c->device));
-    RidgeArgs A{};
     A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
     A.nt_qsno = t->nt_qsno; A.nslyr = t->nslyr; A.nt_alvl = t->nt_alvl; A.nt_vlvl = t->nt_vlvl; A.nt_apnd = t->nt_apnd; A.nt_hpnd = t->nt_hpnd;
     A.nt_fbri = t->nt_fbri; A.tr_pond_topo = t->tr_pond_topo ? 1 : 0;
     A.dt = dt; A.dti_thermo = 1.0 / (ndtd * dt);
     for (int n = 0; n <= ncat; n++) A.hin_max[n] = hin_max[n];
     A.hin_max[ncat] = 1.0e8;
-    const bool pond_at = t->tr_pond_cesm || t->tr_pond_topo;
-    for (int it = 1; it <= ntrcr; it++) {
-        const int dep = trcr_depend[it - 1], k = it - 1;
-        // how atrcrn is built (:1456-1513) and compute_tracers (ice_itd.F90:1407-1499), their branches in the reference's order
-        A.acc[k] = -1; A.rule[k] = -1; A.d1[k] = 0; A.d2[k] = 0; A.slot[k] = 0;
-        if (dep == 0) { A.acc[k] = 0; A.rule[k] = 1; }
-        else if (dep == 1) { A.acc[k] = 1; A.rule[k] = 2; }
-        else if (dep == 2) { A.acc[k] = 2; A.rule[k] = 3; }
-        else if (t->nt_fbri > 0 && dep == 2 + t->nt_fbri) { A.acc[k] = 6; A.rule[k] = 6; A.d1[k] = 3; }
-        else if (t->nt_alvl > 0 && dep == 2 + t->nt_alvl) { A.acc[k] = 3; A.rule[k] = 4; A.d1[k] = 1; }
-        else if (t->nt_apnd > 0 && dep == 2 + t->nt_apnd && pond_at) { A.acc[k] = 4; A.rule[k] = 4; A.d1[k] = 2; }
-        else if (t->nt_apnd > 0 && dep == 2 + t->nt_apnd && t->tr_pond_lvl) { A.acc[k] = 5; A.rule[k] = 5; A.d1[k] = 1; A.d2[k] = 2; }
-        if (it == t->nt_alvl) A.slot[k] = 1;
-        else if (it == t->nt_apnd) A.slot[k] = 2;
-        else if (it == t->nt_fbri) A.slot[k] = 3;
-    }
     const size_t nblk = (size_t)c->nyb * c->nxb, nb = (size_t)c->nblocks, N = nb * nblk;
     // the caller's arrays: in place where the device sees them, else through a staging copy (up, and down again at the end)
     evpk_ridge_diag dg{};
     if (diag) dg = *diag;
-    struct Arr { double *host; size_t n; double **slot; bool out; };
     const size_t n2 = N, n3 = N * ncat;
-    Arr arr[] = {
+    std::vector<HostArr> arr = {
         {aice0, n2, &A.aice0, true}, {aicen, n3, &A.aicen, true}, {vicen, n3, &A.vicen, true}, {vsnon, n3, &A.vsnon, true},
-        {ntrcr ? trcrn : nullptr, n3 * ntrcr_dim, &A.trcrn, true},
-        {const_cast<double *>(rdg_conv), n2, const_cast<double **>(&A.rdg_conv), false}, {const_cast<double *>(rdg_shear), n2, const_cast<double **>(&A.rdg_shear), false},
+        {ntrcr ? trcrn : nullptr, n3 * ntrcr_dim, &A.trcrn, true}, {rdg_conv, n2, &A.rdg_conv, false}, {rdg_shear, n2, &A.rdg_shear, false},
         {dg.dardg1dt, n2, &A.dardg1dt, true}, {dg.dardg2dt, n2, &A.dardg2dt, true}, {dg.dvirdgdt, n2, &A.dvirdgdt, true}, {dg.opening, n2, &A.opening, true},
         {dg.fpond, n2, &A.fpond, true}, {dg.fresh, n2, &A.fresh, true}, {dg.fhocn, n2, &A.fhocn, true},
         {dg.dardg1ndt, n3, &A.dardg1ndt, true}, {dg.dardg2ndt, n3, &A.dardg2ndt, true}, {dg.dvirdgndt, n3, &A.dvirdgndt, true},
         {dg.aparticn, n3, &A.aparticn, true}, {dg.krdgn, n3, &A.krdgn, true}, {dg.araftn, n3, &A.araftn, true}, {dg.vraftn, n3, &A.vraftn, true},
         {dg.aredistn, n3, &A.aredistn, true}, {dg.vredistn, n3, &A.vredistn, true}};
-    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
-    bool staged[NARR];
-    size_t need = 0;
-    for (int q = 0; q < NARR; q++) {
-        *arr[q].slot = (arr[q].host && arr[q].n) ? (double *)mapped_alias(arr[q].host, sizeof(double) * arr[q].n) : nullptr;
-        staged[q] = arr[q].host && arr[q].n && !*arr[q].slot;
-        if (staged[q]) need += arr[q].n;
-    }
-    if (c->rg_stage_n < need) {
-        if (c->rg_stage) (void)hipFree(c->rg_stage);
-        c->rg_stage = nullptr; c->rg_stage_n = 0;
-        HIPCHK(c, hipMalloc(&c->rg_stage, sizeof(double) * need));
-        c->rg_stage_n = need;
-    }
-    {
-        double *q2 = c->rg_stage;
-        for (int q = 0; q < NARR; q++)
-            if (staged[q]) {
-                HIPCHK(c, hipMemcpyAsync(q2, arr[q].host, sizeof(double) * arr[q].n, hipMemcpyHostToDevice, c->stream));
-                *arr[q].slot = q2; q2 += arr[q].n;
-            }
-    }
-    const size_t npool = RidgePool::planes(ncat) * N, nflags = (size_t)(RG_NITER + 1) * nb;
-    if (c->rg_pool_n < npool) {
-        if (c->rg_pool) (void)hipFree(c->rg_pool);
-        c->rg_pool = nullptr; c->rg_pool_n = 0;
-        HIPCHK(c, hipMalloc(&c->rg_pool, sizeof(double) * npool));
-        c->rg_pool_n = npool;
-    }
-    if (c->rg_mask_n < N) {
-        if (c->rg_mask) (void)hipFree(c->rg_mask);
-        c->rg_mask = nullptr; c->rg_mask_n = 0;
-        HIPCHK(c, hipMalloc(&c->rg_mask, sizeof(unsigned) * N));
-        c->rg_mask_n = N;
-    }
-    if (c->rg_flags_n < nflags) {
-        if (c->rg_flags) (void)hipFree(c->rg_flags);
-        c->rg_flags = nullptr; c->rg_flags_n = 0;
-        HIPCHK(c, hipMalloc(&c->rg_flags, sizeof(int) * nflags));
-        c->rg_flags_n = nflags;
-    }
+    if (stage_in(c, arr)) return 1;
+    const size_t nflags = (size_t)(RG_NITER + 1) * nb;
+    HIPCHK(c, grow(c, c->rg_pool, c->rg_pool_n, RidgePool::planes(ncat) * N));
+    HIPCHK(c, grow(c, c->rg_mask, c->rg_mask_n, N));
+    HIPCHK(c, grow(c, c->rg_flags, c->rg_flags_n, nflags));
     if (!c->rg_ctl) HIPCHK(c, hipMalloc(&c->rg_ctl, sizeof(RidgeCtl)));
     RidgeCtl h{};
     h.key = ~0ull;
@@ -3507,16 +3485,14 @@ extern "C" int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat
     HIPCHK(c, hipMemsetAsync(c->rg_flags, 0, sizeof(int) * nflags, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (h and staged caller arrays are pageable)
     RidgePool P{c->rg_pool, c->rg_mask, N, ncat};
-    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
+    const dim3 b(64), g = block_grid(c);
     int reason = 0, iters = 0;
     for (int iter = 1; iter <= RG_NITER && !reason; iter++) {
-        if (ncat == 5) {
-            hipLaunchKernelGGL(k_ridge_weights<5>, g, b, 0, c->stream, s, c->p, (const BlockDesc *)c->d_bd, A, P, iter, c->rg_flags, c->nblocks, c->rg_ctl);
-            hipLaunchKernelGGL(k_ridge_tracers<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, P, iter, (const int *)c->rg_flags, c->nblocks);
-        } else {
-            hipLaunchKernelGGL(k_ridge_weights<0>, g, b, 0, c->stream, s, c->p, (const BlockDesc *)c->d_bd, A, P, iter, c->rg_flags, c->nblocks, c->rg_ctl);
-            hipLaunchKernelGGL(k_ridge_tracers<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, P, iter, (const int *)c->rg_flags, c->nblocks);
-        }
+        with_ncat(ncat, [&](auto NC) {
+            constexpr int nc = decltype(NC)::value;
+            hipLaunchKernelGGL(k_ridge_weights<nc>, g, b, 0, c->stream, s, c->p, (const BlockDesc *)c->d_bd, A, P, iter, c->rg_flags, c->nblocks, c->rg_ctl);
+            hipLaunchKernelGGL(k_ridge_tracers<nc>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, P, iter, (const int *)c->rg_flags, c->nblocks);
+        });
         HIPCHK(c, hipGetLastError());
         // what the host learns per iteration: the stop key and whether any block repeats
         HIPCHK(c, hipMemcpyAsync(&h, c->rg_ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -3543,73 +3519,17 @@ extern "C" int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat
         stop[0] = reason; stop[1] = (int32_t)(h.key >> 44) + 1; stop[2] = (int32_t)(o % c->nxb) + 1; stop[3] = (int32_t)(o / c->nxb) + 1;
     }
     (void)iters;
-    for (int q = 0; q < NARR; q++)
-        if (staged[q] && arr[q].out) HIPCHK(c, hipMemcpyAsync(arr[q].host, *arr[q].slot, sizeof(double) * arr[q].n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stage_out(c, arr)) return 1;
     return reason ? EVPK_RIDGE_STOP : 0;
 }
 
 // ---- cleanup_itd and aggregate (source/ice_itd.F90:1514-1769, :246-458) on the caller's state arrays: the rest of step_ridge / step_dynamics
 // (kernels in evpk_itd.hip) ----
-// the per-tracer tables of ItdArgs: how aicen * trcrn is built (shift_ice :919-975, aggregate :348-433) and compute_tracers (:1407-1499), their
-// branches in the reference's order
+// the tracer indices and per-tracer tables of ItdArgs
 static int itd_tables(evpk_ctx *c, const char *who, ItdArgs &A, int32_t ntrcr, const int32_t *trcr_depend, const evpk_itd_tracers *t) {
-    const int nts[] = {t->nt_Tsfc, t->nt_qice, t->nt_qsno, t->nt_alvl, t->nt_apnd, t->nt_hpnd, t->nt_fbri};
-    for (int q : nts) if (q < 0 || q > ntrcr) FAIL(c, "%s: tracer index %d not in 0..ntrcr = %d", who, q, ntrcr);
-    if (t->nilyr < 0 || (t->nilyr > 0 && (t->nt_qice < 1 || t->nt_qice + t->nilyr - 1 > ntrcr))) FAIL(c, "%s: nt_qice / nilyr beyond ntrcr", who);
-    if (t->nslyr < 0 || (t->nslyr > 0 && (t->nt_qsno < 1 || t->nt_qsno + t->nslyr - 1 > ntrcr))) FAIL(c, "%s: nt_qsno / nslyr beyond ntrcr", who);
-    if (t->tr_pond_topo && (t->nt_apnd < 1 || t->nt_hpnd < 1)) FAIL(c, "%s: tr_pond_topo without nt_apnd / nt_hpnd", who);
-    if (t->tr_pond_lvl && t->nt_apnd > 0 && t->nt_alvl < 1) FAIL(c, "%s: tr_pond_lvl without nt_alvl", who);
+    if (tracer_tables(c, who, A, ntrcr, trcr_depend, *t)) return 1;
     A.nt_Tsfc = t->nt_Tsfc; A.nt_qice = t->nt_qice; A.nilyr = t->nilyr; A.nt_qsno = t->nt_qsno; A.nslyr = t->nslyr; A.nt_alvl = t->nt_alvl;
     A.nt_apnd = t->nt_apnd; A.nt_hpnd = t->nt_hpnd; A.nt_fbri = t->nt_fbri; A.tr_pond_topo = t->tr_pond_topo ? 1 : 0; A.tr_brine = t->tr_brine ? 1 : 0;
-    const bool pond_at = t->tr_pond_cesm || t->tr_pond_topo;
-    for (int it = 1; it <= ntrcr; it++) {
-        const int dep = trcr_depend[it - 1], k = it - 1;
-        A.acc[k] = -1; A.rule[k] = -1; A.d1[k] = 0; A.d2[k] = 0; A.slot[k] = 0;
-        if (dep == 0) { A.acc[k] = 0; A.rule[k] = 1; }
-        else if (dep == 1) { A.acc[k] = 1; A.rule[k] = 2; }
-        else if (dep == 2) { A.acc[k] = 2; A.rule[k] = 3; }
-        else if (t->nt_alvl > 0 && dep == 2 + t->nt_alvl) { A.acc[k] = 3; A.rule[k] = 4; A.d1[k] = 1; }
-        else if (t->nt_apnd > 0 && dep == 2 + t->nt_apnd && pond_at) { A.acc[k] = 4; A.rule[k] = 4; A.d1[k] = 2; }
-        else if (t->nt_apnd > 0 && dep == 2 + t->nt_apnd && t->tr_pond_lvl) { A.acc[k] = 5; A.rule[k] = 5; A.d1[k] = 1; A.d2[k] = 2; }
-        else if (t->nt_fbri > 0 && dep == 2 + t->nt_fbri) { A.acc[k] = 6; A.rule[k] = 6; A.d1[k] = 3; }
-        if (it == t->nt_Tsfc) A.rule[k] = 0;            // compute_tracers asks for nt_Tsfc first (:1408)
-        if (it == t->nt_alvl) A.slot[k] = 1;
-        else if (it == t->nt_apnd) A.slot[k] = 2;
-        else if (it == t->nt_fbri) A.slot[k] = 3;
-    }
-    return 0;
-}
-
-// the caller's arrays of one call: in place where the device sees them, else through a staging copy (up, and down again at the end)
-struct ItdArr { void *host; size_t bytes; void **slot; bool out; bool staged; };
-static int itd_stage_in(evpk_ctx *c, ItdArr *arr, int n, double **pool_p = nullptr, size_t *pool_n_p = nullptr) {
-    double *&pool = pool_p ? *pool_p : c->rg_stage;
-    size_t &pool_n = pool_n_p ? *pool_n_p : c->rg_stage_n;
-    size_t need = 0;
-    for (int q = 0; q < n; q++) {
-        *arr[q].slot = (arr[q].host && arr[q].bytes) ? mapped_alias(arr[q].host, arr[q].bytes) : nullptr;
-        arr[q].staged = arr[q].host && arr[q].bytes && !*arr[q].slot;
-        if (arr[q].staged) need += (arr[q].bytes + 7) / 8;
-    }
-    if (pool_n < need) {
-        if (pool) (void)hipFree(pool);
-        pool = nullptr; pool_n = 0;
-        HIPCHK(c, hipMalloc(&pool, sizeof(double) * need));
-        pool_n = need;
-    }
-    double *q2 = pool;
-    for (int q = 0; q < n; q++)
-        if (arr[q].staged) {
-            HIPCHK(c, hipMemcpyAsync(q2, arr[q].host, arr[q].bytes, hipMemcpyHostToDevice, c->stream));
-            *arr[q].slot = q2; q2 += (arr[q].bytes + 7) / 8;
-        }
-    return 0;
-}
-static int itd_stage_out(evpk_ctx *c, ItdArr *arr, int n) {
-    for (int q = 0; q < n; q++)
-        if (arr[q].staged && arr[q].out) HIPCHK(c, hipMemcpyAsync(arr[q].host, *arr[q].slot, arr[q].bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -3643,39 +3563,29 @@ extern "C" int evpk_cleanup_itd(evpk_ctx *c, double dt, int32_t ncat, int32_t nt
     A.dt = dt; A.Tocnfrz = k->Tocnfrz; A.salinity = k->ice_ref_salinity; A.hs_min = k->hs_min; A.cp_ice = k->cp_ice; A.Lfresh = k->Lfresh;
     A.Tmin = k->Tmin; A.puny = k->puny; A.rhoi = c->p.rhoi; A.rhos = c->p.rhos;
     for (int n = 0; n <= ncat; n++) A.hin_max[n] = hin_max[n];
-    const size_t nblk = (size_t)c->nyb * c->nxb, nb = (size_t)c->nblocks, N = nb * nblk, d8 = sizeof(double);
-    ItdArr arr[] = {
-        {aicen, N * ncat * d8, (void **)&A.aicen, true}, {vicen, N * ncat * d8, (void **)&A.vicen, true}, {vsnon, N * ncat * d8, (void **)&A.vsnon, true},
-        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim * d8, (void **)&A.trcrn, true}, {aice0, N * d8, (void **)&A.aice0, true},
-        {aice, N * d8, (void **)&A.aice, true}, {fpond, N * d8, (void **)&A.fpond, true}, {fresh, N * d8, (void **)&A.fresh, true},
-        {fsalt, N * d8, (void **)&A.fsalt, true}, {fhocn, N * d8, (void **)&A.fhocn, true},
-        {first_ice, N * ncat * sizeof(int32_t), (void **)&A.first_ice, true}};
-    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
-    if (itd_stage_in(c, arr, NARR)) return 1;
-    if (c->itd_bmask_n < nb) {
-        if (c->itd_bmask) (void)hipFree(c->itd_bmask);
-        c->itd_bmask = nullptr; c->itd_bmask_n = 0;
-        HIPCHK(c, hipMalloc(&c->itd_bmask, sizeof(unsigned) * nb));
-        c->itd_bmask_n = nb;
-    }
+    const size_t nb = (size_t)c->nblocks, N = nb * c->nyb * c->nxb;
+    std::vector<HostArr> arr = {
+        {aicen, N * ncat, &A.aicen, true}, {vicen, N * ncat, &A.vicen, true}, {vsnon, N * ncat, &A.vsnon, true},
+        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim, &A.trcrn, true}, {aice0, N, &A.aice0, true}, {aice, N, &A.aice, true},
+        {fpond, N, &A.fpond, true}, {fresh, N, &A.fresh, true}, {fsalt, N, &A.fsalt, true}, {fhocn, N, &A.fhocn, true},
+        {first_ice, N * ncat, &A.first_ice, true}};
+    if (stage_in(c, arr)) return 1;
+    HIPCHK(c, grow(c, c->itd_bmask, c->itd_bmask_n, nb));
     if (!c->itd_key) HIPCHK(c, hipMalloc(&c->itd_key, sizeof(unsigned long long)));
     HIPCHK(c, hipMemsetAsync(c->itd_bmask, 0, sizeof(unsigned) * nb, c->stream));
     HIPCHK(c, hipMemsetAsync(c->itd_key, 0xff, sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
-    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
-    if (ncat == 5) {
-        hipLaunchKernelGGL(k_itd_scan<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, c->itd_bmask, c->itd_key);
-        hipLaunchKernelGGL(k_itd_shift<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask);
-        hipLaunchKernelGGL(k_itd_zap<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask, c->itd_key);
-    } else {
-        hipLaunchKernelGGL(k_itd_scan<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, c->itd_bmask, c->itd_key);
-        hipLaunchKernelGGL(k_itd_shift<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask);
-        hipLaunchKernelGGL(k_itd_zap<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask, c->itd_key);
-    }
+    const dim3 b(64), g = block_grid(c);
+    with_ncat(ncat, [&](auto NC) {
+        constexpr int nc = decltype(NC)::value;
+        hipLaunchKernelGGL(k_itd_scan<nc>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, c->itd_bmask, c->itd_key);
+        hipLaunchKernelGGL(k_itd_shift<nc>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask);
+        hipLaunchKernelGGL(k_itd_zap<nc>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, (const unsigned *)c->itd_bmask, c->itd_key);
+    });
     HIPCHK(c, hipGetLastError());
     unsigned long long key = ~0ull;
     HIPCHK(c, hipMemcpyAsync(&key, c->itd_key, sizeof(key), hipMemcpyDeviceToHost, c->stream));
-    if (itd_stage_out(c, arr, NARR)) return 1;
+    if (stage_out(c, arr)) return 1;
     if (key == ~0ull) return 0;
     const int stage = (int)((key >> 40) & 0xff), sub = (int)((key >> 32) & 0xff);
     const unsigned code = (unsigned)(key & 0xffffffffull);
@@ -3689,30 +3599,14 @@ extern "C" int evpk_cleanup_itd(evpk_ctx *c, double dt, int32_t ncat, int32_t nt
 // bound_state (ice_state.F90:173-238): ice_HaloUpdate, centre scalar, of aicen, trcrn(1:ntrcr), vicen, vsnon on the device -- the planes go
 // through the scratch state planes and the general update, as evpk_halo_update's do (fill 0 next to an eliminated land block)
 static int itd_bound_state(evpk_ctx *c, const ItdArgs &A) {
-    Slab &s = c->s;
     const size_t nn = (size_t)c->nyb * c->nxb;
-    struct Pl { double *p; size_t bstride; };
-    std::vector<Pl> pl;
+    std::vector<BlockPlane> pl;
     for (int n = 0; n < A.ncat; n++) pl.push_back({A.aicen + (size_t)n * nn, (size_t)A.ncat * nn});
     for (int n = 0; n < A.ncat; n++)
         for (int it = 0; it < A.ntrcr; it++) pl.push_back({A.trcrn + ((size_t)n * A.ntrcr_dim + it) * nn, (size_t)A.ncat * A.ntrcr_dim * nn});
     for (int n = 0; n < A.ncat; n++) pl.push_back({A.vicen + (size_t)n * nn, (size_t)A.ncat * nn});
     for (int n = 0; n < A.ncat; n++) pl.push_back({A.vsnon + (size_t)n * nn, (size_t)A.ncat * nn});
-    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
-    const int chunk = std::min(c->max_nf, (int)NSTATE), np = (int)pl.size();
-    for (int k0 = 0; k0 < np; k0 += chunk) {
-        const int nf = std::min(chunk, np - k0);
-        for (int q = 0; q < nf; q++) {
-            if (!c->full_cover) hipLaunchKernelGGL(k_fill_plane, grid2d(s, B2D), B2D, 0, c->stream, s, (int)F_STATE2 + q, 0.0);
-            LAUNCH_BLOCKS(k_gather_fs, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)pl[k0 + q].p, pl[k0 + q].bstride, (int)F_STATE2 + q);
-        }
-        if (halo(c, F_STATE2, nf, false, false, 0.0)) return 1;
-        for (int q = 0; q < nf; q++)
-            LAUNCH_BLOCKS(k_scatter_halo, g, b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (int)F_STATE2 + q, pl[k0 + q].p, pl[k0 + q].bstride, 0.0,
-                          c->ew == EVPK_BND_CYCLIC ? 1 : 0, c->ns == EVPK_BND_TRIPOLE ? 1 : 0, 0, 0, -1);
-    }
-    HIPCHK(c, hipGetLastError());
-    return 0;
+    return block_planes_halo(c, pl, 1, 1, 0.0);          // centre scalars
 }
 
 // k_bound_state finds the block of a global cell as (column, row) of a uniform tiling: true of what create_blocks makes -- every block
@@ -3751,7 +3645,7 @@ static int itd_bound_direct(evpk_ctx *c, const ItdArgs &A) {
 }
 
 // EVPK_BOUND_DIRECT=0 (read per call): the plane-by-plane path, the A/B partner and the pinned definition
-static bool bound_direct_env() { return !(getenv("EVPK_BOUND_DIRECT") && atoi(getenv("EVPK_BOUND_DIRECT")) == 0); }
+static bool bound_direct_env() { return env_on("EVPK_BOUND_DIRECT"); }
 
 extern "C" int evpk_bound_state(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, double *aicen, double *vicen, double *vsnon,
                                 double *trcrn) {
@@ -3767,15 +3661,13 @@ extern "C" int evpk_bound_state(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_
     if (direct && !bound_direct_ok(c)) FAIL(c, "evpk_bound_state: the blocks are not the uniform tiling of create_blocks (EVPK_BOUND_DIRECT=0 takes the plane-by-plane path)");
     ItdArgs A{};
     A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
-    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, d8 = sizeof(double);
-    ItdArr arr[] = {
-        {aicen, N * ncat * d8, (void **)&A.aicen, true}, {vicen, N * ncat * d8, (void **)&A.vicen, true}, {vsnon, N * ncat * d8, (void **)&A.vsnon, true},
-        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim * d8, (void **)&A.trcrn, true}};
-    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
-    if (itd_stage_in(c, arr, NARR)) return 1;
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb;
+    std::vector<HostArr> arr = {{aicen, N * ncat, &A.aicen, true}, {vicen, N * ncat, &A.vicen, true}, {vsnon, N * ncat, &A.vsnon, true},
+                                {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim, &A.trcrn, true}};
+    if (stage_in(c, arr)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
     if (direct ? itd_bound_direct(c, A) : itd_bound_state(c, A)) return 1;
-    if (itd_stage_out(c, arr, NARR)) return 1;
+    if (stage_out(c, arr)) return 1;
     return xp_check(c);
 }
 
@@ -3801,23 +3693,21 @@ extern "C" int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t nca
     HIPCHK(c, hipSetDevice(c->device));
     A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nt_iage = nt_iage;
     A.dt = dt; A.Tocnfrz = Tocnfrz; A.puny = 1.0e-11;
-    const size_t nblk = (size_t)c->nyb * c->nxb, nb = (size_t)c->nblocks, N = nb * nblk, d8 = sizeof(double);
-    const bool bnd = bound != 0;
-    ItdArr arr[] = {
-        {aicen, N * ncat * d8, (void **)&A.aicen, bnd}, {vicen, N * ncat * d8, (void **)&A.vicen, bnd}, {vsnon, N * ncat * d8, (void **)&A.vsnon, bnd},
-        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim * d8, (void **)&A.trcrn, bnd}, {aice0, N * d8, (void **)&A.aice0, true},
-        {aice, N * d8, (void **)&A.aice, true}, {vice, N * d8, (void **)&A.vice, true}, {vsno, N * d8, (void **)&A.vsno, true},
-        {ntrcr ? trcr : nullptr, N * ntrcr_dim * d8, (void **)&A.trcr, true}, {daidtd, N * d8, (void **)&A.daidtd, true},
-        {dvidtd, N * d8, (void **)&A.dvidtd, true}, {dagedtd, N * d8, (void **)&A.dagedtd, true}};
-    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
-    if (itd_stage_in(c, arr, NARR)) return 1;
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb;
+    const bool bnd = bound != 0;          // (without bound_state the category arrays are inputs)
+    std::vector<HostArr> arr = {
+        {aicen, N * ncat, &A.aicen, bnd}, {vicen, N * ncat, &A.vicen, bnd}, {vsnon, N * ncat, &A.vsnon, bnd},
+        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim, &A.trcrn, bnd}, {aice0, N, &A.aice0, true}, {aice, N, &A.aice, true},
+        {vice, N, &A.vice, true}, {vsno, N, &A.vsno, true}, {ntrcr ? trcr : nullptr, N * ntrcr_dim, &A.trcr, true},
+        {daidtd, N, &A.daidtd, true}, {dvidtd, N, &A.dvidtd, true}, {dagedtd, N, &A.dagedtd, true}};
+    if (stage_in(c, arr)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
     if (bnd && ((bound_direct_env() && bound_direct_ok(c)) ? itd_bound_direct(c, A) : itd_bound_state(c, A))) return 1;
-    const dim3 b(64), g((c->nxb + 63) / 64, c->nyb, c->nblocks);
-    if (ncat == 5) hipLaunchKernelGGL(k_itd_aggregate<5>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
-    else hipLaunchKernelGGL(k_itd_aggregate<0>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
+    with_ncat(ncat, [&](auto NC) {
+        hipLaunchKernelGGL(k_itd_aggregate<decltype(NC)::value>, block_grid(c), dim3(64), 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
+    });
     HIPCHK(c, hipGetLastError());
-    if (itd_stage_out(c, arr, NARR)) return 1;
+    if (stage_out(c, arr)) return 1;
     return xp_check(c);
 }
 
@@ -3935,14 +3825,8 @@ static int remap_impl(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, doub
     const int ncp = ncat + 1, ntp = ncat * ntrace;
     const size_t np = mask_elems(s), nblk = (size_t)c->nyb * c->nxb;
     const size_t nplanes = (size_t)5 * ncp + (size_t)6 * ntp;
-    if (c->rm_pool_n < nplanes * np) {
-        if (c->rm_pool) (void)hipFree(c->rm_pool);
-        c->rm_pool = nullptr; c->rm_pool_n = 0;
-        if (hipMalloc(&c->rm_pool, sizeof(double) * nplanes * np) != hipSuccess)
-            FAIL(c, "evpk_transport_remap: %zu planes of %zu cells do not fit on the device", nplanes, np);
-        c->rm_pool_n = nplanes * np;
-        HIPCHK(c, hipMemsetAsync(c->rm_pool, 0, sizeof(double) * nplanes * np, c->stream));
-    }
+    if (grow(c, c->rm_pool, c->rm_pool_n, nplanes * np, true) != hipSuccess)
+        FAIL(c, "evpk_transport_remap: %zu planes of %zu cells do not fit on the device", nplanes, np);
     // pointer tables: [0, nplanes) the planes in RemapPlanes order; then the two halo lists
     //   A (before construct_fields): mm, tm -- scalars;   B: tc -- scalars, then mx, my, tx, ty -- vectors
     std::vector<double *> tab(nplanes);
@@ -3959,14 +3843,8 @@ static int remap_impl(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, doub
     for (int q = 0; q < ntp; q++) { lst.push_back(tab[o_tx + q]); sg.push_back(-1); }
     for (int q = 0; q < ntp; q++) { lst.push_back(tab[o_ty + q]); sg.push_back(-1); }
     const size_t nBv = lst.size() - nA - nBs, nall = nplanes + lst.size();
-    if (c->rm_tab_n < nall) {
-        if (c->rm_tab) (void)hipFree(c->rm_tab);
-        if (c->rm_sgn) (void)hipFree(c->rm_sgn);
-        c->rm_tab = nullptr; c->rm_sgn = nullptr; c->rm_tab_n = 0;
-        HIPCHK(c, hipMalloc(&c->rm_tab, sizeof(double *) * nall));
-        HIPCHK(c, hipMalloc(&c->rm_sgn, nall));
-        c->rm_tab_n = nall;
-    }
+    HIPCHK(c, grow(c, c->rm_tab, c->rm_tab_n, nall));
+    HIPCHK(c, grow(c, c->rm_sgn, c->rm_sgn_n, nall));
     HIPCHK(c, hipMemcpyAsync(c->rm_tab, tab.data(), sizeof(double *) * nplanes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->rm_tab + nplanes, lst.data(), sizeof(double *) * lst.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->rm_sgn, sg.data(), sg.size(), hipMemcpyHostToDevice, c->stream));
@@ -3979,26 +3857,11 @@ static int remap_impl(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, doub
     const int nrg = (c->nyb + 3) / 4;
     if ((long long)nrg * c->nblocks > 65535 || ntp > 65535) FAIL(c, "evpk_transport_remap: too many blocks for one launch");
     double *dmm = nullptr, *dtm = nullptr;
-    bool st_mm = false, st_tm = false;
     RemapState io{};
-    double *host5[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t n5[5] = {0, 0, 0, 0, 0};
-    bool staged5[5] = {false, false, false, false, false};
+    std::vector<HostArr> arr;
     if (!st) {
-        dmm = (double *)mapped_alias(mm, sizeof(double) * n_mm); dtm = ntp ? (double *)mapped_alias(tm, sizeof(double) * n_tm) : nullptr;
-        st_mm = !dmm; st_tm = ntp && !dtm;
-        if (st_mm || st_tm) {
-            const size_t need = (st_mm ? n_mm : 0) + (st_tm ? n_tm : 0);
-            if (c->rm_stage_n < need) {
-                if (c->rm_stage) (void)hipFree(c->rm_stage);
-                c->rm_stage = nullptr; c->rm_stage_n = 0;
-                HIPCHK(c, hipMalloc(&c->rm_stage, sizeof(double) * need));
-                c->rm_stage_n = need;
-            }
-            double *q = c->rm_stage;
-            if (st_mm) { HIPCHK(c, hipMemcpyAsync(q, mm, sizeof(double) * n_mm, hipMemcpyHostToDevice, c->stream)); dmm = q; q += n_mm; }
-            if (st_tm) { HIPCHK(c, hipMemcpyAsync(q, tm, sizeof(double) * n_tm, hipMemcpyHostToDevice, c->stream)); dtm = q; }
-        }
+        arr = {{mm, n_mm, &dmm, true}, {tm, n_tm, &dtm, true}};
+        if (stage_in(c, arr)) return 1;
         // mm(nx_block, ny_block, 0:ncat, max_blocks), tm(nx_block, ny_block, ntrace, ncat, max_blocks) -> planes, one launch per array
         hipLaunchKernelGGL(k_gather_planes, dim3((c->nxb + 63) / 64, nrg * c->nblocks, ncp), b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, (const double *)dmm,
                            nblk, (size_t)ncp * nblk, (double *const *)c->rm_tab, nrg);
@@ -4008,26 +3871,10 @@ static int remap_impl(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, doub
     } else {
         // aice0, aicen, vicen, vsnon, trcrn: state_to_tracers inside the gather
         io = *st;
-        host5[0] = st->aice0; host5[1] = st->aicen; host5[2] = st->vicen; host5[3] = st->vsnon; host5[4] = st->trcrn;
-        n5[0] = (size_t)c->nblocks * nblk; n5[1] = n5[2] = n5[3] = n5[0] * ncat; n5[4] = n5[0] * ncat * st->ntrcr_dim;
-        double **dev5[5] = {&io.aice0, &io.aicen, &io.vicen, &io.vsnon, &io.trcrn};
-        size_t need = 0;
-        for (int q = 0; q < 5; q++) {
-            *dev5[q] = host5[q] ? (double *)mapped_alias(host5[q], sizeof(double) * n5[q]) : nullptr;
-            staged5[q] = host5[q] && !*dev5[q];
-            if (staged5[q]) need += n5[q];
-        }
-        if (need) {
-            if (c->rm_stage_n < need) {
-                if (c->rm_stage) (void)hipFree(c->rm_stage);
-                c->rm_stage = nullptr; c->rm_stage_n = 0;
-                HIPCHK(c, hipMalloc(&c->rm_stage, sizeof(double) * need));
-                c->rm_stage_n = need;
-            }
-            double *q2 = c->rm_stage;
-            for (int q = 0; q < 5; q++)
-                if (staged5[q]) { HIPCHK(c, hipMemcpyAsync(q2, host5[q], sizeof(double) * n5[q], hipMemcpyHostToDevice, c->stream)); *dev5[q] = q2; q2 += n5[q]; }
-        }
+        const size_t N = (size_t)c->nblocks * nblk;
+        arr = {{st->aice0, N, &io.aice0, true}, {st->aicen, N * ncat, &io.aicen, true}, {st->vicen, N * ncat, &io.vicen, true},
+               {st->vsnon, N * ncat, &io.vsnon, true}, {st->trcrn, N * ncat * st->ntrcr_dim, &io.trcrn, true}};
+        if (stage_in(c, arr)) return 1;
         hipLaunchKernelGGL(k_state_gather, dim3((c->nxb + 63) / 64, nrg * c->nblocks, ncp), b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, io, P, nrg);
     }
     HIPCHK(c, hipGetLastError());
@@ -4046,15 +3893,13 @@ static int remap_impl(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, doub
     // three kernels that hand fe, fn, tfe, tfn over through HBM)
     bool remap_direct = false;
     const size_t flux_lds = sizeof(double) * 2 * 256 * (size_t)(1 + ntrace);
-    const bool fused_env = !(getenv("EVPK_REMAP_FUSED") && atoi(getenv("EVPK_REMAP_FUSED")) == 0);
-    if (fused_env && flux_lds <= 60 * 1024) {
+    if (env_on("EVPK_REMAP_FUSED") && flux_lds <= 60 * 1024) {
         const long long ntiles = (long long)((s.nxl + RM_TILE - 2) / (RM_TILE - 1)) * ((s.nyl + RM_TILE - 2) / (RM_TILE - 1)) * ncp;
         // without the state transforms the update delivers straight into the caller's arrays (device-visible, or the staged copy
         // that is sent back below): no scatter pass.  A bad departure point leaves them untouched (the kernel looks at the flag
         // k_remap_dp set); a negative mass is found while they are being written -- the reference aborts the run there
         // (:3622-3640), the arrays are then undefined (include/evpk.h).  EVPK_REMAP_DIRECT=0: planes + scatter as before.
-        const bool direct_env = !(getenv("EVPK_REMAP_DIRECT") && atoi(getenv("EVPK_REMAP_DIRECT")) == 0);
-        remap_direct = !st && direct_env;
+        remap_direct = !st && env_on("EVPK_REMAP_DIRECT");
         RmOut O{};
         if (remap_direct) {
             if (remap_block_map(c)) return 1;
@@ -4092,8 +3937,6 @@ static int remap_impl(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, doub
                                (double *const *)(c->rm_tab + o_tm), dtm, nblk, (size_t)ntp * nblk, nrg);
         }
         HIPCHK(c, hipGetLastError());
-        if (st_mm) HIPCHK(c, hipMemcpyAsync(mm, dmm, sizeof(double) * n_mm, hipMemcpyDeviceToHost, c->stream));
-        if (st_tm) HIPCHK(c, hipMemcpyAsync(tm, dtm, sizeof(double) * n_tm, hipMemcpyDeviceToHost, c->stream));
     } else {
         // bound_state: the ghost ring of the NEW areas and tracers, then tracers_to_state on every cell of every block
         if (planes_halo(c, dl, c->rm_sgn, (int)nA, false)) return 1;
@@ -4106,12 +3949,8 @@ static int remap_impl(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, doub
         }
         hipLaunchKernelGGL(k_state_scatter, dim3((c->nxb + 63) / 64, nrg * c->nblocks, ncp), b, 0, c->stream, s, c->d_bd, c->nxb, c->nyb, io, P, nrg);
         HIPCHK(c, hipGetLastError());
-        double *dev5[5] = {io.aice0, io.aicen, io.vicen, io.vsnon, io.trcrn};
-        for (int q = 0; q < 5; q++)
-            if (staged5[q]) HIPCHK(c, hipMemcpyAsync(host5[q], dev5[q], sizeof(double) * n5[q], hipMemcpyDeviceToHost, c->stream));
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return stage_out(c, arr);
 }
 
 extern "C" int evpk_transport_remap(evpk_ctx *c, double dt, int32_t ncat, int32_t ntrace, double *mm, double *tm, const int32_t *tracer_type,
@@ -4196,33 +4035,27 @@ extern "C" int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t s
     HIPCHK(c, hipSetDevice(c->device));
     // the union of the caller's arrays, each staged once (or used in place): the stages then see device pointers only
     evpk_dyn_args x = *a;
-    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, d8 = sizeof(double), n3 = N * a->ncat * d8;
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
     const bool tr = a->ntrcr > 0;
-    ItdArr arr[] = {
-        {a->aice0, N * d8, (void **)&x.aice0, true}, {a->aicen, n3, (void **)&x.aicen, true}, {a->vicen, n3, (void **)&x.vicen, true},
-        {a->vsnon, n3, (void **)&x.vsnon, true}, {tr ? a->trcrn : nullptr, n3 * a->ntrcr_dim, (void **)&x.trcrn, true},
-        {a->aice, N * d8, (void **)&x.aice, true}, {a->vice, N * d8, (void **)&x.vice, true}, {a->vsno, N * d8, (void **)&x.vsno, true},
-        {tr ? a->trcr : nullptr, N * a->ntrcr_dim * d8, (void **)&x.trcr, true},
-        {a->daidtd, N * d8, (void **)&x.daidtd, true}, {a->dvidtd, N * d8, (void **)&x.dvidtd, true}, {a->dagedtd, N * d8, (void **)&x.dagedtd, true},
-        {a->fpond, N * d8, (void **)&x.fpond, true}, {a->fresh, N * d8, (void **)&x.fresh, true}, {a->fsalt, N * d8, (void **)&x.fsalt, true},
-        {a->fhocn, N * d8, (void **)&x.fhocn, true}, {a->first_ice, N * a->ncat * sizeof(int32_t), (void **)&x.first_ice, true},
-        {a->ridge ? const_cast<double *>(a->rdg_conv) : nullptr, N * d8, (void **)&x.rdg_conv, false},
-        {a->ridge ? const_cast<double *>(a->rdg_shear) : nullptr, N * d8, (void **)&x.rdg_shear, false},
-        {dg.dardg1dt, N * d8, (void **)&dg.dardg1dt, true}, {dg.dardg2dt, N * d8, (void **)&dg.dardg2dt, true}, {dg.dvirdgdt, N * d8, (void **)&dg.dvirdgdt, true},
-        {dg.opening, N * d8, (void **)&dg.opening, true}, {dg.dardg1ndt, n3, (void **)&dg.dardg1ndt, true}, {dg.dardg2ndt, n3, (void **)&dg.dardg2ndt, true},
-        {dg.dvirdgndt, n3, (void **)&dg.dvirdgndt, true}, {dg.aparticn, n3, (void **)&dg.aparticn, true}, {dg.krdgn, n3, (void **)&dg.krdgn, true},
-        {dg.araftn, n3, (void **)&dg.araftn, true}, {dg.vraftn, n3, (void **)&dg.vraftn, true}, {dg.aredistn, n3, (void **)&dg.aredistn, true},
-        {dg.vredistn, n3, (void **)&dg.vredistn, true}};
-    constexpr int NARR = sizeof(arr) / sizeof(arr[0]);
-    if (!a->ridge)          // (the diagnostics belong to ridge_ice alone)
-        for (int q = 19; q < NARR; q++) arr[q].host = nullptr;
-    if (itd_stage_in(c, arr, NARR, &c->dyn_stage, &c->dyn_stage_n)) return 1;
+    std::vector<HostArr> arr = {
+        {a->aice0, N, &x.aice0, true}, {a->aicen, n3, &x.aicen, true}, {a->vicen, n3, &x.vicen, true}, {a->vsnon, n3, &x.vsnon, true},
+        {tr ? a->trcrn : nullptr, n3 * a->ntrcr_dim, &x.trcrn, true}, {a->aice, N, &x.aice, true}, {a->vice, N, &x.vice, true},
+        {a->vsno, N, &x.vsno, true}, {tr ? a->trcr : nullptr, N * a->ntrcr_dim, &x.trcr, true}, {a->daidtd, N, &x.daidtd, true},
+        {a->dvidtd, N, &x.dvidtd, true}, {a->dagedtd, N, &x.dagedtd, true}, {a->fpond, N, &x.fpond, true}, {a->fresh, N, &x.fresh, true},
+        {a->fsalt, N, &x.fsalt, true}, {a->fhocn, N, &x.fhocn, true}, {a->first_ice, n3, &x.first_ice, true}};
+    if (a->ridge) {         // (the rates and the diagnostics belong to ridge_ice alone)
+        arr.push_back({a->rdg_conv, N, &x.rdg_conv, false}); arr.push_back({a->rdg_shear, N, &x.rdg_shear, false});
+        for (double **p : {&dg.dardg1dt, &dg.dardg2dt, &dg.dvirdgdt, &dg.opening}) arr.push_back({*p, N, p, true});
+        for (double **p : {&dg.dardg1ndt, &dg.dardg2ndt, &dg.dvirdgndt, &dg.aparticn, &dg.krdgn, &dg.araftn, &dg.vraftn, &dg.aredistn, &dg.vredistn})
+            arr.push_back({*p, n3, p, true});
+    }
+    if (stage_in(c, arr, true)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
     dg.fpond = x.fpond; dg.fresh = x.fresh; dg.fhocn = x.fhocn;
     const int rc = dyn_stages(c, x, &dg, stop);
     if (rc == 1) return 1;
     const std::string keep = c->err;
-    if (itd_stage_out(c, arr, NARR)) return 1;
+    if (stage_out(c, arr)) return 1;
     if (rc) c->err = keep;
     return rc;
 }
