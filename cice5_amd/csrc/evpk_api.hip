@@ -350,6 +350,10 @@ struct evpk_ctx {
     unsigned long long *itd_key = nullptr;
     // evpk_bound_state: whether the blocks are the uniform tiling k_bound_state's block table assumes (0 not looked at yet, 1 yes, -1 no)
     int bs_uniform = 0;
+    // ... on x-slab ranks (itd_bound_ranks): local message buffers of the transports without mapped slots, [send | recv] per partner;
+    // rounds and planes of the last bound_state (evpk_stats)
+    double *br_buf = nullptr; size_t br_buf_n = 0;
+    int bs_rounds = 0, bs_planes = 0;
     // evpk_step_dynamics: check_only makes the stage routines return after their argument checks, before the first copy or launch
     bool check_only = false;
     // EAP (kdyn = 2): set by evpk_eap_init -- the subcycle loop then runs stress_eap / stepu / stepa (evpk_eap.hip)
@@ -1367,7 +1371,7 @@ static void destroy_impl(evpk_ctx *c) {
     if (c->relay) { c->relay->close_(); delete c->relay; }
     if (c->ipc) { if (c->stream2) (void)hipStreamSynchronize(c->stream2); c->ipc->close_(); delete c->ipc; }
     void *ptrs[] = {c->itd, c->stage_itd, c->d_zflags, c->d_zrows, c->s.F, c->s.tmask, c->s.umask, c->s.iceumask, c->s.cmask, c->s.tmphm, c->d_bd, c->stage, c->d_flags,
-                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->call_stage, c->rm_grid, c->rm_pool, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->dyn_stage, c->d_ns2, c->d_bmap, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
+                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->call_stage, c->rm_grid, c->rm_pool, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->dyn_stage, c->d_ns2, c->d_bmap, c->br_buf, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -3424,13 +3428,22 @@ template <class Args> static int tracer_tables(evpk_ctx *c, const char *who, Arg
     return 0;
 }
 
+// The first check of the entry points of step_dynamics' second half, which run on x-slab ranks: a context of several ranks on which
+// nothing collective has happened yet is refused before any argument is read; a rank without a block column has nothing to do and is in
+// no exchange
+#define RANKS_ENTRY(c, who)                                                                                                  \
+    do {                                                                                                                     \
+        if ((c)->nranks > 1 && !(c)->connected) FAIL(c, who ": nranks = %d: the context is not connected yet (evpk_connect)", (c)->nranks); \
+        if ((c)->idle) return 0;                                                                                             \
+    } while (0)
+
 // ---- ridge_ice (source/ice_mechred.F90:101-746) on the caller's state arrays (kernels in evpk_ridge.hip) ----
 extern "C" int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
                               const evpk_ridge_tracers *t, const double *hin_max, const double *rdg_conv, const double *rdg_shear, double *aice0,
                               double *aicen, double *vicen, double *vsnon, double *trcrn, evpk_ridge_diag *diag, int32_t stop[4]) {
     if (!c) return 1;
     if (stop) stop[0] = stop[1] = stop[2] = stop[3] = 0;
-    if (c->nranks > 1) FAIL(c, "evpk_ridge_ice: nranks = %d: ridging on more than one rank is not supported yet", c->nranks);
+    RANKS_ENTRY(c, "evpk_ridge_ice");
     if (!t || !hin_max || !aice0 || !aicen || !vicen || !vsnon || !stop || ntrcr < 0 || ntrcr_dim < ntrcr || (ntrcr > 0 && (!trcrn || !trcr_depend)))
         FAIL(c, "evpk_ridge_ice: a required argument is missing");
     if (!c->connected) FAIL(c, "evpk_ridge_ice: the context is not connected yet (evpk_connect)");
@@ -3539,7 +3552,7 @@ extern "C" int evpk_cleanup_itd(evpk_ctx *c, double dt, int32_t ncat, int32_t nt
                                 double *fpond, double *fresh, double *fsalt, double *fhocn, int32_t *first_ice, int32_t stop[4]) {
     if (!c) return 1;
     if (stop) stop[0] = stop[1] = stop[2] = stop[3] = 0;
-    if (c->nranks > 1) FAIL(c, "evpk_cleanup_itd: nranks = %d: more than one rank is not supported yet", c->nranks);
+    RANKS_ENTRY(c, "evpk_cleanup_itd");
     if (!t || !hin_max || !k || !aice0 || !aice || !aicen || !vicen || !vsnon || !stop || ntrcr < 0 || ntrcr_dim < ntrcr ||
         (ntrcr > 0 && (!trcrn || !trcr_depend)))
         FAIL(c, "evpk_cleanup_itd: a required argument is missing");
@@ -3606,6 +3619,9 @@ static int itd_bound_state(evpk_ctx *c, const ItdArgs &A) {
         for (int it = 0; it < A.ntrcr; it++) pl.push_back({A.trcrn + ((size_t)n * A.ntrcr_dim + it) * nn, (size_t)A.ncat * A.ntrcr_dim * nn});
     for (int n = 0; n < A.ncat; n++) pl.push_back({A.vicen + (size_t)n * nn, (size_t)A.ncat * nn});
     for (int n = 0; n < A.ncat; n++) pl.push_back({A.vsnon + (size_t)n * nn, (size_t)A.ncat * nn});
+    c->bs_planes = (int)pl.size();
+    const int chunk = std::min(c->max_nf, (int)NSTATE);             // (block_planes_halo's: one fold + one ring exchange per chunk)
+    c->bs_rounds = c->nranks > 1 ? ((int)pl.size() + chunk - 1) / chunk : 0;
     return block_planes_halo(c, pl, 1, 1, 0.0);          // centre scalars
 }
 
@@ -3615,12 +3631,13 @@ static int remap_block_map(evpk_ctx *c);
 static bool bound_direct_ok(evpk_ctx *c) {
     if (!c->bs_uniform) {
         const int bsx = c->nxb - 2, bsy = c->nyb - 2;
-        bool ok = c->nranks == 1 && c->s.i0 == 1 && c->s.j0 == 1 && c->s.nxl == c->s.nxg && c->s.nyl == c->s.nyg;
+        // (x-slab ranks: the same tiling of the global grid on the rank's own block columns, which start the slab)
+        bool ok = c->s.j0 == 1 && c->s.nyl == c->s.nyg && (c->nranks > 1 ? (c->s.i0 - 1) % bsx == 0 : (c->s.i0 == 1 && c->s.nxl == c->s.nxg));
         for (int b = 0; ok && b < c->nblocks; b++) {
             const BlockDesc &d = c->bd[b];
             const int ci = (d.iglob_lo - 1) / bsx, cj = (d.jglob_lo - 1) / bsy;
             ok = d.iglob_lo == ci * bsx + 1 && d.jglob_lo == cj * bsy + 1 && d.ihi - d.ilo + 1 == std::min(bsx, c->s.nxg - ci * bsx) &&
-                 d.jhi - d.jlo + 1 == std::min(bsy, c->s.nyg - cj * bsy);
+                 d.jhi - d.jlo + 1 == std::min(bsy, c->s.nyg - cj * bsy) && d.iglob_lo >= c->s.i0 && d.iglob_lo + (d.ihi - d.ilo) < c->s.i0 + c->s.nxl;
         }
         c->bs_uniform = ok ? 1 : -1;
     }
@@ -3641,21 +3658,128 @@ static int itd_bound_direct(evpk_ctx *c, const ItdArgs &A) {
     const dim3 g((4 * (c->nxb + c->nyb) + BS_TX - 1) / BS_TX, c->nblocks, (B.nplanes + BS_PG - 1) / BS_PG);
     LAUNCH_BLOCKS(k_bound_state, g, dim3(BS_TX), 0, c->stream, (const BlockDesc *)c->d_bd, (const int *)c->d_bmap, B);
     HIPCHK(c, hipGetLastError());
+    c->bs_rounds = 0; c->bs_planes = B.nplanes;
+    return 0;
+}
+
+// bound_state across x-slab ranks (k_bound_pack -> one exchange -> k_bound_fill, evpk_itd.hip): every rank packs physical cells only --
+// its edge columns for the ring neighbours, its top row for its tripole fold partners -- into ONE message per partner, the ring and the
+// fold messages are posted together, and every ghost cell is then filled in one launch.  A message holds up to `ppr` planes; more planes
+// take more rounds.  ppr follows from quantities every rank shares (the slot size, wmax, ny_global, the plane count), never from the
+// rank's own slab width, so that all ranks post the same exchanges.  A rank whose blocks are all eliminated packs zeros and fills nothing.
+static int itd_bound_ranks(evpk_ctx *c, const ItdArgs &A) {
+    if (remap_block_map(c)) return 1;
+    Slab &s = c->s;
+    hipStream_t st = c->stream;
+    const int ch = xp_channel(c, st);
+    const size_t nn = (size_t)c->nyb * c->nxb;
+    BsArgs B{};
+    B.aicen = {A.aicen, (size_t)A.ncat * nn}; B.trcrn = {A.trcrn, (size_t)A.ncat * A.ntrcr_dim * nn};
+    B.vicen = {A.vicen, (size_t)A.ncat * nn}; B.vsnon = {A.vsnon, (size_t)A.ncat * nn};
+    B.ncat = A.ncat; B.ntrcr = A.ntrcr; B.ntrcr_dim = A.ntrcr_dim; B.nxb = c->nxb; B.nyb = c->nyb; B.nplanes = A.ncat * (3 + A.ntrcr);
+    B.nxg = s.nxg; B.nyg = s.nyg; B.bsx = c->nxb - 2; B.bsy = c->nyb - 2; B.nbx = c->bmap_nbx;
+    B.cyclic = c->ew == EVPK_BND_CYCLIC ? 1 : 0; B.tripole = c->ns == EVPK_BND_TRIPOLE ? 1 : 0;
+    if (c->nblocks > 65535) FAIL(c, "evpk_bound_state: %d blocks exceed one launch", c->nblocks);
+    // partners: the ring neighbours, then the fold partners that are not among them; what each message holds
+    struct Partner { int q; bool w, e, t; };
+    std::vector<Partner> P;
+    if (c->west >= 0) P.push_back({c->west, true, c->east == c->west, false});
+    if (c->east >= 0 && c->east != c->west) P.push_back({c->east, false, true, false});
+    if (B.tripole)
+        for (int q : c->fold_dst) {
+            bool found = false;
+            for (Partner &p : P) if (p.q == q) { p.t = true; found = true; }
+            if (!found) P.push_back({q, false, false, true});
+        }
+    if ((int)c->fold_dst.size() > BR_MAXT) FAIL(c, "evpk_bound_state: %d fold partners", (int)c->fold_dst.size());
+    // planes per round, the same on every rank
+    const size_t unit = (size_t)2 * s.nyg + c->wmax;
+    const size_t cap = c->ipc ? c->ipc->slot[ch] / sizeof(double) : c->relay ? c->relay->slot / sizeof(double) : unit * B.nplanes;
+    const int ppr = (int)std::min<size_t>((size_t)B.nplanes, cap / unit);
+    if (ppr < 1) FAIL(c, "evpk_bound_state: one plane's messages (%zu doubles) do not fit the transport's slot", unit);
+    const int rounds = (B.nplanes + ppr - 1) / ppr;
+    const size_t msgcap = (size_t)ppr * unit;             // doubles per message buffer
+    if (!c->ipc) HIPCHK(c, grow(c, c->br_buf, c->br_buf_n, 2 * P.size() * msgcap));
+    auto lsend = [&](size_t k) { return c->br_buf + k * msgcap; };
+    auto lrecv = [&](size_t k) { return c->br_buf + (P.size() + k) * msgcap; };
+    for (int r = 0; r < rounds; r++) {
+        BrArgs R{};
+        R.i0 = s.i0; R.i1 = s.i0 + s.nxl - 1; R.p0 = r * ppr; R.np = std::min(ppr, B.nplanes - R.p0);
+        const size_t col = (size_t)R.np * s.nyg;
+        std::vector<size_t> nsend(P.size()), nrecv(P.size());
+        for (size_t k = 0; k < P.size(); k++) {
+            const Partner &p = P[k];
+            // (peer-mapped: the page of the NEXT message, before the signal / wait turn it)
+            double *snd = c->ipc ? ipc_send_ptr(c, ch, p.q, 0) : lsend(k);
+            const double *rcv = c->ipc ? ipc_recv_ptr(c, ch, p.q, 0) : lrecv(k);
+            const int wq = c->slab_i0[p.q + 1] - c->slab_i0[p.q];
+            size_t o = 0;
+            if (p.w) { R.toW = snd + o; o += col; }
+            if (p.e) { R.toE = snd + o; o += col; }
+            if (p.t) { R.toT[R.nT++] = snd + o; o += (size_t)R.np * s.nxl; }
+            nsend[k] = o;
+            // the partner's message: its W section if this rank is its west neighbour (it is this rank's east one), and so on
+            o = 0;
+            if (p.e) { R.fromE = rcv + o; o += col; }
+            if (p.w) { R.fromW = rcv + o; o += col; }
+            if (p.t) { R.fromT[R.nS] = rcv + o; R.t_i0[R.nS] = c->slab_i0[p.q]; R.t_w[R.nS++] = wq; o += (size_t)R.np * wq; }
+            nrecv[k] = o;
+            if (nsend[k] > msgcap || nrecv[k] > msgcap) FAIL(c, "evpk_bound_state: message larger than its buffer");
+        }
+        const int ng = (R.np + BS_PG - 1) / BS_PG;
+        hipLaunchKernelGGL(k_bound_pack, dim3((std::max(s.nyg, s.nxl) + BS_TX - 1) / BS_TX, 3, ng), dim3(BS_TX), 0, st, (const BlockDesc *)c->d_bd,
+                           (const int *)c->d_bmap, B, R);
+        HIPCHK(c, hipGetLastError());
+        if (c->ipc) {
+            for (const Partner &p : P) if (ipc_signal(c, ch, p.q, st)) return 1;
+            for (const Partner &p : P) if (ipc_wait(c, ch, p.q, st)) return 1;
+        } else if (c->relay) {
+            int rc = 0;
+            for (size_t k = 0; k < P.size(); k++) rc |= c->relay->send(P[k].q, lsend(k), nsend[k] * 8, st);
+            for (size_t k = 0; k < P.size(); k++) rc |= c->relay->recv(P[k].q, lrecv(k), nrecv[k] * 8, st);
+            if (rc) FAIL(c, "shared-memory relay: bound_state exchange failed (%s)", rc & 2 ? "timeout" : "copy / size");
+        } else {
+            NCCLCHK(c, ncclGroupStart());
+            ncclResult_t rc = ncclSuccess;
+            auto keep = [&](ncclResult_t e) { if (rc == ncclSuccess) rc = e; };
+            for (size_t k = 0; k < P.size(); k++) if (nsend[k]) keep(ncclSend(lsend(k), nsend[k], ncclDouble, P[k].q, c->comm, st));
+            for (size_t k = 0; k < P.size(); k++) if (nrecv[k]) keep(ncclRecv(lrecv(k), nrecv[k], ncclDouble, P[k].q, c->comm, st));
+            const ncclResult_t rce = ncclGroupEnd();
+            if (rc != ncclSuccess) FAIL(c, "bound_state exchange: ncclSend/ncclRecv failed: %s", ncclGetErrorString(rc));
+            if (rce != ncclSuccess) FAIL(c, "bound_state exchange: ncclGroupEnd failed: %s", ncclGetErrorString(rce));
+        }
+        const dim3 g((4 * (c->nxb + c->nyb) + BS_TX - 1) / BS_TX, c->nblocks, ng);
+        if (g.y) hipLaunchKernelGGL(k_bound_fill, g, dim3(BS_TX), 0, st, (const BlockDesc *)c->d_bd, (const int *)c->d_bmap, B, R);
+        HIPCHK(c, hipGetLastError());
+    }
+    c->bs_rounds = rounds; c->bs_planes = B.nplanes;
     return 0;
 }
 
 // EVPK_BOUND_DIRECT=0 (read per call): the plane-by-plane path, the A/B partner and the pinned definition
 static bool bound_direct_env() { return env_on("EVPK_BOUND_DIRECT"); }
 
+// bound_state of the device arrays of A by the path the knob and the decomposition select (collective on x-slab ranks).  On one rank a
+// decomposition that is not the uniform tiling takes the plane-by-plane path; on several every rank must take the same path, so there
+// it is an error
+static int itd_bound(evpk_ctx *c, const ItdArgs &A, const char *who) {
+    if (!bound_direct_env()) return itd_bound_state(c, A);
+    if (!bound_direct_ok(c)) {
+        if (c->nranks > 1) FAIL(c, "%s: the blocks are not the uniform tiling of create_blocks (EVPK_BOUND_DIRECT=0 on every rank takes the plane-by-plane path)", who);
+        return itd_bound_state(c, A);
+    }
+    return c->nranks > 1 ? itd_bound_ranks(c, A) : itd_bound_direct(c, A);
+}
+
 extern "C" int evpk_bound_state(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, double *aicen, double *vicen, double *vsnon,
                                 double *trcrn) {
     if (!c) return 1;
-    if (c->nranks > 1) FAIL(c, "evpk_bound_state: nranks = %d: more than one rank is not supported yet", c->nranks);
+    RANKS_ENTRY(c, "evpk_bound_state");
     if (!aicen || !vicen || !vsnon || ntrcr < 0 || ntrcr_dim < ntrcr || (ntrcr > 0 && !trcrn)) FAIL(c, "evpk_bound_state: a required argument is missing");
     if (!c->connected) FAIL(c, "evpk_bound_state: the context is not connected yet (evpk_connect)");
     if (ncat < 1 || ncat > MAXCAT) FAIL(c, "evpk_bound_state: ncat = %d not in 1..%d", ncat, MAXCAT);
     if (ntrcr > RG_MAXT) FAIL(c, "evpk_bound_state: ntrcr = %d exceeds %d", ntrcr, RG_MAXT);
-    if (!c->nblocks) return 0;
+    if (!c->nblocks && c->nranks == 1) return 0;          // (a slab rank whose blocks are all eliminated still posts its messages)
     HIPCHK(c, hipSetDevice(c->device));
     const bool direct = bound_direct_env();
     if (direct && !bound_direct_ok(c)) FAIL(c, "evpk_bound_state: the blocks are not the uniform tiling of create_blocks (EVPK_BOUND_DIRECT=0 takes the plane-by-plane path)");
@@ -3666,7 +3790,7 @@ extern "C" int evpk_bound_state(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_
                                 {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim, &A.trcrn, true}};
     if (stage_in(c, arr)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
-    if (direct ? itd_bound_direct(c, A) : itd_bound_state(c, A)) return 1;
+    if (itd_bound(c, A, "evpk_bound_state")) return 1;
     if (stage_out(c, arr)) return 1;
     return xp_check(c);
 }
@@ -3676,7 +3800,7 @@ extern "C" int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t nca
                               double *aice, double *vice, double *vsno, double *aice0, double *trcr, double *daidtd, double *dvidtd,
                               double *dagedtd) {
     if (!c) return 1;
-    if (c->nranks > 1) FAIL(c, "evpk_aggregate: nranks = %d: more than one rank is not supported yet", c->nranks);
+    RANKS_ENTRY(c, "evpk_aggregate");
     if (!t || !aice0 || !aice || !vice || !vsno || !aicen || !vicen || !vsnon || ntrcr < 0 || ntrcr_dim < ntrcr ||
         (ntrcr > 0 && (!trcrn || !trcr_depend || !trcr)))
         FAIL(c, "evpk_aggregate: a required argument is missing");
@@ -3688,8 +3812,8 @@ extern "C" int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t nca
     if (nt_iage < 0 || nt_iage > ntrcr) FAIL(c, "evpk_aggregate: nt_iage = %d not in 0..ntrcr = %d", nt_iage, ntrcr);
     ItdArgs A{};
     if (itd_tables(c, "evpk_aggregate", A, ntrcr, trcr_depend, t)) return 1;
-    if (!c->nblocks || c->check_only) return 0;
-    Slab &s = c->s;
+    if (c->check_only || (!c->nblocks && !(bound && c->nranks > 1))) return 0;     // (bound_state is collective: a slab rank whose blocks
+    Slab &s = c->s;                                                                   // are all eliminated still posts its messages)
     HIPCHK(c, hipSetDevice(c->device));
     A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nt_iage = nt_iage;
     A.dt = dt; A.Tocnfrz = Tocnfrz; A.puny = 1.0e-11;
@@ -3702,10 +3826,11 @@ extern "C" int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t nca
         {daidtd, N, &A.daidtd, true}, {dvidtd, N, &A.dvidtd, true}, {dagedtd, N, &A.dagedtd, true}};
     if (stage_in(c, arr)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
-    if (bnd && ((bound_direct_env() && bound_direct_ok(c)) ? itd_bound_direct(c, A) : itd_bound_state(c, A))) return 1;
-    with_ncat(ncat, [&](auto NC) {
-        hipLaunchKernelGGL(k_itd_aggregate<decltype(NC)::value>, block_grid(c), dim3(64), 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
-    });
+    if (bnd && itd_bound(c, A, "evpk_aggregate")) return 1;
+    if (c->nblocks)
+        with_ncat(ncat, [&](auto NC) {
+            hipLaunchKernelGGL(k_itd_aggregate<decltype(NC)::value>, block_grid(c), dim3(64), 0, c->stream, s, (const BlockDesc *)c->d_bd, A);
+        });
     HIPCHK(c, hipGetLastError());
     if (stage_out(c, arr)) return 1;
     return xp_check(c);
@@ -3978,6 +4103,19 @@ static int dyn_stages(evpk_ctx *c, const evpk_dyn_args &x, evpk_ridge_diag *dg, 
     const evpk_itd_tracers &t = x.t;
     int32_t s4[4] = {0, 0, 0, 0};
     int rc = 0;
+    // Ranks decide alone, as the reference's l_stop is per task -- but a rank whose stage stops still posts the exchange of the call
+    // that is left, aggregate's bound_state, with whatever its arrays hold, so that its slab neighbours are not left waiting: they
+    // return normally, it returns its stage's code afterwards (include/evpk.h)
+    auto stopped = [&](int code) {
+        if (c->nranks == 1 || c->check_only || code == 1) return code;
+        const std::string keep = c->err;
+        ItdArgs A{};
+        A.ncat = x.ncat; A.ntrcr = x.ntrcr; A.ntrcr_dim = x.ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
+        A.aicen = x.aicen; A.vicen = x.vicen; A.vsnon = x.vsnon; A.trcrn = x.ntrcr ? x.trcrn : nullptr;
+        if (itd_bound(c, A, "evpk_step_dynamics") || hipStreamSynchronize(c->stream) != hipSuccess || xp_check(c)) return 1;
+        c->err = keep;
+        return code;
+    };
     if (x.advection == 1)
         rc = evpk_transport_upwind_state(c, x.dt, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, t.nt_Tsfc, t.nt_alvl, t.nt_apnd, t.nt_fbri, t.tr_pond_cesm,
                                          t.tr_pond_lvl, t.tr_pond_topo, x.k.Tocnfrz, x.aice0, x.aicen, x.vicen, x.vsnon, x.trcrn);
@@ -3986,7 +4124,7 @@ static int dyn_stages(evpk_ctx *c, const evpk_dyn_args &x, evpk_ridge_diag *dg, 
                                         x.trcrn, x.tracer_type, x.depend, x.has_dependents, x.integral_order, x.l_dp_midpt);
     if (rc) {
         if (rc == EVPK_REMAP_BAD_DEPARTURE || rc == EVPK_REMAP_NEGATIVE_MASS) stop[0] = 1;
-        return rc;
+        return stopped(rc);
     }
     if (x.ridge) {
         const evpk_ridge_tracers rt{t.nt_qsno, t.nslyr, t.nt_alvl, x.nt_vlvl, t.nt_apnd, t.nt_hpnd, t.nt_fbri, t.tr_pond_cesm, t.tr_pond_lvl, t.tr_pond_topo};
@@ -3994,14 +4132,14 @@ static int dyn_stages(evpk_ctx *c, const evpk_dyn_args &x, evpk_ridge_diag *dg, 
                             x.vicen, x.vsnon, x.trcrn, dg, s4);
         if (rc) {
             if (rc == EVPK_RIDGE_STOP) { stop[0] = 2; for (int q = 0; q < 4; q++) stop[1 + q] = s4[q]; }
-            return rc;
+            return stopped(rc);
         }
     }
     rc = evpk_cleanup_itd(c, x.dt * x.ndtd, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, &t, x.hin_max, &x.k, x.tr_aero, x.nbtrcr, x.heat_capacity,
                           x.aicen, x.vicen, x.vsnon, x.trcrn, x.aice0, x.aice, x.fpond, x.fresh, x.fsalt, x.fhocn, x.first_ice, s4);
     if (rc) {
         if (rc == EVPK_ITD_STOP) { stop[0] = 3; for (int q = 0; q < 4; q++) stop[1 + q] = s4[q]; }
-        return rc;
+        return stopped(rc);
     }
     return evpk_aggregate(c, x.dt, 1, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, &t, x.nt_iage, x.k.Tocnfrz, x.aicen, x.vicen, x.vsnon, x.trcrn,
                           x.aice, x.vice, x.vsno, x.aice0, x.trcr, x.daidtd, x.dvidtd, x.dagedtd);
@@ -4010,7 +4148,7 @@ static int dyn_stages(evpk_ctx *c, const evpk_dyn_args &x, evpk_ridge_diag *dg, 
 extern "C" int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t stop[5]) {
     if (!c) return 1;
     if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
-    if (c->nranks > 1) FAIL(c, "evpk_step_dynamics: nranks = %d: more than one rank is not supported yet", c->nranks);
+    RANKS_ENTRY(c, "evpk_step_dynamics");
     if (!a || !stop) FAIL(c, "evpk_step_dynamics: a required argument is missing");
     if (a->advection < 0 || a->advection > 2) FAIL(c, "evpk_step_dynamics: advection = %d not in 0..2", a->advection);
     if (a->ridge != 0 && a->ridge != 1) FAIL(c, "evpk_step_dynamics: ridge = %d", a->ridge);
@@ -4031,7 +4169,7 @@ extern "C" int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t s
         c->check_only = false;
         if (rc) return rc;
     }
-    if (!c->nblocks) return 0;
+    if (!c->nblocks && c->nranks == 1) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     // the union of the caller's arrays, each staged once (or used in place): the stages then see device pointers only
     evpk_dyn_args x = *a;
@@ -4120,5 +4258,6 @@ extern "C" int evpk_get_stats(evpk_ctx *c, evpk_stats *o) {
     (void)hipDeviceGetAttribute(&dev, hipDeviceAttributePciDeviceId, c->device);
     o->device_pci = (dom << 16) | (bus << 8) | dev;
     o->delivery_checked = c->dv_checked; o->delivery_bad = c->dv_bad;
+    o->bound_state_rounds = c->bs_rounds; o->bound_state_planes = c->bs_planes;
     return 0;
 }

@@ -554,4 +554,154 @@ __global__ void __launch_bounds__(BS_TX) k_bound_state(const BlockDesc *bd, cons
     for (int q = 0; q < BS_PG; q++) if (dst[q]) *dst[q] = v[q];
 }
 
+// ---- bound_state across x-slab ranks in one exchange round ----
+// The same fact carries further: the source of every ghost cell is a PHYSICAL cell of some rank, so every rank packs physical cells
+// only, the messages cross once, and every rank then fills all its ghost cells in one launch -- no N-S-then-E-W ordering.
+// A rank's message to a partner, for the `np` planes of a round (plane list of k_bound_state):
+//     [ W: np x nyg, its westmost physical column, rows 1 .. ny_global ]      if the partner is its west neighbour
+//     [ E: np x nyg, its eastmost physical column ]                            if the partner is its east neighbour
+//     [ T: np x nxl, its top physical row (ny_global) over its own columns ]   if the partner is a tripole fold partner
+// (two ranks on a cyclic ring: one message holds W and E).  A cell of an eliminated land block packs 0: the sender knows its block table,
+// the receiver does not need it.  The block table bmap covers the GLOBAL block columns; "not mine" is told from "eliminated" by the
+// rank's own column range i0 .. i1.
+constexpr int BR_MAXT = 5;          // fold partners (evpk_connect refuses more)
+struct BrArgs {
+    int i0, i1;                     // the rank's global columns
+    int p0, np;                     // the planes of this round
+    // pack: where the sections go (the neighbour's mapped slot, or a local send buffer); null: no such partner
+    double *toW, *toE;
+    double *toT[BR_MAXT];
+    int nT;
+    // fill: the west neighbour's E section, the east neighbour's W section, the fold partners' T sections with their columns
+    const double *fromW, *fromE;
+    const double *fromT[BR_MAXT];
+    int t_i0[BR_MAXT], t_w[BR_MAXT];
+    int nS;
+};
+
+// plane p of the list aicen(1:ncat), trcrn(1:ntrcr, 1:ncat), vicen, vsnon: its array and its plane inside a block of that array
+__device__ inline BsArr bs_plane(const BsArgs &A, int p, int &pp) {
+    const int c1 = A.ncat, c2 = c1 + A.ncat * A.ntrcr, c3 = c2 + A.ncat;
+    if (p < c1) { pp = p; return A.aicen; }
+    if (p < c2) { const int r = p - c1, n = r / A.ntrcr; pp = n * A.ntrcr_dim + (r - n * A.ntrcr); return A.trcrn; }
+    if (p < c3) { pp = p - c2; return A.vicen; }
+    pp = p - c3;
+    return A.vsnon;
+}
+
+// blockIdx.y: 0 the W section, 1 the E section, 2 the T sections; a thread takes one physical cell and a group of BS_PG planes, loads
+// ahead of stores (the column sections read one cell per block row; the stores of every section are consecutive along the message)
+__global__ void __launch_bounds__(BS_TX) k_bound_pack(const BlockDesc *bd, const int *bmap, BsArgs A, BrArgs R) {
+    const int t = blockIdx.x * BS_TX + threadIdx.x, sec = blockIdx.y;
+    const int nxl = R.i1 - R.i0 + 1;
+    int si, sj;
+    if (sec < 2) {
+        if ((sec == 0 ? R.toW : R.toE) == nullptr || t >= A.nyg) return;
+        si = sec == 0 ? R.i0 : R.i1; sj = t + 1;
+    } else {
+        if (R.nT == 0 || t >= nxl) return;
+        si = R.i0 + t; sj = A.nyg;
+    }
+    const int sb = bmap[((sj - 1) / A.bsy) * A.nbx + (si - 1) / A.bsx];
+    const size_t nn = (size_t)A.nyb * A.nxb;
+    size_t scell = 0;
+    if (sb >= 0) {
+        const BlockDesc e = bd[sb];
+        scell = (size_t)(e.jlo + (sj - e.jglob_lo) - 1) * A.nxb + (e.ilo + (si - e.iglob_lo) - 1);
+    }
+    const int q0 = blockIdx.z * BS_PG;
+    double v[BS_PG];
+#pragma unroll
+    for (int q = 0; q < BS_PG; q++) {
+        v[q] = 0.0;
+        if (q0 + q < R.np && sb >= 0) {
+            int pp;
+            const BsArr a = bs_plane(A, R.p0 + q0 + q, pp);
+            v[q] = a.base[(size_t)sb * a.bstride + (size_t)pp * nn + scell];
+        }
+    }
+    if (sec < 2) {
+        double *to = sec == 0 ? R.toW : R.toE;
+#pragma unroll
+        for (int q = 0; q < BS_PG; q++) if (q0 + q < R.np) to[(size_t)(q0 + q) * A.nyg + t] = v[q];
+    } else {
+        for (int k = 0; k < R.nT; k++) {
+            double *to = R.toT[k];
+#pragma unroll
+            for (int q = 0; q < BS_PG; q++) if (q0 + q < R.np) to[(size_t)(q0 + q) * nxl + t] = v[q];
+        }
+    }
+}
+
+// k_bound_state's classification per ghost cell on a slab that starts at i0 > 1: keep, fill, copy from a physical cell of the rank's own
+// blocks, or take the value a partner packed
+__global__ void __launch_bounds__(BS_TX) k_bound_fill(const BlockDesc *bd, const int *bmap, BsArgs A, BrArgs R) {
+    const int t = blockIdx.x * BS_TX + threadIdx.x, b = blockIdx.y;
+    const int nxb = A.nxb, nyb = A.nyb;
+    const BlockDesc d = bd[b];
+    int i, j;
+    if (t < 4 * nxb) {
+        const int r = t / nxb;
+        i = t - r * nxb + 1;
+        j = r == 0 ? 1 : r == 1 ? nyb : r == 2 ? d.jhi + 1 : d.jlo - 1;
+        if (r >= 2 && (j <= 1 || j >= nyb)) return;
+    } else {
+        const int u = t - 4 * nxb;
+        if (u >= 4 * nyb) return;
+        const int r = u / nyb;
+        j = u - r * nyb + 1;
+        i = r == 0 ? 1 : r == 1 ? nxb : r == 2 ? d.ihi + 1 : d.ilo - 1;
+        if (r >= 2 && (i <= 1 || i >= nxb)) return;
+        if (j == 1 || j == nyb || j == d.jhi + 1 || j == d.jlo - 1) return;
+    }
+    if (i >= d.ilo && i <= d.ihi && j >= d.jlo && j <= d.jhi) return;          // physical cells are never written
+    const bool edge = (i == 1 || i == nxb || j == 1 || j == nyb);
+    const bool padding = (i > d.ihi + 1 || j > d.jhi + 1);
+    const int gi = d.iglob_lo + (i - d.ilo), gj = d.jglob_lo + (j - d.jlo);
+    const bool has_src = !padding && ((gi >= 1 && gi <= A.nxg) || A.cyclic) && ((gj >= 1 && gj <= A.nyg) || (A.tripole && gj == A.nyg + 1));
+    if (!has_src && !edge) return;                                              // keeps the caller's value
+    const size_t nn = (size_t)nyb * nxb;
+    const size_t dcell = (size_t)(j - 1) * nxb + (i - 1);
+    int sb = -1;                    // own block of the source, -1: none
+    size_t scell = 0;
+    const double *msg = nullptr;    // or the source's place in a received section (plane 0 of the round), planes mstride apart
+    size_t mstride = 0;
+    if (has_src) {
+        int si = gi, sj = gj;
+        if (si < 1) si += A.nxg;
+        if (si > A.nxg) si -= A.nxg;
+        const bool folded = sj == A.nyg + 1;
+        if (folded) { si = A.nxg - si + 1; sj = A.nyg; }                        // centre fold: ghost(g, ny + 1) = top(nx - g + 1, ny)
+        if (folded ? (si >= R.i0 && si <= R.i1) : (gi >= R.i0 && gi <= R.i1)) {
+            sb = bmap[((sj - 1) / A.bsy) * A.nbx + (si - 1) / A.bsx];
+            if (sb >= 0) {
+                const BlockDesc e = bd[sb];
+                scell = (size_t)(e.jlo + (sj - e.jglob_lo) - 1) * nxb + (e.ilo + (si - e.iglob_lo) - 1);
+            }
+        } else if (!folded) {
+            const double *from = gi < R.i0 ? R.fromW : R.fromE;
+            if (from) { msg = from + (sj - 1); mstride = (size_t)A.nyg; }
+        } else {
+            for (int k = 0; k < R.nS; k++)
+                if (si >= R.t_i0[k] && si < R.t_i0[k] + R.t_w[k]) { msg = R.fromT[k] + (si - R.t_i0[k]); mstride = (size_t)R.t_w[k]; }
+        }
+    }
+    const int q0 = blockIdx.z * BS_PG;
+    double v[BS_PG];
+    double *dst[BS_PG];
+#pragma unroll
+    for (int q = 0; q < BS_PG; q++) {
+        v[q] = 0.0; dst[q] = nullptr;
+        if (q0 + q < R.np) {
+            int pp;
+            const BsArr a = bs_plane(A, R.p0 + q0 + q, pp);
+            dst[q] = a.base + (size_t)b * a.bstride + (size_t)pp * nn + dcell;
+            if (sb >= 0) v[q] = a.base[(size_t)sb * a.bstride + (size_t)pp * nn + scell];
+            else if (msg) v[q] = msg[(size_t)(q0 + q) * mstride];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < BS_PG; q++) if (dst[q]) *dst[q] = v[q];
+}
+
 }  // namespace evpk

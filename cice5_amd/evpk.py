@@ -84,7 +84,8 @@ class Stats(ct.Structure):
                 ("kernel3_ms", ct.c_float), ("kernel3_launches", ct.c_int32), ("kernel3_timed", ct.c_int32),
                 ("strip_rows3", ct.c_int32), ("nstrips3", ct.c_int32),
                 ("rccl_ranks", ct.c_int32), ("device", ct.c_int32), ("device_pci", ct.c_int32),
-                ("delivery_checked", ct.c_int64), ("delivery_bad", ct.c_int64)]
+                ("delivery_checked", ct.c_int64), ("delivery_bad", ct.c_int64),
+                ("bound_state_rounds", ct.c_int32), ("bound_state_planes", ct.c_int32)]
 
 XP_NAMES = {0: "none", 1: "rccl", 2: "shm relay", 3: "ipc peer-mapped", 4: "self (forced exchange)"}
 
@@ -572,7 +573,9 @@ class Context:
 
     def bound_state(self, aicen, vicen, vsnon, trcrn, ntrcr: int):
         """evpk_bound_state (bound_state, ice_state.F90:173-238): the ghost cells of aicen / vicen / vsnon (nb, ncat, ny, nx) and of tracers
-        1 .. ntrcr of trcrn (nb, ncat, ntrcr_dim, ny, nx; None when ntrcr == 0) in place, one launch"""
+        1 .. ntrcr of trcrn (nb, ncat, ntrcr_dim, ny, nx; None when ntrcr == 0) in place, one launch.  On x-slab ranks the call is
+        collective: one packed message per partner rank, then one launch (stats().bound_state_rounds / bound_state_planes); so are
+        aggregate(bound=True) and step_dynamics"""
         ntrcr_dim = int(trcrn.shape[2]) if trcrn is not None else 0
         self._chk(self._L.evpk_bound_state(self._ctx, int(aicen.shape[1]), int(ntrcr), ntrcr_dim, _p64(aicen), _p64(vicen), _p64(vsnon),
                                            _p64(trcrn)), "evpk_bound_state")

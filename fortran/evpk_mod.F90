@@ -87,6 +87,7 @@
          integer (c_int32_t) :: kernel3_launches, kernel3_timed, strip_rows3, nstrips3
          integer (c_int32_t) :: rccl_ranks, device, device_pci
          integer (c_int64_t) :: delivery_checked, delivery_bad
+         integer (c_int32_t) :: bound_state_rounds, bound_state_planes
       end type evpk_stats
 
       ! evpk_eap_state (include/evpk.h): the structure tensor at the four corners, its cell means, the EAP history fields

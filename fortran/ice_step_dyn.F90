@@ -13,6 +13,11 @@
 ! ice_transport_driver keeps tracer_type, depend and has_dependents private, so they are rebuilt here from trcr_depend by the
 ! rule of init_transport (ice_transport_driver.F90:90-118).  integral_order and l_dp_midpt are private there too: optional
 ! arguments with the reference's values (3, .true.).
+!
+! More than one task (x-slabs, one GPU each): every task makes this call -- evpk_step_dynamics is collective, bound_state
+! exchanges between the slab neighbours and the tripole fold partners; a task without a block column returns at once.  Stops are
+! per task, as the reference's l_stop: any non-zero return goes to abort_ice below, which ends the run on every task; the task that
+! stopped has still posted its exchanges, so no other task waits for it.  The block number in the message is the task's local one.
 !=======================================================================
 
       module ice_step_dyn

@@ -174,6 +174,10 @@ typedef struct {
     int64_t delivery_checked;          /* EVPK_VERIFY_DELIVERY: values written in place into page-locked caller arrays that were delivered a second
                                           time through the staged path and compared (since evpk_create) ... */
     int64_t delivery_bad;              /* ... and how many of them differed (mode 1: the first one fails the download; mode 2: repaired) */
+    int32_t bound_state_rounds;        /* exchange rounds of the last bound_state (evpk_bound_state, evpk_aggregate(bound = 1), evpk_step_dynamics):
+                                          0 on one rank; on x-slab ranks 1 while the planes fit one message per partner, one per 14 planes on the
+                                          plane-by-plane path */
+    int32_t bound_state_planes;        /* planes that bound_state moved: ncat * (3 + ntrcr) */
 } evpk_stats;
 
 enum { EVPK_XP_NONE = 0, EVPK_XP_RCCL = 1, EVPK_XP_SHM_RELAY = 2, EVPK_XP_IPC = 3, EVPK_XP_SELF = 4 };
@@ -327,7 +331,9 @@ int evpk_transport_remap_state(evpk_ctx *c, double dt, int32_t ncat, int32_t ntr
  * that comes first in (block, j, i) order at the earliest iteration; the state arrays are then undefined (the reference aborts); or 1
  * with evpk_last_error: krdg_redist == 0 (ridge_shift reads hrmax with the index of the compressed list of ridging cells, :1724-1725,
  * :1860-1866, so the reference's result depends on which other cells of the block ridge), aerosol tracers (none can be passed),
- * nranks > 1 (follow-up), ntrcr > 32, ncat > 16. */
+ * ntrcr > 32, ncat > 16; nranks > 1 on a context that is not connected yet.
+ * x-slab ranks (nranks > 1): ridging never looks beyond a block, so every rank ridges its own blocks and the call is NOT collective; a
+ * rank without a block column returns 0 at once; stop[1] is the rank's local block number. */
 typedef struct {            /* 1-based tracer indices of ice_state, 0 = not in use */
     int32_t nt_qsno, nslyr, nt_alvl, nt_vlvl, nt_apnd, nt_hpnd, nt_fbri;
     int32_t tr_pond_cesm, tr_pond_lvl, tr_pond_topo;
@@ -375,14 +381,18 @@ int evpk_ridge_ice(evpk_ctx *c, double dt, int32_t ndtd, int32_t ncat, int32_t n
  * 5 dvice > vicen (:1112); 6 zap: aicen < -puny (:1881); 7 zap: excess area (:2025).  Inputs can reach 1, 3 (a negative vicen under
  * aicen > puny, a donor on the downward pass) and 6.  2, 4, 5 cannot be reached from rebin: it sets daice = aicen > puny and
  * dvice = vicen of the donor, which pass those checks identically; 7 cannot, because aice is checked at :1650 and not recomputed.
- * Or 1 with evpk_last_error: aerosol tracers, nbtrcr > 0, heat_capacity = .false., nranks > 1 (follow-ups), ntrcr > 32, ncat > 16.
+ * Or 1 with evpk_last_error: aerosol tracers, nbtrcr > 0, heat_capacity = .false., ntrcr > 32, ncat > 16; nranks > 1 on a context that is
+ * not connected yet.  x-slab ranks: as evpk_ridge_ice -- not collective, the rank's own blocks, stop[1] the local block number.
  *
  * evpk_aggregate: the second half of step_dynamics.  bound = 1: bound_state (ice_state.F90:173-238) first -- ice_HaloUpdate, centre
  * scalar, of aicen, trcrn(1:ntrcr), vicen, vsnon (their ghost cells are then in / out; fill 0 next to an eliminated land block) -- then
  * aggregate (ice_itd.F90:246-458) on every cell of every block, ghost cells included: aice, vice, vsno, aice0 (nx_block, ny_block, nblocks)
  * and trcr (nx_block, ny_block, ntrcr_dim, nblocks) are written on every cell, tracers 1 .. ntrcr; the category sums run n outer, the products
  * as written at :356-431.  Then, on physical cells, the tendencies (ice_step_mod.F90:1183-1189): daidtd, dvidtd are in / out -- on entry they
- * hold the pre-dynamics aice, vice -- and so is dagedtd, computed when nt_iage > 0; each may be NULL. */
+ * hold the pre-dynamics aice, vice -- and so is dagedtd, computed when nt_iage > 0; each may be NULL.
+ * x-slab ranks: bound = 1 is COLLECTIVE over the ranks that own block columns (bound_state exchanges, see evpk_bound_state); bound = 0 is
+ * not.  A rank without a block column returns 0 at once and joins no exchange.  Refused with 1 and evpk_last_error like the others:
+ * nranks > 1 on a context that is not connected yet. */
 #define EVPK_HAS_CLEANUP_ITD 1
 typedef struct {            /* 1-based tracer indices of ice_state, 0 = not in use; nilyr / nslyr layers from nt_qice / nt_qsno */
     int32_t nt_Tsfc, nt_qice, nilyr, nt_qsno, nslyr, nt_alvl, nt_apnd, nt_hpnd, nt_fbri;
@@ -409,7 +419,15 @@ int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t 
  * eliminated land block), a cell without one takes 0 on the outermost row / column of the array and keeps the caller's value elsewhere;
  * physical cells and the tracer slots ntrcr + 1 .. ntrcr_dim are never written.  Arrays as for evpk_aggregate; trcrn may be NULL when
  * ntrcr == 0.  evpk_aggregate(bound = 1) takes the same path.  EVPK_BOUND_DIRECT=0 (read per call) keeps the plane-by-plane path through
- * the slab, which defines the result.  Returns 1 with evpk_last_error: nranks > 1, ncat > 16, ntrcr > 32.
+ * the slab, which defines the result.  Returns 1 with evpk_last_error: ncat > 16, ntrcr > 32; nranks > 1 on a context that is not
+ * connected yet.
+ * x-slab ranks (nranks > 1): COLLECTIVE over the ranks that own block columns; a rank without one returns 0 at once and joins no
+ * exchange.  Every rank packs physical cells only -- its westmost and eastmost column for the ring neighbours, on a tripole grid its top
+ * row for its fold partners -- into one message per partner; the messages cross once over the context's transport and one launch then
+ * fills every ghost cell (k_bound_pack / k_bound_fill).  Planes that do not fit the buffers sized at evpk_connect take further rounds
+ * (evpk_stats.bound_state_rounds).  EVPK_BOUND_DIRECT must be the same on every rank: the two paths post different exchanges.  Of the
+ * entry points of this section only evpk_bound_state, evpk_aggregate(bound = 1) and evpk_step_dynamics are collective; every collective
+ * call ends by checking the transport (a partner that never arrived is an error after 20 s, not a hang).
  *
  * evpk_step_dynamics: [evpk_transport_upwind_state | evpk_transport_remap_state](dt), [evpk_ridge_ice(dt, ndtd)],
  * evpk_cleanup_itd(dt * ndtd), evpk_aggregate(bound = 1, dt), bit for bit, with every caller array the device cannot see copied up at
@@ -424,9 +442,17 @@ int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t 
  *   diag                             may be NULL; its fpond / fresh / fhocn members are ignored in favour of the ones above
  * A stop of a stage returns that stage's code (EVPK_REMAP_BAD_DEPARTURE, EVPK_REMAP_NEGATIVE_MASS, EVPK_RIDGE_STOP, EVPK_ITD_STOP) with
  * stop[0] = the stage (1 transport, 2 ridge, 3 cleanup) and stop[1..4] that stage's four numbers (0 for transport); later stages do not
- * run and the arrays are undefined.  A refused call (return 1 with evpk_last_error: nranks > 1, advection / ridge out of range, a
- * missing pointer, anything one of the stages refuses) is refused before the first copy and touches nothing. */
+ * run and the arrays are undefined.  A refused call (return 1 with evpk_last_error: nranks > 1 on a context that is not connected
+ * yet, advection / ridge out of range, a missing pointer, anything one of the stages refuses) is refused before the first copy and
+ * touches nothing.
+ * x-slab ranks: COLLECTIVE -- every rank that owns block columns calls it with the same advection / ridge / ncat / ntrcr; a rank without
+ * a block column returns 0 at once.  Stops are per rank, as the reference's l_stop is per task: a rank whose transport, ridging or
+ * cleanup stage stops skips the computation that is left but still posts every remaining exchange of the call (aggregate's
+ * bound_state) with whatever its arrays hold, then returns its stage's code and stop[] (stop[2] its local block number).  The other
+ * ranks return 0; their ghost cells next to the stopped rank are undefined.  The host aborts the run on any non-zero return, as the
+ * reference does (abort_ice). */
 #define EVPK_HAS_STEP_DYNAMICS 1
+#define EVPK_HAS_STEP_DYNAMICS_RANKS 1
 int evpk_bound_state(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim,
                      double *aicen, double *vicen, double *vsnon, double *trcrn);
 typedef struct {
