@@ -3609,6 +3609,65 @@ extern "C" int evpk_cleanup_itd(evpk_ctx *c, double dt, int32_t ncat, int32_t nt
     return EVPK_ITD_STOP;
 }
 
+// ---- linear_itd as step_therm2 calls it (ice_step_mod.F90:821-871, ice_therm_itd.F90:69-859) on the caller's state arrays ----
+extern "C" int evpk_linear_itd(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend, const evpk_itd_tracers *t,
+                               const double *hin_max, double hi_min, const evpk_itd_constants *k, const double *aicen_init,
+                               const double *vicen_init, double *aicen, double *vicen, double *vsnon, double *trcrn, double *aice, double *aice0,
+                               double *fpond, int32_t stop[4]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = 0;
+    RANKS_ENTRY(c, "evpk_linear_itd");
+    if (!t || !hin_max || !k || !aicen_init || !vicen_init || !aice0 || !aice || !aicen || !vicen || !vsnon || !stop || ntrcr < 0 ||
+        ntrcr_dim < ntrcr || (ntrcr > 0 && (!trcrn || !trcr_depend)))
+        FAIL(c, "evpk_linear_itd: a required argument is missing");
+    if (!c->connected) FAIL(c, "evpk_linear_itd: the context is not connected yet (evpk_connect)");
+    if (!c->have_params) FAIL(c, "evpk_linear_itd: evpk_set_params has not been called (rhos)");
+    if (ncat < 1 || ncat > MAXCAT) FAIL(c, "evpk_linear_itd: ncat = %d not in 1..%d", ncat, MAXCAT);
+    if (ntrcr > RG_MAXT) FAIL(c, "evpk_linear_itd: ntrcr = %d exceeds %d", ntrcr, RG_MAXT);
+    if (k->puny != 1.0e-11) FAIL(c, "evpk_linear_itd: puny = %g: compute_tracers on the device is built with 1e-11", k->puny);
+    if (c->nblocks >= 65536) FAIL(c, "evpk_linear_itd: %d blocks exceed the stop key", c->nblocks);
+    ItdArgs A{};
+    if (itd_tables(c, "evpk_linear_itd", A, ntrcr, trcr_depend, t)) return 1;
+    if (ntrcr > 0 && t->nt_Tsfc < 1) FAIL(c, "evpk_linear_itd: nt_Tsfc is required (compute_tracers resets it to Tocnfrz)");
+    if (t->tr_pond_topo && !fpond) FAIL(c, "evpk_linear_itd: tr_pond_topo needs fpond");
+    if (!c->nblocks || c->check_only) return 0;
+    Slab &s = c->s;
+    HIPCHK(c, hipSetDevice(c->device));
+    A.ncat = ncat; A.ntrcr = ntrcr; A.ntrcr_dim = ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
+    A.Tocnfrz = k->Tocnfrz; A.Lfresh = k->Lfresh; A.puny = k->puny; A.rhos = c->p.rhos;
+    for (int n = 0; n < ncat; n++) A.hin_max[n] = hin_max[n];
+    A.hin_max[ncat] = 999.9;                              // ice_therm_itd.F90:208 (the caller's array is not written)
+    LitdArgs L{};
+    L.hi_min = hi_min;
+    const size_t nb = (size_t)c->nblocks, N = nb * c->nyb * c->nxb;
+    std::vector<HostArr> arr = {
+        {aicen_init, N * ncat, &L.aicen_init, false}, {vicen_init, N * ncat, &L.vicen_init, false},
+        {aicen, N * ncat, &A.aicen, true}, {vicen, N * ncat, &A.vicen, true}, {vsnon, N * ncat, &A.vsnon, true},
+        {ntrcr ? trcrn : nullptr, N * ncat * ntrcr_dim, &A.trcrn, true}, {aice, N, &A.aice, true}, {aice0, N, &A.aice0, true},
+        {t->tr_pond_topo ? fpond : nullptr, N, &A.fpond, true}};
+    if (stage_in(c, arr)) return 1;
+    HIPCHK(c, grow(c, c->itd_bmask, c->itd_bmask_n, nb));
+    if (!c->itd_key) HIPCHK(c, hipMalloc(&c->itd_key, sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->itd_bmask, 0, sizeof(unsigned) * nb, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->itd_key, 0xff, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    const dim3 b(64), g = block_grid(c);
+    with_ncat(ncat, [&](auto NC) {
+        constexpr int nc = decltype(NC)::value;
+        hipLaunchKernelGGL(k_litd_scan<nc>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, c->itd_bmask);
+        hipLaunchKernelGGL(k_litd_remap<nc>, g, b, 0, c->stream, s, (const BlockDesc *)c->d_bd, A, L, (const unsigned *)c->itd_bmask, c->itd_key);
+    });
+    HIPCHK(c, hipGetLastError());
+    unsigned long long key = ~0ull;
+    HIPCHK(c, hipMemcpyAsync(&key, c->itd_key, sizeof(key), hipMemcpyDeviceToHost, c->stream));
+    if (stage_out(c, arr)) return 1;
+    if (key == ~0ull) return 0;
+    const size_t o = (size_t)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+    stop[0] = ITD_STOP_NEG_DAICE + (int)((key >> 32) & 0xff);
+    stop[1] = (int32_t)(key >> 48) + 1; stop[2] = (int32_t)(o % c->nxb) + 1; stop[3] = (int32_t)(o / c->nxb) + 1;
+    return EVPK_LITD_STOP;
+}
+
 // bound_state (ice_state.F90:173-238): ice_HaloUpdate, centre scalar, of aicen, trcrn(1:ntrcr), vicen, vsnon on the device -- the planes go
 // through the scratch state planes and the general update, as evpk_halo_update's do (fill 0 next to an eliminated land block)
 static int itd_bound_state(evpk_ctx *c, const ItdArgs &A) {

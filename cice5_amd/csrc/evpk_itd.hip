@@ -1,7 +1,7 @@
 // evpk_itd.hip -- cleanup_itd (source/ice_itd.F90:1514-1769: aggregate_area, the area check, rebin with shift_ice and compute_tracers,
 // zap_small_areas I / II with zap_snow, zap_snow_temperature, the flux increments) and aggregate (:246-458) with the tendency lines of
-// step_dynamics (ice_step_mod.F90:1183-1189) on the device, on the caller's block arrays as they are.  Included by evpk_api.hip (one
-// translation unit).
+// step_dynamics (ice_step_mod.F90:1183-1189) on the device, on the caller's block arrays as they are; at the end of the file linear_itd
+// (source/ice_therm_itd.F90:69-958), which ends in the same shift_ice / compute_tracers.  Included by evpk_api.hip (one translation unit).
 //
 // One thread per cell of the block arrays.  rebin's shiftflag is one flag per BLOCK and per category boundary -- 2 (ncat - 1) boundaries,
 // first upward, then downward: when any listed cell of a block (physical, aice > puny) shifts at a boundary, shift_ice runs for every
@@ -703,5 +703,266 @@ __global__ void __launch_bounds__(BS_TX) k_bound_fill(const BlockDesc *bd, const
 #pragma unroll
     for (int q = 0; q < BS_PG; q++) if (dst[q]) *dst[q] = v[q];
 }
+
+// ---- linear_itd (source/ice_therm_itd.F90:69-859 with fit_line :871-958) as step_therm2 calls it (ice_step_mod.F90:821-871) ----
+// Two launches, no host synchronisation between them:
+//   k_litd_scan   every cell: aggregate_area (aice, aice0); a physical ocean cell with aice > puny is listed and sets its block's flag
+//   k_litd_remap  physical ocean cells of the flagged blocks: an unlisted cell zeroes its tracers (compute_tracers, ice_itd.F90:1401); a
+//                 listed cell computes hbnew, remap_flag, fit_line, the category-1 melt, donor / daice / dvice of every boundary, then
+//                 shift_ice with all ncat - 1 boundaries at once and compute_tracers, the hi_min clamp and aggregate_area
+// A boundary's donor is the category below or above it, known at run time only: it is kept as a direction (LITD_UP / LITD_DOWN) and every
+// access is a select between the two neighbours of an unrolled loop, never an index into a per-thread array.
+// The stop key is cleanup_itd's: block | boundary n | shift_ice's check 0 .. 3 | cell counting down (the error loops do not exit).
+struct LitdArgs {
+    const double *aicen_init, *vicen_init;                      // (nb, ncat, ny, nx)
+    double hi_min;
+};
+enum { LITD_NONE = 0, LITD_UP = 1, LITD_DOWN = 2 };             // donor(n) = 0, n, n + 1
+
+template <int NC>
+__global__ void __launch_bounds__(64) k_litd_scan(Slab s, const BlockDesc *bd, ItdArgs A, unsigned *bflag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    const int j = blockIdx.y + 1;
+    const int b = blockIdx.z;
+    if (i > A.nxb) return;
+    const double c0 = 0.0, c1 = 1.0;
+    const int ncat = NC ? NC : A.ncat;
+    const size_t nn = (size_t)A.nyb * A.nxb, o = (size_t)(j - 1) * A.nxb + (i - 1), ci = (size_t)b * nn + o;
+    double aice = c0;                                                                                       // aggregate_area (ice_itd.F90:489-506)
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) aice = aice + A.aicen[((size_t)b * ncat + (n - 1)) * nn + o];
+    A.aice[ci] = aice;
+    A.aice0[ci] = fmax(c1 - aice, c0);
+    // ice_step_mod.F90:830-839; the flag only ever goes from 0 to 1, so a cell that sees it set has nothing to add
+    if (itd_ocean(s, bd[b], i, j) && aice > A.puny && __atomic_load_n(&bflag[b], __ATOMIC_RELAXED) == 0u) atomicOr(&bflag[b], 1u);
+}
+template __global__ void __launch_bounds__(64) k_litd_scan<0>(Slab, const BlockDesc *, ItdArgs, unsigned *);
+template __global__ void __launch_bounds__(64) k_litd_scan<5>(Slab, const BlockDesc *, ItdArgs, unsigned *);
+
+// (min / max as a comparison and a select: no NaN rule to differ on)
+__device__ __forceinline__ double litd_min(double x, double y) { return y < x ? y : x; }
+__device__ __forceinline__ double litd_max(double x, double y) { return y > x ? y : x; }
+
+// fit_line (:917-956) of one cell and category
+__device__ __forceinline__ void litd_fit_line(double a, double hice, double hbL, double hbR, double puny, double &g0, double &g1, double &hL, double &hR) {
+    const double c0 = 0.0, c1 = 1.0, c2 = 2.0, c3 = 3.0, c6 = 6.0, p5 = 0.5, p333 = c1 / c3, p666 = c2 / c3;
+    if (a > puny && hbR - hbL > puny) {
+        hL = hbL; hR = hbR;
+        const double h13 = p333 * (c2 * hL + hR), h23 = p333 * (hL + c2 * hR);
+        if (hice < h13) hR = c3 * hice - c2 * hL;
+        else if (hice > h23) hL = c3 * hice - c2 * hR;
+        const double dhr = c1 / (hR - hL), wk1 = c6 * a * dhr, wk2 = (hice - hL) * dhr;
+        g0 = wk1 * (p666 - wk2);
+        g1 = c2 * dhr * wk1 * (wk2 - p5);
+    } else {
+        g0 = c0; g1 = c0; hL = c0; hR = c0;
+    }
+}
+
+// shift_ice's tracer part for all boundaries of one call (ice_itd.F90:919-975, :1175-1214, :1234-1239), the extension of
+// itd_shift_tracers: atrcrn once from the old state, the transfers of boundaries 1 .. ncat - 1 in order, each with the donor's untouched
+// trcrn, compute_tracers once.  qoff != 0: the snow enthalpies carry + rhos * Lfresh through the call (ice_therm_itd.F90:659-690).
+// apnd1 / hpnd1: the new pond tracers of category 1, for the hi_min clamp.
+template <int NC>
+__device__ __forceinline__ void litd_shift_tracers(const ItdArgs &A, int ncat, double *t0, size_t nn, const double *ao, const double *vo,
+                                                   const double *so, const double *an, const double *vn, const double *sn, const int *dn,
+                                                   const double *dA, const double *dV, const double *dS, double qoff, double &apnd1,
+                                                   double &hpnd1) {
+    constexpr int NA = NC ? NC : MAXCAT;
+    double oldP[3][NA + 2], newP[3][NA + 2];
+    const size_t cs = (size_t)A.ntrcr_dim * nn;                 // category stride
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        const double *t = t0 + (size_t)(n - 1) * cs;
+        oldP[0][n] = A.nt_alvl ? t[(size_t)(A.nt_alvl - 1) * nn] : 0.0;
+        oldP[1][n] = A.nt_apnd ? t[(size_t)(A.nt_apnd - 1) * nn] : 0.0;
+        oldP[2][n] = A.nt_fbri ? t[(size_t)(A.nt_fbri - 1) * nn] : 0.0;
+        newP[0][n] = 0.0; newP[1][n] = 0.0; newP[2][n] = 0.0;
+    }
+    for (int it = 0; it < A.ntrcr; it++) {
+        const int acc = A.acc[it], rule = A.rule[it], d1 = A.d1[it], d2 = A.d2[it], sl = A.slot[it];
+        const bool qs = qoff != 0.0 && A.nslyr > 0 && it + 1 >= A.nt_qsno && it + 1 < A.nt_qsno + A.nslyr;
+        double told[NA + 2], atr[NA + 2];
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) {
+            told[n] = t0[(size_t)(n - 1) * cs + (size_t)it * nn];
+            if (qs) told[n] = told[n] + qoff;
+            atr[n] = itd_product(acc, ao[n], vo[n], so[n], oldP[0][n], oldP[1][n], oldP[2][n], told[n]);
+        }
+        if (acc >= 0) {
+            _Pragma("unroll")
+            for (int n = 1; n < ncat; n++) {
+                if (dn[n] == LITD_NONE) continue;
+                const bool up = dn[n] == LITD_UP;
+                const double dat = itd_product(acc, dA[n], dV[n], dS[n], up ? oldP[0][n] : oldP[0][n + 1], up ? oldP[1][n] : oldP[1][n + 1],
+                                               up ? oldP[2][n] : oldP[2][n + 1], up ? told[n] : told[n + 1]);
+                const double lo = up ? atr[n] - dat : atr[n] + dat, hi = up ? atr[n + 1] + dat : atr[n + 1] - dat;
+                atr[n] = lo; atr[n + 1] = hi;
+            }
+        }
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) {
+            const double p1 = d1 == 1 ? newP[0][n] : d1 == 2 ? newP[1][n] : d1 == 3 ? newP[2][n] : 0.0;
+            const double p2 = d2 == 1 ? newP[0][n] : d2 == 2 ? newP[1][n] : d2 == 3 ? newP[2][n] : 0.0;
+            const double r = compute_tracer(rule, atr[n], an[n], vn[n], sn[n], p1, p2, it + 1 == A.nt_fbri, A.Tocnfrz);
+            if (sl == 1) newP[0][n] = r;
+            else if (sl == 2) newP[1][n] = r;
+            else if (sl == 3) newP[2][n] = r;
+            if (n == 1 && it + 1 == A.nt_apnd) apnd1 = r;
+            if (n == 1 && it + 1 == A.nt_hpnd) hpnd1 = r;
+            t0[(size_t)(n - 1) * cs + (size_t)it * nn] = qs ? r - qoff : r;
+        }
+    }
+}
+
+template <int NC>
+__global__ void __launch_bounds__(64) k_litd_remap(Slab s, const BlockDesc *bd, ItdArgs A, LitdArgs L, const unsigned *bflag, unsigned long long *key) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    const int j = blockIdx.y + 1;
+    const int b = blockIdx.z;
+    if (i > A.nxb) return;
+    if (!bflag[b]) return;                                // icells = 0: linear_itd is not called for this block
+    if (!itd_ocean(s, bd[b], i, j)) return;
+    const double puny = A.puny, c0 = 0.0, c1 = 1.0, c2 = 2.0, c3 = 3.0, p5 = 0.5, p333 = c1 / c3;
+    const int ncat = NC ? NC : A.ncat;
+    constexpr int NA = NC ? NC : MAXCAT;
+    const size_t nn = (size_t)A.nyb * A.nxb, o = (size_t)(j - 1) * A.nxb + (i - 1), ci = (size_t)b * nn + o;
+    const size_t cs = (size_t)A.ntrcr_dim * nn;
+    double *t0 = A.trcrn + (size_t)b * ncat * cs + o;
+    if (!(A.aice[ci] > puny)) {                           // an unlisted cell of a block that calls shift_ice: trcrn(:,:,:) = c0 (ice_itd.F90:1401)
+        for (int n = 0; n < ncat; n++)
+            for (int it = 0; it < A.ntrcr; it++) t0[(size_t)n * cs + (size_t)it * nn] = c0;
+        return;
+    }
+    double a[NA + 2], v[NA + 2], sn[NA + 2], h[NA + 2], hi0[NA + 2], dh[NA + 2], hb[NA + 2];
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {                                                                       // :308-328
+        const size_t bc = ((size_t)b * ncat + (n - 1)) * nn + o;
+        a[n] = A.aicen[bc]; v[n] = A.vicen[bc]; sn[n] = A.vsnon[bc];
+        const double ai = L.aicen_init[bc], vi = L.vicen_init[bc];
+        hi0[n] = ai > puny ? vi / ai : c0;
+        if (a[n] > puny) { h[n] = v[n] / a[n]; dh[n] = h[n] - hi0[n]; }
+        else { h[n] = c0; dh[n] = c0; }
+    }
+    bool remap = true;
+    hb[0] = A.hin_max[0];
+    _Pragma("unroll")
+    for (int n = 1; n < ncat; n++) {                                                                        // :339-436
+        const double hn = A.hin_max[n];
+        if (hi0[n] > puny && hi0[n + 1] > puny) {
+            const double slope = (dh[n + 1] - dh[n]) / (hi0[n + 1] - hi0[n]);
+            hb[n] = hn + dh[n] + slope * (hn - hi0[n]);
+        } else if (hi0[n] > puny) hb[n] = hn + dh[n];
+        else if (hi0[n + 1] > puny) hb[n] = hn + dh[n + 1];
+        else hb[n] = hn;
+        if (a[n] > puny && h[n] >= hb[n]) remap = false;
+        else if (a[n + 1] > puny && h[n + 1] <= hb[n]) remap = false;
+        if (hb[n] > A.hin_max[n + 1]) remap = false;
+        if (hb[n] < A.hin_max[n - 1]) remap = false;
+    }
+    hb[ncat] = a[ncat] > puny ? c3 * h[ncat] - c2 * hb[ncat - 1] : A.hin_max[ncat];                         // :445-454
+    hb[ncat] = litd_max(hb[ncat], A.hin_max[ncat - 1]);
+
+    int dn[NA + 2];
+    double dA[NA + 2], dV[NA + 2], dS[NA + 2];
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) { dn[n] = LITD_NONE; dA[n] = c0; dV[n] = c0; dS[n] = c0; }
+    const bool topo = A.tr_pond_topo != 0;
+    double fp = topo ? A.fpond[ci] : c0;
+    if (remap) {
+        double g0[NA + 2], g1[NA + 2], hL[NA + 2], hR[NA + 2];
+        litd_fit_line(a[1], hi0[1], hb[0], A.hin_max[1], puny, g0[1], g1[1], hL[1], hR[1]);                 // :482-492
+        if (a[1] > puny) {                                                                                  // :501-548
+            double dh0 = dh[1];
+            if (dh0 < c0) {
+                dh0 = litd_min(-dh0, A.hin_max[1]);
+                const double etamax = litd_min(dh0, hR[1]) - hL[1];
+                if (etamax > c0) {
+                    const double x1 = etamax, x2 = p5 * etamax * etamax;
+                    double da0 = g1[1] * x2 + g0[1] * x1;
+                    const double damax = a[1] * (c1 - h[1] / hi0[1]);
+                    da0 = litd_min(da0, damax);
+                    h[1] = h[1] * a[1] / (a[1] - da0);
+                    a[1] = a[1] - da0;
+                    if (topo) fp = fp - (da0 * t0[(size_t)(A.nt_apnd - 1) * nn] * t0[(size_t)(A.nt_hpnd - 1) * nn]);
+                }
+            } else {
+                hb[0] = litd_min(dh0, A.hin_max[1]);
+            }
+        }
+        _Pragma("unroll")
+        for (int n = 1; n <= ncat; n++) litd_fit_line(a[n], h[n], hb[n - 1], hb[n], puny, g0[n], g1[n], hL[n], hR[n]);      // :554-563
+        _Pragma("unroll")
+        for (int n = 1; n < ncat; n++) {                                                                    // :577-647
+            const double hn = A.hin_max[n];
+            const bool up = hb[n] > hn;
+            const double G0 = up ? g0[n] : g0[n + 1], G1 = up ? g1[n] : g1[n + 1], HL = up ? hL[n] : hL[n + 1], HR = up ? hR[n] : hR[n + 1];
+            const double and_ = up ? a[n] : a[n + 1], vnd = up ? v[n] : v[n + 1];
+            const double etamin = up ? litd_max(hn, HL) - HL : c0;
+            const double etamax = (up ? litd_min(hb[n], HR) : litd_min(hn, HR)) - HL;
+            double da = c0, dv = c0;
+            int don = up ? LITD_UP : LITD_DOWN;
+            if (etamax > etamin) {
+                const double x1 = etamax - etamin;
+                double wk1 = etamin * etamin, wk2 = etamax * etamax;
+                const double x2 = p5 * (wk2 - wk1);
+                wk1 = wk1 * etamin; wk2 = wk2 * etamax;
+                const double x3 = p333 * (wk2 - wk1);
+                da = G1 * x2 + G0 * x1;
+                dv = G1 * x3 + G0 * x2 + da * HL;
+            }
+            if (da < and_ * puny) { da = c0; dv = c0; don = LITD_NONE; }
+            if (dv < vnd * puny) { da = c0; dv = c0; don = LITD_NONE; }
+            if (da > and_ * (c1 - puny)) { da = and_; dv = vnd; }
+            if (dv > vnd * (c1 - puny)) { da = and_; dv = vnd; }
+            // (donor = 0 with daice > 0 needs a negative vicen under aicen > puny; the reference then indexes category 0: nothing moves here)
+            if (don == LITD_NONE) { da = c0; dv = c0; }
+            dn[n] = don; dA[n] = da; dV[n] = dv;
+        }
+    }
+    // shift_ice (ice_itd.F90:815-1250) with every boundary, for every listed cell
+    double ao[NA + 2], vo[NA + 2], so[NA + 2];
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) { ao[n] = a[n]; vo[n] = v[n]; so[n] = sn[n]; }
+    _Pragma("unroll")
+    for (int n = 1; n < ncat; n++) {
+        if (dn[n] == LITD_NONE) continue;
+        const bool up = dn[n] == LITD_UP;
+        const double and_ = up ? a[n] : a[n + 1], vnd = up ? v[n] : v[n + 1], snd = up ? sn[n] : sn[n + 1];
+        const int bad = itd_check(dA[n], dV[n], and_, vnd, puny);
+        if (bad >= 0) { atomicMin(key, itd_key(b, n, bad, 0xffffffffu - (unsigned)o)); return; }           // a stop: the state is undefined
+        if (!(dA[n] > c0)) { dn[n] = LITD_NONE; continue; }                                                // :1137
+        const double worka = dA[n] / and_;
+        const double dvs = snd * worka;
+        dS[n] = dvs;
+        const double alo = up ? a[n] - dA[n] : a[n] + dA[n], ahi = up ? a[n + 1] + dA[n] : a[n + 1] - dA[n];
+        const double vlo = up ? v[n] - dV[n] : v[n] + dV[n], vhi = up ? v[n + 1] + dV[n] : v[n + 1] - dV[n];
+        const double slo = up ? sn[n] - dvs : sn[n] + dvs, shi = up ? sn[n + 1] + dvs : sn[n + 1] - dvs;
+        a[n] = alo; a[n + 1] = ahi; v[n] = vlo; v[n + 1] = vhi; sn[n] = slo; sn[n + 1] = shi;
+    }
+    double apnd1 = c0, hpnd1 = c0;
+    if (A.ntrcr > 0)
+        litd_shift_tracers<NC>(A, ncat, t0, nn, ao, vo, so, a, v, sn, dn, dA, dV, dS, remap ? A.rhos * A.Lfresh : c0, apnd1, hpnd1);
+    if (remap) {                                                                                            // :701-718
+        const double h1 = a[1] > puny ? v[1] / a[1] : c0;                                                   // (shift_ice's hicen, ice_itd.F90:1227-1231)
+        if (L.hi_min > c0 && a[1] > puny && h1 < L.hi_min) {
+            const double da0 = a[1] * (c1 - h1 / L.hi_min);
+            a[1] = a[1] - da0;
+            if (topo) fp = fp - (da0 * apnd1 * hpnd1);
+        }
+    }
+    double aice = c0;                                                                                       // aggregate_area
+    _Pragma("unroll")
+    for (int n = 1; n <= ncat; n++) {
+        const size_t bc = ((size_t)b * ncat + (n - 1)) * nn + o;
+        A.aicen[bc] = a[n]; A.vicen[bc] = v[n]; A.vsnon[bc] = sn[n];
+        aice = aice + a[n];
+    }
+    A.aice[ci] = aice;
+    A.aice0[ci] = fmax(c1 - aice, c0);
+    if (topo) A.fpond[ci] = fp;
+}
+template __global__ void __launch_bounds__(64) k_litd_remap<0>(Slab, const BlockDesc *, ItdArgs, LitdArgs, const unsigned *, unsigned long long *);
+template __global__ void __launch_bounds__(64) k_litd_remap<5>(Slab, const BlockDesc *, ItdArgs, LitdArgs, const unsigned *, unsigned long long *);
 
 }  // namespace evpk

@@ -97,7 +97,7 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_transport_upwind", "evpk_remap_init", "evpk_transport_remap", "evpk_transport_remap_state",
            "evpk_eap_init", "evpk_eap_upload", "evpk_eap_download", "evpk_halo_update", "evpk_halo_update_stress",
            "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
-           "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics"]
+           "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics", "evpk_linear_itd"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -118,6 +118,7 @@ class RidgeDiag(ct.Structure):
 ITD_STOP = 14
 ITD_STOP_REASONS = {1: "aggregate ice area out of bounds", 2: "shift_ice: negative daice", 3: "shift_ice: negative dvice",
                     4: "shift_ice: daice > aicen", 5: "shift_ice: dvice > vicen", 6: "zap ice: negative ice area", 7: "zap ice: excess ice area"}
+LITD_STOP = 15                                           # reasons 2 .. 5 of ITD_STOP_REASONS
 ITD_TRACER_FIELDS = ["nt_Tsfc", "nt_qice", "nilyr", "nt_qsno", "nslyr", "nt_alvl", "nt_apnd", "nt_hpnd", "nt_fbri", "tr_pond_cesm", "tr_pond_lvl",
                      "tr_pond_topo", "tr_brine"]
 ITD_CONSTANT_FIELDS = ["Tocnfrz", "ice_ref_salinity", "hs_min", "cp_ice", "Lfresh", "Tmin", "puny"]
@@ -223,6 +224,8 @@ def lib():
                                      [ct.POINTER(RidgeDiag), c_i32p])
         L.evpk_cleanup_itd.argtypes = ([ctxp, ct.c_double] + [ct.c_int32] * 3 + [c_i32p, ct.POINTER(ItdTracers), c_f64p, ct.POINTER(ItdConstants)] +
                                        [ct.c_int32] * 3 + [c_f64p] * 10 + [c_i32p, c_i32p])
+        L.evpk_linear_itd.argtypes = ([ctxp] + [ct.c_int32] * 3 + [c_i32p, ct.POINTER(ItdTracers), c_f64p, ct.c_double, ct.POINTER(ItdConstants)] +
+                                      [c_f64p] * 9 + [c_i32p])
         L.evpk_aggregate.argtypes = ([ctxp, ct.c_double] + [ct.c_int32] * 4 + [c_i32p, ct.POINTER(ItdTracers), ct.c_int32, ct.c_double] +
                                      [c_f64p] * 12)
         L.evpk_bound_state.argtypes = [ctxp] + [ct.c_int32] * 3 + [c_f64p] * 4
@@ -551,6 +554,30 @@ class Context:
         if rc == ITD_STOP:
             return tuple(int(v) for v in stop)
         self._chk(rc, "evpk_cleanup_itd")
+        return None
+
+    def linear_itd(self, aicen_init, vicen_init, aicen, vicen, vsnon, trcrn, aice, aice0, ntrcr: int, trcr_depend, tracers, hin_max,
+                   hi_min: float, constants=None, fpond=None):
+        """evpk_linear_itd (linear_itd, ice_therm_itd.F90:69-859, as step_therm2 calls it): aicen_init / vicen_init (nb, ncat, ny, nx) in;
+        aicen / vicen / vsnon (nb, ncat, ny, nx), trcrn (nb, ncat, ntrcr_dim, ny, nx) in place on the physical ocean cells, aice / aice0
+        (nb, ny, nx) on every cell; fpond (nb, ny, nx) in / out, needed with tr_pond_topo only.  tracers, hin_max, constants as for
+        cleanup_itd; hin_max[ncat] is taken as 999.9 inside the call.
+        Returns None, or (reason, block, i, j) for shift_ice's l_stop cases (ITD_STOP_REASONS 2 .. 5); raises on a refusal."""
+        from . import constants as C
+        ncat = int(aicen.shape[1])
+        dep = np.ascontiguousarray(trcr_depend, dtype=np.int32)
+        hin = np.ascontiguousarray(hin_max, dtype=np.float64)
+        assert hin.shape == (ncat + 1,)
+        it = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        ik = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
+        stop = np.zeros(4, dtype=np.int32)
+        ntrcr_dim = int(trcrn.shape[2]) if trcrn is not None else 0
+        rc = self._L.evpk_linear_itd(self._ctx, ncat, int(ntrcr), ntrcr_dim, _p32(dep) if ntrcr else None, ct.byref(it), _p64(hin), float(hi_min),
+                                     ct.byref(ik), _p64(aicen_init), _p64(vicen_init), _p64(aicen), _p64(vicen), _p64(vsnon), _p64(trcrn),
+                                     _p64(aice), _p64(aice0), _p64(fpond), _p32(stop))
+        if rc == LITD_STOP:
+            return tuple(int(v) for v in stop)
+        self._chk(rc, "evpk_linear_itd")
         return None
 
     def aggregate(self, dt: float, aicen, vicen, vsnon, trcrn, aice, vice, vsno, aice0, trcr, ntrcr: int, trcr_depend, tracers, bound=False,

@@ -157,11 +157,12 @@
                 evpk_eap_state, evpk_eap_init, evpk_eap_upload, evpk_eap_download, &
                 evpk_ridge_tracers, evpk_ridge_diag, evpk_ridge_ice, EVPK_RIDGE_STOP, &
                 evpk_itd_tracers, evpk_itd_constants, evpk_cleanup_itd, evpk_aggregate, EVPK_ITD_STOP, &
-                evpk_dyn_args, evpk_bound_state, evpk_step_dynamics
+                evpk_dyn_args, evpk_bound_state, evpk_step_dynamics, evpk_linear_itd, EVPK_LITD_STOP
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
       integer (c_int), parameter :: EVPK_ITD_STOP = 14
+      integer (c_int), parameter :: EVPK_LITD_STOP = 15
 
       interface
          integer (c_int) function evpk_get_unique_id (id) bind(C, name='evpk_get_unique_id')
@@ -317,6 +318,19 @@
             type (c_ptr), value :: ctx, trcr_depend, hin_max, aicen, vicen, vsnon, trcrn, aice0, aice, fpond, fresh, fsalt, fhocn, first_ice
             real (c_double), value :: dt
             integer (c_int32_t), value :: ncat, ntrcr, ntrcr_dim, tr_aero, nbtrcr, heat_capacity
+            type (evpk_itd_tracers), intent(in) :: t
+            type (evpk_itd_constants), intent(in) :: k
+            integer (c_int32_t), intent(out) :: stop(4)
+         end function
+         ! linear_itd (ice_therm_itd.F90:69-859) for every block: what step_therm2 does at ice_step_mod.F90:821-871 (kitd = 1).
+         ! aicen_init, vicen_init: the state before the vertical thermodynamics; fpond may be c_null_ptr unless tr_pond_topo;
+         ! stop(4): reason (2 .. 5 of shift_ice), block, i, j
+         integer (c_int) function evpk_linear_itd (ctx, ncat, ntrcr, ntrcr_dim, trcr_depend, t, hin_max, hi_min, k, aicen_init, &
+               vicen_init, aicen, vicen, vsnon, trcrn, aice, aice0, fpond, stop) bind(C, name='evpk_linear_itd')
+            import :: c_int, c_ptr, c_double, c_int32_t, evpk_itd_tracers, evpk_itd_constants
+            type (c_ptr), value :: ctx, trcr_depend, hin_max, aicen_init, vicen_init, aicen, vicen, vsnon, trcrn, aice, aice0, fpond
+            real (c_double), value :: hi_min
+            integer (c_int32_t), value :: ncat, ntrcr, ntrcr_dim
             type (evpk_itd_tracers), intent(in) :: t
             type (evpk_itd_constants), intent(in) :: k
             integer (c_int32_t), intent(out) :: stop(4)

@@ -411,6 +411,55 @@ int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t 
                    const evpk_itd_tracers *t, int32_t nt_iage, double Tocnfrz, double *aicen, double *vicen, double *vsnon, double *trcrn,
                    double *aice, double *vice, double *vsno, double *aice0, double *trcr, double *daidtd, double *dvidtd, double *dagedtd);
 
+/* evpk_linear_itd: the thermodynamic remapping of the thickness distribution, linear_itd (source/ice_therm_itd.F90:69-859 with fit_line
+ * :871-958; kitd = 1), as step_therm2 calls it (ice_step_mod.F90:821-871), for every block of the context at once -- the reference calls
+ * it block by block and nothing in it looks beyond a block.  A host whose ITD lives on the device runs it there between its vertical
+ * thermodynamics and add_new_ice; its output is what evpk_cleanup_itd consumes.  Array conventions as evpk_cleanup_itd.
+ *   ncat, ntrcr, ntrcr_dim, trcr_depend, t     as for evpk_cleanup_itd; nt_Tsfc is required when ntrcr > 0
+ *   hin_max(0:ncat)                  the category boundaries; hin_max(ncat) is taken as 999.9 inside the call (:208), the array is not written
+ *   hi_min                           ice_itd's minimum thickness of category 1
+ *   k                                Lfresh, Tocnfrz and puny (must be 1e-11) are read; rhos comes from evpk_params
+ *   aicen_init, vicen_init           (nx_block, ny_block, ncat, nblocks), in: the state before the vertical thermodynamics
+ *   aicen, vicen, vsnon, trcrn       in / out
+ *   aice, aice0                      (nx_block, ny_block, nblocks), out on every cell
+ *   fpond                            in / out; read and written only with tr_pond_topo, else it may be NULL
+ * What it does: aggregate_area on every cell; the cell list -- physical cells with tmask and aice > puny; for a listed cell hicen_init,
+ * hicen, dhicen, the new boundaries hbnew(0:ncat) with the four tests that clear remap_flag, fit_line for category 1 on hicen_init, the
+ * category-1 melt da0 (damax clamp, fpond under topo ponds) or the shift of hbnew(0), fit_line for every category, donor / daice / dvice of
+ * every boundary with the "very small" resets and the "entire category" rules, in the reference's operation order with p333 = c1 / c3,
+ * p666 = c2 / c3; the snow enthalpies of the remap_flag cells carry + rhos * Lfresh through shift_ice; ONE shift_ice call with all
+ * ncat - 1 boundaries for every listed cell -- a listed cell whose remap_flag is false still has all its tracers rewritten as
+ * (aicen * trcrn) / aicen -- and, in a block with a listed cell, trcrn(1:ntrcr, :) = 0 on the unlisted physical ocean cells
+ * (ice_itd.F90:1401); the hi_min clamp of category 1 on remap_flag cells; aggregate_area on every cell.  A block without a listed cell is
+ * not touched beyond aice / aice0: its trcrn keeps every bit.
+ * Departures: the reference lists every physical cell with aice > puny, this call those with tmask (land carries no ice in CICE;
+ * evpk_cleanup_itd draws the same line); land and ghost cells of aicen, vicen, vsnon, trcrn keep the caller's values (the reference
+ * zeroes their tracers in a block that calls shift_ice); on a stop the arrays are undefined (the reference aborts).  A boundary that
+ * is left with donor = 0 but daice > 0 -- only a negative vicen under aicen > puny can do that, through the second "entire category"
+ * rule -- moves nothing (the reference indexes category 0 there).
+ * Parity: held bit for bit to a numpy restatement written from the Fortran (tests/nplitd.py), whose shift_ice / compute_tracers are
+ * pinned to reference-built output; fit_line and the boundary integrals are not pinned to reference-built output yet.
+ * Returns 0; EVPK_LITD_STOP with stop[] = {reason, block (local, 1-based), i, j}: reasons 2 .. 5 are EVPK_ITD_STOP's shift_ice reasons
+ * (2 negative daice, 3 negative dvice, 4 daice > aicen, 5 dvice > vicen) -- the lowest block, in it the lowest boundary, in it the first
+ * failing check, and the LAST failing listed cell in (j, i) order, as the non-exiting error loops report.  The reference's report loops
+ * for reasons 2 and 3 (ice_itd.F90:1046, :1067) read nd as the preceding loop left it, not the cell's own donor; this call uses the
+ * cell's own donor.  linear_itd's own rules keep its transfers inside these checks: a daice or dvice below puny times the donor's is
+ * reset with donor = 0, one above (1 - puny) times it becomes the whole category, so no input reaches a stop through the remapping
+ * of a non-negative state; the checks are made all the same.
+ * Or 1 with evpk_last_error, before any copy: a missing pointer, ncat > 16, ntrcr > 32, puny != 1e-11, tr_pond_topo without fpond,
+ * ntrcr > 0 without nt_Tsfc; a context of several ranks (nranks > 1) on which evpk_connect has not run.
+ * x-slab ranks: not collective -- each rank runs its own blocks, and a rank without a block column returns 0. */
+#define EVPK_HAS_LINEAR_ITD 1
+#define EVPK_LITD_STOP 15
+int evpk_linear_itd(evpk_ctx *c, int32_t ncat, int32_t ntrcr, int32_t ntrcr_dim, const int32_t *trcr_depend,
+                    const evpk_itd_tracers *t, const double *hin_max /* 0:ncat */, double hi_min,
+                    const evpk_itd_constants *k,
+                    const double *aicen_init, const double *vicen_init,          /* in, (nx_block,ny_block,ncat,nblocks) */
+                    double *aicen, double *vicen, double *vsnon, double *trcrn,  /* in / out */
+                    double *aice, double *aice0,                                 /* out, every cell */
+                    double *fpond,                                               /* in / out, may be NULL unless tr_pond_topo */
+                    int32_t stop[4] /* out: reason, block, i, j */);
+
 /* everything of step_dynamics behind evp / eap (ice_step_mod.F90:1126-1192) in one call, on state staged once.
  *
  * evpk_bound_state: bound_state (ice_state.F90:173-238) alone -- ice_HaloUpdate, centre scalar, fill 0, of aicen, trcrn(1:ntrcr), vicen,
