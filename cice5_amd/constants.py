@@ -26,6 +26,7 @@ Tocnfrz = -1.8
 ice_ref_salinity = 5.0
 hs_min = 1.0e-4
 cp_ice = 2106.0
+cp_ocn = 4218.0                       # specific heat of the ocean (J/kg/K), drivers/cice/ice_constants.F90
 Lfresh = 2.835e6 - 2.501e6          # Lsub - Lvap
 Tmin = -100.0
 

@@ -33,6 +33,7 @@
 #include "evpk_remap.hip"
 #include "evpk_ridge.hip"
 #include "evpk_itd.hip"
+#include "evpk_therm2.hip"
 #include "evpk_eap.hip"
 
 using namespace evpk;
@@ -4250,6 +4251,153 @@ extern "C" int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t s
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
     dg.fpond = x.fpond; dg.fresh = x.fresh; dg.fhocn = x.fhocn;
     const int rc = dyn_stages(c, x, &dg, stop);
+    if (rc == 1) return 1;
+    const std::string keep = c->err;
+    if (stage_out(c, arr)) return 1;
+    if (rc) c->err = keep;
+    return rc;
+}
+
+// ---- step_therm2 (source/ice_step_mod.F90:741-995) in one call: the frain line, aggregate_area, linear_itd, add_new_ice with
+// lateral_melt (kernels in evpk_therm2.hip), cleanup_itd ----
+// what both entry points refuse, and the kernel arguments of one call on the pointers of x (the caller's own, or device pointers)
+static int therm2_args(evpk_ctx *c, const char *who, const evpk_therm2_args &x, ItdArgs &A, Therm2Args &T) {
+    const evpk_itd_tracers &t = x.t;
+    if (t.tr_brine || x.skl_bgc) FAIL(c, "%s: tr_brine / skl_bgc (add_new_ice_bgc) are not supported", who);
+    if (x.tr_aero) FAIL(c, "%s: aerosol tracers (tr_aero) are not supported: faero_ocn cannot be passed", who);
+    if (x.nbtrcr > 0) FAIL(c, "%s: nbtrcr = %d: bgc tracers are not supported: flux_bio cannot be passed", who, x.nbtrcr);
+    if (!x.heat_capacity) FAIL(c, "%s: heat_capacity = .false. is not supported", who);
+    if (x.ktherm != 1 && x.ktherm != 2) FAIL(c, "%s: ktherm = %d not 1 or 2", who, x.ktherm);
+    if (x.kitd != 0 && x.kitd != 1) FAIL(c, "%s: kitd = %d not 0 or 1", who, x.kitd);
+    if (!x.hin_max || !x.aicen_init || !x.vicen_init || !x.aicen || !x.vicen || !x.vsnon || !x.aice || !x.aice0 || !x.frzmlt || !x.Tf || !x.sss ||
+        !x.rside || !x.salinz || !x.frazil || !x.meltl || !x.fresh || !x.fsalt || !x.fhocn || x.ntrcr < 0 || x.ntrcr_dim < x.ntrcr ||
+        (x.ntrcr > 0 && (!x.trcrn || !x.trcr_depend)))
+        FAIL(c, "%s: a required argument is missing", who);
+    if (!c->connected) FAIL(c, "%s: the context is not connected yet (evpk_connect)", who);
+    if (!c->have_params) FAIL(c, "%s: evpk_set_params has not been called (rhow, rhoi, rhos)", who);
+    if (!(x.dt > 0.0)) FAIL(c, "%s: dt = %g", who, x.dt);
+    if (x.ncat < 1 || x.ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, x.ncat, MAXCAT);
+    if (x.ntrcr > RG_MAXT) FAIL(c, "%s: ntrcr = %d exceeds %d", who, x.ntrcr, RG_MAXT);
+    if (x.k.puny != 1.0e-11) FAIL(c, "%s: puny = %g: compute_tracers on the device is built with 1e-11", who, x.k.puny);
+    if (tracer_tables(c, who, A, x.ntrcr, x.trcr_depend, t, x.nt_vlvl)) return 1;
+    if (x.ntrcr > 0 && (t.nt_Tsfc < 1 || t.nt_qice < 1 || x.nt_sice < 1)) FAIL(c, "%s: nt_Tsfc, nt_qice and nt_sice are required", who);
+    if (t.nilyr > T2_MAXL || t.nslyr > T2_MAXL) FAIL(c, "%s: nilyr = %d, nslyr = %d exceed %d", who, t.nilyr, t.nslyr, T2_MAXL);
+    if (x.ntrcr > 0 && x.nt_sice + t.nilyr - 1 > x.ntrcr) FAIL(c, "%s: nt_sice / nilyr beyond ntrcr", who);
+    for (int q : {x.nt_iage, x.nt_FY, x.nt_vlvl}) if (q < 0 || q > x.ntrcr) FAIL(c, "%s: tracer index %d not in 0..ntrcr = %d", who, q, x.ntrcr);
+    if ((t.tr_pond_cesm || t.tr_pond_lvl) && t.nt_apnd < 1) FAIL(c, "%s: ponds without nt_apnd", who);
+    if (t.tr_pond_lvl && (t.nt_alvl < 1 || x.nt_vlvl < 1)) FAIL(c, "%s: tr_pond_lvl without nt_alvl / nt_vlvl", who);
+    if (t.tr_pond_topo && !x.fpond) FAIL(c, "%s: tr_pond_topo needs fpond", who);
+    A.nt_Tsfc = t.nt_Tsfc; A.nt_qice = t.nt_qice; A.nilyr = x.ntrcr ? t.nilyr : 0; A.nt_qsno = t.nt_qsno; A.nslyr = x.ntrcr ? t.nslyr : 0;
+    A.nt_alvl = t.nt_alvl; A.nt_apnd = t.nt_apnd; A.nt_hpnd = t.nt_hpnd; A.tr_pond_topo = t.tr_pond_topo ? 1 : 0;
+    A.ncat = x.ncat; A.ntrcr = x.ntrcr; A.ntrcr_dim = x.ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb;
+    A.dt = x.dt; A.salinity = x.k.ice_ref_salinity; A.cp_ice = x.k.cp_ice; A.Lfresh = x.k.Lfresh; A.puny = x.k.puny; A.rhoi = c->p.rhoi;
+    A.rhos = c->p.rhos;
+    A.hin_max[0] = x.hin_max[0];
+    A.aicen = x.aicen; A.vicen = x.vicen; A.vsnon = x.vsnon; A.trcrn = x.ntrcr ? x.trcrn : nullptr; A.aice = x.aice; A.aice0 = x.aice0;
+    A.fpond = t.tr_pond_topo ? x.fpond : nullptr; A.fresh = x.fresh; A.fsalt = x.fsalt; A.fhocn = x.fhocn;
+    T.aicen_init = x.aicen_init; T.vicen_init = x.vicen_init; T.frain = x.frain; T.frzmlt = x.frzmlt; T.Tf = x.Tf; T.sss = x.sss; T.rside = x.rside;
+    T.salinz = x.salinz; T.frazil = x.frazil; T.frz_onset = x.frz_onset; T.meltl = x.meltl;
+    T.ktherm = x.ktherm; T.update_ocn_f = x.update_ocn_f ? 1 : 0; T.nt_sice = x.nt_sice; T.nt_iage = x.nt_iage; T.nt_FY = x.nt_FY;
+    T.nt_vlvl = x.nt_vlvl; T.tr_pond_cesm = t.tr_pond_cesm ? 1 : 0; T.tr_pond_lvl = t.tr_pond_lvl ? 1 : 0;
+    T.yday = x.yday; T.hfrazilmin = x.hfrazilmin; T.phi_init = x.phi_init; T.dSin0_frazil = x.dSin0_frazil; T.cp_ocn = x.cp_ocn; T.rhow = c->p.rhow;
+    T.hi0max = x.ncat > 1 ? x.hin_max[1] * 0.9 : 1.0e30;  // ice_therm_itd.F90:1416-1420 (bignum)
+    return 0;
+}
+
+// the caller's arrays of section 1 (and of the stages around it when `step`), each staged once or used in place
+static std::vector<HostArr> therm2_arrays(evpk_ctx *c, const evpk_therm2_args &a, evpk_therm2_args &x, bool step) {
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a.ncat;
+    const bool tr = a.ntrcr > 0;
+    std::vector<HostArr> arr = {
+        {a.aicen_init, n3, &x.aicen_init, false}, {a.vicen_init, n3, &x.vicen_init, false},
+        {a.aicen, n3, &x.aicen, true}, {a.vicen, n3, &x.vicen, true}, {a.vsnon, n3, &x.vsnon, true},
+        {tr ? a.trcrn : nullptr, n3 * a.ntrcr_dim, &x.trcrn, true}, {a.aice, N, &x.aice, step}, {a.aice0, N, &x.aice0, true},
+        {a.frzmlt, N, &x.frzmlt, false}, {a.Tf, N, &x.Tf, false}, {a.sss, N, &x.sss, false}, {a.rside, N, &x.rside, false},
+        {a.salinz, N * (a.t.nilyr + 1), &x.salinz, false}, {a.frazil, N, &x.frazil, true}, {a.frz_onset, N, &x.frz_onset, true},
+        {a.meltl, N, &x.meltl, true}, {(a.t.tr_pond_topo || step) ? a.fpond : nullptr, N, &x.fpond, true}, {a.fresh, N, &x.fresh, true},
+        {a.fsalt, N, &x.fsalt, true}, {a.fhocn, N, &x.fhocn, true}};
+    if (step) {
+        arr.push_back({a.frain, N, &x.frain, false});
+        arr.push_back({a.first_ice, n3, &x.first_ice, true});
+    }
+    return arr;
+}
+
+extern "C" int evpk_new_ice_lateral_melt(evpk_ctx *c, const evpk_therm2_args *a) {
+    if (!c) return 1;
+    RANKS_ENTRY(c, "evpk_new_ice_lateral_melt");
+    if (!a) FAIL(c, "evpk_new_ice_lateral_melt: a required argument is missing");
+    ItdArgs A{};
+    Therm2Args T{};
+    if (therm2_args(c, "evpk_new_ice_lateral_melt", *a, A, T)) return 1;
+    if (!c->nblocks || c->check_only) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    evpk_therm2_args x = *a;
+    std::vector<HostArr> arr = therm2_arrays(c, *a, x, false);
+    if (stage_in(c, arr)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    if (therm2_args(c, "evpk_new_ice_lateral_melt", x, A, T)) return 1;
+    const dim3 b(64), g = block_grid(c);
+    if (a->ncat == 5 && A.nilyr == 4)
+        hipLaunchKernelGGL((k_therm2_leads<5, 4>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A, T);
+    else
+        hipLaunchKernelGGL((k_therm2_leads<0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A, T);
+    HIPCHK(c, hipGetLastError());
+    return stage_out(c, arr);
+}
+
+// the stages of evpk_step_therm2 on the arrays of x; a stop fills stop[0] with the stage and stop[1..4] with its numbers
+static int therm2_stages(evpk_ctx *c, const evpk_therm2_args &x, int32_t stop[5]) {
+    int32_t s4[4] = {0, 0, 0, 0};
+    if (!c->check_only && c->nblocks) {                   // the frain line and aggregate_area on every cell
+        ItdArgs A{};
+        Therm2Args T{};
+        if (therm2_args(c, "evpk_step_therm2", x, A, T)) return 1;
+        with_ncat(x.ncat, [&](auto NC) {
+            constexpr int nc = decltype(NC)::value;
+            hipLaunchKernelGGL(k_therm2_open<nc>, block_grid(c), dim3(64), 0, c->stream, A, T.frain);
+        });
+        HIPCHK(c, hipGetLastError());
+    }
+    int rc = 0;
+    if (x.kitd == 1) {
+        rc = evpk_linear_itd(c, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, &x.t, x.hin_max, x.hi_min, &x.k, x.aicen_init, x.vicen_init, x.aicen,
+                             x.vicen, x.vsnon, x.trcrn, x.aice, x.aice0, x.fpond, s4);
+        if (rc) {
+            if (rc == EVPK_LITD_STOP) { stop[0] = 1; for (int q = 0; q < 4; q++) stop[1 + q] = s4[q]; }
+            return rc;
+        }
+    }
+    rc = evpk_new_ice_lateral_melt(c, &x);
+    if (rc) return rc;
+    rc = evpk_cleanup_itd(c, x.dt, x.ncat, x.ntrcr, x.ntrcr_dim, x.trcr_depend, &x.t, x.hin_max, &x.k, x.tr_aero, x.nbtrcr, x.heat_capacity, x.aicen,
+                          x.vicen, x.vsnon, x.trcrn, x.aice0, x.aice, x.fpond, x.fresh, x.fsalt, x.fhocn, x.first_ice, s4);
+    if (rc == EVPK_ITD_STOP) { stop[0] = 3; for (int q = 0; q < 4; q++) stop[1 + q] = s4[q]; }
+    return rc;
+}
+
+extern "C" int evpk_step_therm2(evpk_ctx *c, const evpk_therm2_args *a, int32_t stop[5]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
+    RANKS_ENTRY(c, "evpk_step_therm2");
+    if (!a || !stop) FAIL(c, "evpk_step_therm2: a required argument is missing");
+    {       // what the stages refuse, before the first copy: each of them with the caller's own pointers, returning after its checks
+        ItdArgs A{};
+        Therm2Args T{};
+        if (therm2_args(c, "evpk_step_therm2", *a, A, T)) return 1;
+        int32_t s5[5] = {0, 0, 0, 0, 0};
+        c->check_only = true;
+        const int rc = therm2_stages(c, *a, s5);
+        c->check_only = false;
+        if (rc) return rc;
+    }
+    if (!c->nblocks) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    evpk_therm2_args x = *a;
+    std::vector<HostArr> arr = therm2_arrays(c, *a, x, true);
+    if (stage_in(c, arr, true)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    const int rc = therm2_stages(c, x, stop);
     if (rc == 1) return 1;
     const std::string keep = c->err;
     if (stage_out(c, arr)) return 1;

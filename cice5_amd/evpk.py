@@ -97,7 +97,8 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_transport_upwind", "evpk_remap_init", "evpk_transport_remap", "evpk_transport_remap_state",
            "evpk_eap_init", "evpk_eap_upload", "evpk_eap_download", "evpk_halo_update", "evpk_halo_update_stress",
            "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
-           "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics", "evpk_linear_itd"]
+           "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics", "evpk_linear_itd",
+           "evpk_new_ice_lateral_melt", "evpk_step_therm2"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -147,6 +148,25 @@ class DynArgs(ct.Structure):
 
 
 DYN_STAGES = {1: "transport", 2: "ridge_ice", 3: "cleanup_itd"}
+
+
+class Therm2Args(ct.Structure):
+    """evpk_therm2_args (include/evpk.h), member for member"""
+    _fields_ = ([("kitd", ct.c_int32), ("ktherm", ct.c_int32), ("update_ocn_f", ct.c_int32)] +
+                [(n, ct.c_double) for n in ("dt", "yday", "hi_min", "hfrazilmin", "phi_init", "dSin0_frazil", "cp_ocn")] +
+                [("ncat", ct.c_int32), ("ntrcr", ct.c_int32), ("ntrcr_dim", ct.c_int32), ("trcr_depend", c_i32p),
+                 ("t", ItdTracers), ("nt_sice", ct.c_int32), ("nt_iage", ct.c_int32), ("nt_FY", ct.c_int32), ("nt_vlvl", ct.c_int32),
+                 ("hin_max", c_f64p), ("k", ItdConstants),
+                 ("tr_aero", ct.c_int32), ("nbtrcr", ct.c_int32), ("heat_capacity", ct.c_int32), ("skl_bgc", ct.c_int32)] +
+                [(n, c_f64p) for n in ("aicen_init", "vicen_init", "aicen", "vicen", "vsnon", "trcrn", "aice", "aice0", "frain", "frzmlt", "Tf",
+                                       "sss", "rside", "salinz", "frazil", "frz_onset", "meltl", "fpond", "fresh", "fsalt", "fhocn")] +
+                [("first_ice", c_i32p)])
+
+
+THERM2_STAGES = {1: "linear_itd", 3: "cleanup_itd"}
+THERM2_STATE = ["aicen_init", "vicen_init", "aicen", "vicen", "vsnon", "trcrn", "aice", "aice0"]
+THERM2_FORCING = ["frain", "frzmlt", "Tf", "sss", "rside", "salinz"]
+THERM2_FLUXES = ["frazil", "frz_onset", "meltl", "fpond", "fresh", "fsalt", "fhocn"]
 
 
 def remap_tracer_tables(trcr_depend):
@@ -230,6 +250,8 @@ def lib():
                                      [c_f64p] * 12)
         L.evpk_bound_state.argtypes = [ctxp] + [ct.c_int32] * 3 + [c_f64p] * 4
         L.evpk_step_dynamics.argtypes = [ctxp, ct.POINTER(DynArgs), c_i32p]
+        L.evpk_new_ice_lateral_melt.argtypes = [ctxp, ct.POINTER(Therm2Args)]
+        L.evpk_step_therm2.argtypes = [ctxp, ct.POINTER(Therm2Args), c_i32p]
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -661,6 +683,63 @@ class Context:
         if rc in (REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS, RIDGE_STOP, ITD_STOP):
             return (int(rc),) + tuple(int(v) for v in stop)
         self._chk(rc, "evpk_step_dynamics")
+        return None
+
+    def _therm2_args(self, dt, state, forcing, fluxes, ntrcr, trcr_depend, tracers, hin_max, kitd, ktherm, update_ocn_f, yday, hi_min, hfrazilmin,
+                     phi_init, dSin0_frazil, cp_ocn, constants, first_ice, tr_aero, nbtrcr, heat_capacity, skl_bgc):
+        from . import constants as C
+        a = Therm2Args()
+        a.kitd, a.ktherm, a.update_ocn_f = int(kitd), int(ktherm), int(bool(update_ocn_f))
+        a.dt, a.yday, a.hi_min, a.hfrazilmin = float(dt), float(yday), float(hi_min), float(hfrazilmin)
+        a.phi_init, a.dSin0_frazil, a.cp_ocn = float(phi_init), float(dSin0_frazil), float(C.cp_ocn if cp_ocn is None else cp_ocn)
+        aicen, trcrn = state.get("aicen"), state.get("trcrn")
+        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
+        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
+        dep = np.ascontiguousarray(trcr_depend, dtype=np.int32)
+        a.trcr_depend = _p32(dep) if ntrcr else None
+        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        a.nt_sice, a.nt_iage, a.nt_FY, a.nt_vlvl = (int(tracers.get(k, 0)) for k in ("nt_sice", "nt_iage", "nt_FY", "nt_vlvl"))
+        hin = np.ascontiguousarray(hin_max, dtype=np.float64)
+        assert hin.shape == (a.ncat + 1,) or aicen is None
+        a.hin_max = _p64(hin)
+        a.k = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
+        a.tr_aero, a.nbtrcr, a.heat_capacity, a.skl_bgc = int(bool(tr_aero)), int(nbtrcr), int(bool(heat_capacity)), int(bool(skl_bgc))
+        for names, src in ((THERM2_STATE, state), (THERM2_FORCING, forcing), (THERM2_FLUXES, fluxes)):
+            for n in names:
+                setattr(a, n, _p64(src.get(n)))
+        a.first_ice = _p32(first_ice)
+        return a, [dep, hin]
+
+    def new_ice_lateral_melt(self, dt: float, state, forcing, fluxes, ntrcr: int, trcr_depend, tracers, hin_max, ktherm=1, update_ocn_f=False,
+                             yday=0.0, hfrazilmin=0.05, phi_init=0.75, dSin0_frazil=3.0, cp_ocn=None, constants=None, tr_aero=False, nbtrcr=0,
+                             heat_capacity=True, skl_bgc=False):
+        """evpk_new_ice_lateral_melt: add_new_ice, lateral_melt and (ncat = 1) reduce_area of step_therm2 in one launch, on the aice / aice0
+        given.  state: dict of THERM2_STATE -- aicen_init / vicen_init / aicen / vicen / vsnon (nb, ncat, ny, nx), trcrn (nb, ncat, ntrcr_dim,
+        ny, nx), aice / aice0 (nb, ny, nx); forcing: dict of THERM2_FORCING (nb, ny, nx), salinz (nb, nilyr + 1, ny, nx), frain not read;
+        fluxes: dict of THERM2_FLUXES (nb, ny, nx), frz_onset may be absent, fpond unless tr_pond_topo.  tracers: dict of
+        ITD_TRACER_FIELDS plus nt_sice, nt_iage, nt_FY, nt_vlvl.  Raises on a refusal, which leaves every array untouched."""
+        a, keep = self._therm2_args(dt, state, forcing, fluxes, ntrcr, trcr_depend, tracers, hin_max, 0, ktherm, update_ocn_f, yday, 0.0, hfrazilmin,
+                                    phi_init, dSin0_frazil, cp_ocn, constants, None, tr_aero, nbtrcr, heat_capacity, skl_bgc)
+        rc = self._L.evpk_new_ice_lateral_melt(self._ctx, ct.byref(a))
+        del keep
+        self._chk(rc, "evpk_new_ice_lateral_melt")
+
+    def step_therm2(self, dt: float, state, forcing, fluxes, ntrcr: int, trcr_depend, tracers, hin_max, kitd=1, ktherm=1, update_ocn_f=False,
+                    yday=0.0, hi_min=0.01, hfrazilmin=0.05, phi_init=0.75, dSin0_frazil=3.0, cp_ocn=None, constants=None, first_ice=None,
+                    tr_aero=False, nbtrcr=0, heat_capacity=True, skl_bgc=False):
+        """evpk_step_therm2: step_therm2 in one call, the arrays staged once -- the frain line, aggregate_area, linear_itd (kitd = 1),
+        add_new_ice, lateral_melt, cleanup_itd(dt).  Arguments as for new_ice_lateral_melt; forcing may hold frain; first_ice: int32
+        (nb, ncat, ny, nx) or None.
+        Returns None, or (code, stage, reason, block, i, j) when a stage stops (code: LITD_STOP, ITD_STOP; stage: THERM2_STAGES); raises on
+        a refusal, which leaves every array untouched."""
+        a, keep = self._therm2_args(dt, state, forcing, fluxes, ntrcr, trcr_depend, tracers, hin_max, kitd, ktherm, update_ocn_f, yday, hi_min,
+                                    hfrazilmin, phi_init, dSin0_frazil, cp_ocn, constants, first_ice, tr_aero, nbtrcr, heat_capacity, skl_bgc)
+        stop = np.zeros(5, dtype=np.int32)
+        rc = self._L.evpk_step_therm2(self._ctx, ct.byref(a), _p32(stop))
+        del keep
+        if rc in (LITD_STOP, ITD_STOP):
+            return (int(rc),) + tuple(int(v) for v in stop)
+        self._chk(rc, "evpk_step_therm2")
         return None
 
     def eap_init(self, tables):

@@ -146,6 +146,24 @@
          type (c_ptr) :: diag = c_null_ptr              ! c_loc of an evpk_ridge_diag, or c_null_ptr
       end type evpk_dyn_args
 
+      ! evpk_therm2_args (include/evpk.h): the arguments of evpk_step_therm2 and evpk_new_ice_lateral_melt, member for member
+      type, bind(C) :: evpk_therm2_args
+         integer (c_int32_t) :: kitd = 1, ktherm = 1, update_ocn_f = 0
+         real (c_double) :: dt, yday, hi_min, hfrazilmin, phi_init, dSin0_frazil, cp_ocn
+         integer (c_int32_t) :: ncat, ntrcr, ntrcr_dim
+         type (c_ptr) :: trcr_depend = c_null_ptr
+         type (evpk_itd_tracers) :: t
+         integer (c_int32_t) :: nt_sice = 0, nt_iage = 0, nt_FY = 0, nt_vlvl = 0
+         type (c_ptr) :: hin_max = c_null_ptr
+         type (evpk_itd_constants) :: k
+         integer (c_int32_t) :: tr_aero = 0, nbtrcr = 0, heat_capacity = 1, skl_bgc = 0
+         type (c_ptr) :: aicen_init = c_null_ptr, vicen_init = c_null_ptr
+         type (c_ptr) :: aicen = c_null_ptr, vicen = c_null_ptr, vsnon = c_null_ptr, trcrn = c_null_ptr, aice = c_null_ptr, aice0 = c_null_ptr
+         type (c_ptr) :: frain = c_null_ptr, frzmlt = c_null_ptr, Tf = c_null_ptr, sss = c_null_ptr, rside = c_null_ptr, salinz = c_null_ptr
+         type (c_ptr) :: frazil = c_null_ptr, frz_onset = c_null_ptr, meltl = c_null_ptr, fpond = c_null_ptr, fresh = c_null_ptr
+         type (c_ptr) :: fsalt = c_null_ptr, fhocn = c_null_ptr, first_ice = c_null_ptr
+      end type evpk_therm2_args
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -157,7 +175,8 @@
                 evpk_eap_state, evpk_eap_init, evpk_eap_upload, evpk_eap_download, &
                 evpk_ridge_tracers, evpk_ridge_diag, evpk_ridge_ice, EVPK_RIDGE_STOP, &
                 evpk_itd_tracers, evpk_itd_constants, evpk_cleanup_itd, evpk_aggregate, EVPK_ITD_STOP, &
-                evpk_dyn_args, evpk_bound_state, evpk_step_dynamics, evpk_linear_itd, EVPK_LITD_STOP
+                evpk_dyn_args, evpk_bound_state, evpk_step_dynamics, evpk_linear_itd, EVPK_LITD_STOP, &
+                evpk_therm2_args, evpk_new_ice_lateral_melt, evpk_step_therm2
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
@@ -357,6 +376,21 @@
             import :: c_int, c_ptr, c_int32_t, evpk_dyn_args
             type (c_ptr), value :: ctx
             type (evpk_dyn_args), intent(in) :: a
+            integer (c_int32_t), intent(out) :: stop(5)
+         end function
+         ! add_new_ice, lateral_melt and (ncat = 1) reduce_area of step_therm2 (ice_step_mod.F90:875-960) in one launch, on the aice / aice0
+         ! given: for a host that keeps its own linear_itd
+         integer (c_int) function evpk_new_ice_lateral_melt (ctx, a) bind(C, name='evpk_new_ice_lateral_melt')
+            import :: c_int, c_ptr, evpk_therm2_args
+            type (c_ptr), value :: ctx
+            type (evpk_therm2_args), intent(in) :: a
+         end function
+         ! step_therm2 (ice_step_mod.F90:741-995) in one call, the arrays staged once: the frain line, aggregate_area, linear_itd
+         ! (kitd = 1), add_new_ice, lateral_melt, cleanup_itd; stop(5): stage (1 linear_itd, 3 cleanup), reason, block, i, j
+         integer (c_int) function evpk_step_therm2 (ctx, a, stop) bind(C, name='evpk_step_therm2')
+            import :: c_int, c_ptr, c_int32_t, evpk_therm2_args
+            type (c_ptr), value :: ctx
+            type (evpk_therm2_args), intent(in) :: a
             integer (c_int32_t), intent(out) :: stop(5)
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then

@@ -522,6 +522,71 @@ typedef struct {
 } evpk_dyn_args;
 int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t stop[5] /* out: stage, reason, block, i, j */);
 
+/* step_therm2 (source/ice_step_mod.F90:741-995) in one call, on state staged once.
+ *
+ * evpk_new_ice_lateral_melt: what step_therm2 does between linear_itd and cleanup_itd, in ONE launch, for every block of the context:
+ * add_new_ice (source/ice_therm_itd.F90:1239-1850, l_conservation_check = .false.), lateral_melt (:1043-1217) and, when ncat == 1,
+ * reduce_area (ice_itd.F90:743-806).  It runs on the aice / aice0 it is given (aggregate_area is the caller's, or evpk_linear_itd's),
+ * has no stop and is not collective; it is there for a host that keeps its own linear_itd.  Array conventions as evpk_cleanup_itd.
+ * Per physical ocean cell (tmask), in the reference's order and operation order:
+ *   add_new_ice   hi0max = 0.9 hin_max(1) (bignum = 1e30 for ncat == 1); qi0new = -rhoi * Lfresh and Sprofile = salinz(1:nilyr) for
+ *                 ktherm == 1; for ktherm == 2 Si0new from sss (both cases of :1468-1472), Ti = min(liquidus_temperature_mush(Si0new /
+ *                 phi_init), -0.1), qi0new = enthalpy_mush(Ti, Si0new) through liquid_fraction and liquidus_brine_salinity_mush
+ *                 (ice_therm_mushy.F90:3687-3756, :3903-3918) with that module's liquidus parameters compiled in (:43-123, derived in its
+ *                 expression order; the merge masks are multiplications); fnew, vi0new, frazil; frz_onset when given; the update_ocn_f /
+ *                 mushy-return increments of fresh, fsalt; the distribution decision with its four outcomes; the surplus loop over all
+ *                 categories (iage, vlvl, the volume, then update_vertical_tracers on qice and sice for ktherm == 2 or the bulk mix for
+ *                 ktherm == 1); the category-1 merge (Tsfc and FY with their clamps, iage, alvl / vlvl, the three pond rules, qice / sice)
+ *   lateral_melt  for n = 1 .. ncat, where rside > 0: dfresh, dfsalt, dfpond under topo ponds, meltl, the three state scalings, then
+ *                 fhocn over the ice layers and the snow layers with the scaled vicen / vsnon; n outer, the layers inner
+ *   reduce_area   when ncat == 1, with aicen_init / vicen_init
+ * A cell with frzmlt <= 0 and rside <= 0 writes frazil (0) and nothing else and reads no tracer.  nt_iage, nt_FY, nt_vlvl (with
+ * t.nt_alvl) switch tr_iage, tr_FY, tr_lvl; ntrcr == 0 leaves every tracer statement out.
+ * Departures: (a) lateral_melt's cell list is physical cells with tmask and rside > 0 (the reference: every physical cell with
+ * rside > 0; land carries no ice); land and ghost cells of every array keep the caller's values.  (b) In the ktherm /= 2 surplus loop the
+ * reference indexes qi0new and Sprofile with the counter of the compressed surplus list, not with the cell's own index (:1688, :1691):
+ * harmless for qi0new, one constant there, but Sprofile then is the salinz profile of another ocean cell of the block.  This call uses the
+ * cell's own profile; the two agree whenever salinz is horizontally uniform, which is how init_thermo_vertical fills it
+ * (ice_therm_vertical.F90:575-591) -- salinz must be horizontally uniform for parity.  (c) add_new_ice_bgc, aerosols and bgc tracers
+ * are refused.
+ * Parity: held bit for bit to a numpy restatement written from the Fortran (tests/nptherm2.py); add_new_ice, lateral_melt and the mushy
+ * liquidus are NOT pinned to reference-built output yet.
+ *
+ * evpk_step_therm2: the frain line (ice_step_mod.F90:804-809: fresh += frain * aice on every cell, ghost cells included, on the aice of
+ * entry), aggregate_area on every cell, evpk_linear_itd when kitd == 1, evpk_new_ice_lateral_melt, evpk_cleanup_itd(dt) -- bit for bit
+ * those entry points called in that order, with every caller array the device cannot see copied up at most once and down at most once
+ * (page-locked and device arrays are used in place).  fresh is the reference's sum in its order: frain, add_new_ice, lateral_melt
+ * n = 1 .. ncat, cleanup_itd.  A stop returns the stage's code, EVPK_LITD_STOP or EVPK_ITD_STOP, with stop[0] = 1 (linear_itd) or 3
+ * (cleanup_itd) and stop[1..4] that stage's numbers; later stages do not run and the arrays are undefined.
+ * Members (one struct of borrowed pointers; arrays (nx_block, ny_block[, ncat | nilyr+1], nblocks)):
+ *   kitd (0 / 1), ktherm (1 / 2), update_ocn_f; dt, yday, hi_min, hfrazilmin, phi_init, dSin0_frazil, cp_ocn
+ *   ncat, ntrcr, ntrcr_dim, trcr_depend, t, nt_sice, nt_iage, nt_FY, nt_vlvl; hin_max(0:ncat); k (puny must be 1e-11)
+ *   tr_aero, nbtrcr, heat_capacity, skl_bgc      only 0, 0, 1, 0 are accepted; rhow, rhoi, rhos come from evpk_params
+ *   aicen_init, vicen_init                       in (read by linear_itd and reduce_area)
+ *   aicen, vicen, vsnon, trcrn, aice, aice0      in / out
+ *   frain, frzmlt, Tf, sss, rside, salinz        in; salinz (nx_block, ny_block, nilyr+1, nblocks)
+ *   frazil, frz_onset, meltl, fpond, fresh, fsalt, fhocn, first_ice     in / out
+ * May be NULL (that increment is skipped): frain; frz_onset (with it yday is not read); fpond unless tr_pond_topo; first_ice.
+ * Both return 1 with evpk_last_error before any copy, touching nothing: tr_brine or skl_bgc, tr_aero, nbtrcr > 0, heat_capacity = 0,
+ * ktherm not 1 or 2, a missing pointer, nt_Tsfc / nt_qice / nt_sice not given while ntrcr > 0, nilyr or nslyr > 8, ncat > 16,
+ * ntrcr > 32, puny != 1e-11, a context of several ranks (nranks > 1) on which evpk_connect has not run.
+ * x-slab ranks: neither call is collective -- each rank runs its own blocks, and a rank without a block column returns 0. */
+#define EVPK_HAS_STEP_THERM2 1
+typedef struct {
+    int32_t kitd, ktherm, update_ocn_f;
+    double dt, yday, hi_min, hfrazilmin, phi_init, dSin0_frazil, cp_ocn;
+    int32_t ncat, ntrcr, ntrcr_dim; const int32_t *trcr_depend;
+    evpk_itd_tracers t; int32_t nt_sice, nt_iage, nt_FY, nt_vlvl;
+    const double *hin_max; evpk_itd_constants k;
+    int32_t tr_aero, nbtrcr, heat_capacity, skl_bgc;
+    const double *aicen_init, *vicen_init;                    /* in */
+    double *aicen, *vicen, *vsnon, *trcrn, *aice, *aice0;     /* in / out */
+    const double *frain, *frzmlt, *Tf, *sss, *rside, *salinz; /* in; frain may be NULL */
+    double *frazil, *frz_onset, *meltl, *fpond, *fresh, *fsalt, *fhocn; int32_t *first_ice;
+} evpk_therm2_args;
+int evpk_new_ice_lateral_melt(evpk_ctx *c, const evpk_therm2_args *a);
+int evpk_step_therm2(evpk_ctx *c, const evpk_therm2_args *a, int32_t stop[5] /* out: stage, reason, block, i, j */);
+
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared
  * (:79-80), stress_eap (:1052-1467) with update_stress_rdg (:1474-1658) takes the place of stress, stepa (:1664-1787, with

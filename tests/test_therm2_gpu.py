@@ -1,0 +1,399 @@
+"""evpk_new_ice_lateral_melt and evpk_step_therm2 on the device against the numpy restatement tests/nptherm2.py -- bit for bit: the routines
+use only + - x / , comparisons and selects, the library is built with -ffp-contract=off.  Parity with the reference is unpinned for
+add_new_ice, lateral_melt and the mushy liquidus (no reference-built record); cleanup_itd, shift_ice and compute_tracers of the chain are
+pinned (tests/test_itd_ref.py).  Inputs: tests/golden/therm2vec.py (no shape larger than 26 x 18 cells); tests/test_therm2_host.py shows
+that they take every branch.
+"""
+import os
+import sys
+import traceback
+import uuid
+
+import numpy as np
+import pytest
+
+try:
+    import torch          # before libevpk: the process must end up with ONE HIP runtime (torch bundles its own)
+    torch.cuda.is_available()
+except ImportError:
+    torch = None
+
+from cice5_amd import blocks, constants as C
+from cice5_amd import dyn, evpk, synth
+from tests import nplitd
+from tests.golden import itdvec as iv
+from tests.golden import therm2vec as tv
+from tests.test_therm2_host import restate, restate_step
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SENTINEL = -777.25
+BCASE = "cyclic_open"
+IN = ["aicen_init", "vicen_init", "frain", "frzmlt", "Tf", "sss", "rside", "salinz"]
+OUT2D = ["aice", "aice0"] + tv.FLUXES
+
+
+def geometry(cfg, nprocs=1, rank=0):
+    """the context arguments of one rank and the whole-domain decomposition"""
+    nx, ny, bx, by, _ = tv.CONFIGS[cfg]
+    ew, ns, _ = iv.BOUNDS[BCASE]
+    d1 = blocks.create_distrb_cart(nx, ny, bx, by, ew_boundary_type=ew, ns_boundary_type=ns)
+    d = d1 if nprocs == 1 else blocks.create_distrb_cart(nx, ny, bx, by, nprocs=nprocs, rank=rank, ew_boundary_type=ew, ns_boundary_type=ns)
+    f = synth.make_block_fields(synth.SynthCase(nx=nx, ny=ny, ew_boundary=C.BND_NAMES[ew], ns_boundary=C.BND_NAMES[ns]), d)
+    return d1, d, f
+
+
+def params(x):
+    p = dyn.set_evp_parameters(3600.0, 4, False, 1.0e4, ncat=5)
+    p.rhow, p.rhoi, p.rhos = x["rhow"], x["k"]["rhoi"], x["k"]["rhos"]
+    return p
+
+
+@pytest.fixture(scope="module")
+def contexts():
+    made = {}
+
+    def get(cfg):
+        if cfg not in made:
+            x = inputs(cfg, "plain")
+            _, d, f = geometry(cfg)
+            f["tmask"] = x["tmask"]                 # the land of the inputs
+            made[cfg] = evpk.Context(d, f)
+            made[cfg].set_params(params(x))
+        return made[cfg]
+    yield get
+    for c in made.values():
+        c.close()
+
+
+_inputs, _want = {}, {}
+
+
+def inputs(cfg, tcase, ncat=5):
+    key = (cfg, tcase, ncat)
+    if key not in _inputs:
+        _inputs[key] = tv.therm2_input(cfg, tcase, ncat=ncat)
+    return _inputs[key]
+
+
+def wanted(cfg, tcase, ktherm, ncat=5, update_ocn_f=False):
+    """the restatement of section 1 alone: computed once per case, shared, not modified"""
+    key = (cfg, tcase, ktherm, ncat, update_ocn_f)
+    if key not in _want:
+        _want[key] = restate(inputs(cfg, tcase, ncat), ktherm, update_ocn_f)[0]
+    return _want[key]
+
+
+def outputs(x):
+    return {k: x[k].copy() for k in tv.OUT}
+
+
+def scalars(x, **kw):
+    a = dict(ntrcr=x["ntrcr"], trcr_depend=x["trcr_depend"], tracers=x["tracers"], hin_max=x["hin_max"], yday=x["yday"],
+             hfrazilmin=x["hfrazilmin"], phi_init=x["phi_init"], dSin0_frazil=x["dSin0_frazil"], cp_ocn=x["cp_ocn"], constants=x["k"])
+    a.update(kw)
+    return a
+
+
+def dicts(x, y):
+    """state, forcing, fluxes of one call: what the call writes from y, the rest from x"""
+    g = lambda k: y[k] if k in y else x.get(k)
+    return ({k: g(k) for k in evpk.THERM2_STATE}, {k: g(k) for k in evpk.THERM2_FORCING}, {k: g(k) for k in evpk.THERM2_FLUXES})
+
+
+def leads(ctx, x, y, ktherm=1, update_ocn_f=False, **kw):
+    st, fo, fl = dicts(x, y)
+    return ctx.new_ice_lateral_melt(x["dt"], st, fo, fl, ktherm=ktherm, update_ocn_f=update_ocn_f, **scalars(x, **kw))
+
+
+def step(ctx, x, y, kitd=1, ktherm=1, update_ocn_f=False, **kw):
+    st, fo, fl = dicts(x, y)
+    return ctx.step_therm2(x["dt"], st, fo, fl, kitd=kitd, ktherm=ktherm, update_ocn_f=update_ocn_f, hi_min=x["hi_min"],
+                           first_ice=y.get("first_ice"), **scalars(x, **kw))
+
+
+def eq(a, b):
+    return bool(((a == b) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def cells(a, m):
+    """a[..., cells of m] with the block axis first"""
+    return np.moveaxis(a, (0, -2, -1), (0, 1, 2))[m]
+
+
+def assert_section1(x, got, want, keys=None):
+    """every array: the restatement on the physical ocean cells, untouched elsewhere (the restatement writes ocean cells only)"""
+    for k in keys or (iv.STATE + ["aice0"] + tv.FLUXES):
+        if got.get(k) is not None:
+            assert eq(got[k], want[k]), (k, int((got[k] != want[k]).sum()))
+
+
+@pytest.mark.parametrize("cfg", list(tv.CONFIGS))
+@pytest.mark.parametrize("tcase", tv.POND_CASES)
+@pytest.mark.parametrize("ktherm", [1, 2])
+def test_section_equals_restatement_and_leaves_land_and_ghost_cells(contexts, cfg, tcase, ktherm):
+    """both grids, four tracer tables, both ktherm, ncat = 5 (k_therm2_leads<5, 4>): physical ocean cells equal the restatement; land,
+    ghost and padding cells of every array keep a sentinel"""
+    ctx = contexts(cfg)
+    x, want = inputs(cfg, tcase), wanted(cfg, tcase, ktherm)
+    y = outputs(x)
+    keys = iv.STATE + ["aice0"] + tv.FLUXES
+    for k in keys:
+        cells(y[k], ~x["ocean"])[...] = SENTINEL
+    before = {k: y[k].copy() for k in keys}
+    leads(ctx, x, y, ktherm)
+    m = x["ocean"]
+    for k in keys:
+        assert eq(cells(y[k], m), cells(want[k], m)), (k, int((cells(y[k], m) != cells(want[k], m)).sum()))
+        assert eq(cells(y[k], ~m), cells(before[k], ~m)), k
+    assert eq(y["aice"], x["aice"])
+    if not x["tracers"].get("tr_pond_topo"):
+        assert eq(y["fpond"], before["fpond"])
+
+
+@pytest.mark.parametrize("ktherm", [1, 2])
+def test_update_ocn_f(contexts, ktherm):
+    ctx = contexts("g24x16_b6x4")
+    x, want = inputs("g24x16_b6x4", "lvl_ponds"), wanted("g24x16_b6x4", "lvl_ponds", ktherm, update_ocn_f=True)
+    off = wanted("g24x16_b6x4", "lvl_ponds", ktherm)
+    assert not eq(want["fresh"], off["fresh"]) and not eq(want["fsalt"], off["fsalt"])
+    y = outputs(x)
+    leads(ctx, x, y, ktherm, update_ocn_f=True)
+    assert_section1(x, y, want)
+
+
+@pytest.mark.parametrize("ncat,tcase,ktherm", [(3, "lvl_ponds", 2), (3, "topo_ponds", 1), (1, "lvl_ponds", 1), (1, "cesm_ponds", 2)])
+def test_generic_kernel_and_reduce_area(contexts, ncat, tcase, ktherm):
+    """k_therm2_leads<0, 0>; ncat = 1 ends in reduce_area (hin_max(0) = 0 and 0.1)"""
+    ctx = contexts("g26x18_b8x5")
+    x, want = inputs("g26x18_b8x5", tcase, ncat), wanted("g26x18_b8x5", tcase, ktherm, ncat)
+    y = outputs(x)
+    leads(ctx, x, y, ktherm)
+    assert_section1(x, y, want)
+    assert ncat > 1 or not eq(want["aicen"], x["aicen"])
+
+
+@pytest.mark.parametrize("ktherm", [1, 2])
+def test_table_without_age_first_year_level_ice_and_ponds(contexts, ktherm):
+    ctx = contexts("g26x18_b8x5")
+    x, want = inputs("g26x18_b8x5", "bare"), wanted("g26x18_b8x5", "bare", ktherm)
+    y = dict(outputs(x), fpond=None)
+    leads(ctx, dict(x, fpond=None), y, ktherm)
+    assert_section1(x, y, want)
+
+
+def test_frz_onset_none(contexts):
+    ctx = contexts("g26x18_b8x5")
+    x0 = inputs("g26x18_b8x5", "cesm_ponds")
+    x = dict(x0, frz_onset=None)
+    want, _ = restate(x, 1)
+    assert eq(want["frazil"], wanted("g26x18_b8x5", "cesm_ponds", 1)["frazil"])
+    y = dict(outputs(x0), frz_onset=None)
+    leads(ctx, x, y, 1)
+    assert_section1(x, y, want)
+
+
+def test_device_pointers_and_pageable_arrays_agree(contexts):
+    ctx = contexts("g26x18_b8x5")
+    x, want = inputs("g26x18_b8x5", "topo_ponds"), wanted("g26x18_b8x5", "topo_ponds", 2)
+    y = outputs(x)
+    assert not evpk.host_is_mapped(y["aicen"])
+    leads(ctx, x, y, 2)
+    names = [k for k in tv.OUT if k != "first_ice"] + IN
+    dev = {k: torch.from_numpy(x[k].copy()).cuda() for k in names}
+    leads(ctx, x, dev, 2)
+    torch.cuda.synchronize()
+    for k in tv.OUT:
+        if k != "first_ice":
+            assert eq(dev[k].cpu().numpy(), y[k]), k
+    assert_section1(x, y, want)
+
+
+def compare_step(x, got, want):
+    """state on the physical ocean cells (the reference zeroes land tracers in a block that shifts, the device leaves them), the 2-D
+    outputs on every cell"""
+    m = x["ocean"]
+    for k in iv.STATE + ["first_ice"]:
+        if got.get(k) is not None:
+            assert np.array_equal(cells(got[k], m), cells(want[k], m)), (k, int((cells(got[k], m) != cells(want[k], m)).sum()))
+    for k in OUT2D:
+        if got.get(k) is not None:
+            assert eq(got[k], want[k]), (k, int((got[k] != want[k]).sum()))
+
+
+@pytest.mark.parametrize("kitd,ktherm,tcase", [(1, 1, "lvl_ponds"), (1, 2, "topo_ponds"), (0, 2, "plain"), (0, 1, "cesm_ponds")])
+def test_step_therm2_equals_the_chain_and_the_separate_calls(contexts, kitd, ktherm, tcase):
+    """one call against nptherm2.step_therm2, and against the frain line, [aggregate_area | evpk_linear_itd], evpk_new_ice_lateral_melt,
+    evpk_cleanup_itd called one after the other -- that comparison on every element of every array"""
+    cfg = "g26x18_b8x5"
+    ctx = contexts(cfg)
+    x = inputs(cfg, tcase)
+    want, infos, stop = restate_step(x, kitd, ktherm)
+    assert stop is None
+    y = outputs(x)
+    assert step(ctx, x, y, kitd, ktherm) is None
+    compare_step(x, y, want)
+    z = outputs(x)
+    z["fresh"] = z["fresh"] + x["frain"] * z["aice"]
+    if kitd == 1:
+        assert ctx.linear_itd(x["aicen_init"], x["vicen_init"], z["aicen"], z["vicen"], z["vsnon"], z["trcrn"], z["aice"], z["aice0"], x["ntrcr"],
+                              x["trcr_depend"], x["tracers"], x["hin_max"], x["hi_min"], x["k"], z["fpond"]) is None
+    else:
+        for b in range(z["aicen"].shape[0]):
+            nplitd.aggregate_area(z["aicen"][b], z["aice"][b], z["aice0"][b])
+    leads(ctx, x, z, ktherm)
+    assert ctx.cleanup_itd(x["dt"], z["aicen"], z["vicen"], z["vsnon"], z["trcrn"], z["aice0"], z["aice"], x["ntrcr"], x["trcr_depend"], x["tracers"],
+                           x["hin_max"], x["k"], {k: z[k] for k in iv.FLUX}, z["first_ice"]) is None
+    for k in tv.OUT:
+        assert eq(y[k], z[k]), (k, int((y[k] != z[k]).sum()))
+
+
+def test_step_therm2_without_frain_and_first_ice_on_device_arrays(contexts):
+    cfg, tcase = "g24x16_b6x4", "lvl_ponds"
+    ctx = contexts(cfg)
+    x = dict(inputs(cfg, tcase), frain=None)
+    want, infos, stop = restate_step(x, 1, 2)
+    assert stop is None
+    names = [k for k in tv.OUT if k != "first_ice"] + [k for k in IN if k != "frain"]
+    dev = {k: torch.from_numpy(x[k].copy()).cuda() for k in names}
+    assert step(ctx, x, dev, 1, 2) is None
+    torch.cuda.synchronize()
+    compare_step(x, {k: dev[k].cpu().numpy() for k in names}, want)
+
+
+def test_cleanup_stop_arrives_as_stage_3(contexts):
+    ctx = contexts("g26x18_b8x5")
+    x = tv.stop_input()
+    y = outputs(x)
+    assert step(ctx, x, y, kitd=0) == (evpk.ITD_STOP, 3) + x["stop_expect"]
+
+
+def test_refusals_leave_the_arrays_untouched(contexts):
+    ctx = contexts("g26x18_b8x5")
+    x = inputs("g26x18_b8x5", "topo_ponds")
+    y = outputs(x)
+    nb, ncat, nt, ny, nx = x["trcrn"].shape
+    z = lambda *s: np.zeros(s)
+    for fn in (leads, step):
+        R = lambda match, xx=x, yy=y, **kw: _refused(fn, ctx, xx, yy, match, **kw)
+        R("tr_brine / skl_bgc", tracers=dict(x["tracers"], tr_brine=1))
+        R("tr_brine / skl_bgc", skl_bgc=True)
+        R("aerosol tracers", tr_aero=True)
+        R("nbtrcr = 2", nbtrcr=2)
+        R("heat_capacity", heat_capacity=False)
+        R("ktherm = 0 not 1 or 2", ktherm=0)
+        R("a required argument is missing", yy=dict(y, aice0=None))
+        R("a required argument is missing", yy=dict(y, trcrn=None))
+        R("a required argument is missing", yy=dict(y, meltl=None))
+        R("a required argument is missing", xx=dict(x, salinz=None))
+        R("a required argument is missing", xx=dict(x, vicen_init=None))
+        R("tr_pond_topo needs fpond", yy=dict(y, fpond=None))
+        R("nt_Tsfc, nt_qice and nt_sice are required", tracers=dict(x["tracers"], nt_sice=0))
+        R("nt_Tsfc, nt_qice and nt_sice are required", tracers=dict(x["tracers"], nt_Tsfc=0))
+        R("nilyr = 9", tracers=dict(x["tracers"], nilyr=9))
+        R("ntrcr = 33 exceeds 32", yy=dict(y, trcrn=z(nb, ncat, 33, ny, nx)), ntrcr=33, trcr_depend=np.zeros(33, dtype=np.int32))
+        R("puny = 1e-12", constants=dict(x["k"], puny=1.0e-12))
+        big = {k: z(nb, 17, ny, nx) for k in ("aicen_init", "vicen_init", "aicen", "vicen", "vsnon")}
+        R("ncat = 17 not in", xx=dict(x, **big), yy=dict(y, trcrn=z(nb, 17, nt, ny, nx), **big), hin_max=np.zeros(18))
+    for k in tv.OUT:
+        assert eq(y[k], x[k]), k
+
+
+def _refused(fn, ctx, x, y, match, **kw):
+    with pytest.raises(evpk.EvpkError, match=match):
+        fn(ctx, x, y, **kw)
+    return True
+
+
+def test_refusal_on_more_than_one_rank_before_connect():
+    x = inputs("g26x18_b8x5", "plain")
+    _, d, f = geometry("g26x18_b8x5", nprocs=2, rank=0)
+    ctx = evpk.Context(d, f, defer_connect=True)    # (the geometry says two ranks; nothing collective has happened)
+    try:
+        at = [b.block_id for b in d.local_blocks]
+        assert len(at) > 0
+        loc = list(range(len(at)))
+        xx = {k: (np.ascontiguousarray(v[loc]) if isinstance(v, np.ndarray) and v.ndim >= 3 else v) for k, v in x.items()}
+        y = outputs(xx)
+        for fn in (leads, step):
+            with pytest.raises(evpk.EvpkError, match="nranks = 2"):
+                fn(ctx, xx, y)
+    finally:
+        ctx.close()
+
+
+# ---- x-slab ranks: one process per rank on one GPU (the harness of tests/test_litd_gpu.py) ----
+CFG = "g26x18_b8x5"
+
+
+def job_therm2(rank, world, tag, tcase, kitd, ktherm):
+    d1, d, f = geometry(CFG, world, rank)
+    at = {b.block_id: n for n, b in enumerate(d1.local_blocks)}
+    loc = [at[b.block_id] for b in d.local_blocks]
+    x = tv.therm2_input(CFG, tcase)
+    f["tmask"] = np.ascontiguousarray(x["tmask"][loc])
+    cut = lambda a: np.ascontiguousarray(a[loc])
+    ctx = evpk.Context(d, f, device=0, unique_id=(b"EVPKIPC:" + f"{tag}_0".encode()).ljust(128, b"\0"))
+    try:
+        ctx.set_params(params(x))
+        xx = dict(x, **{k: cut(x[k]) for k in IN})
+        y = {k: cut(x[k]) for k in tv.OUT}
+        stop = step(ctx, xx, y, kitd, ktherm)
+    finally:
+        ctx.close()
+    return loc, y, stop
+
+
+def _worker(rank, world, tag, job, args, q):
+    try:
+        sys.path.insert(0, ROOT)
+        os.environ["OMP_NUM_THREADS"] = "2"
+        q.put((rank, None, globals()[job](rank, world, tag, *args)))
+    except Exception:
+        q.put((rank, traceback.format_exc(), None))
+
+
+def _spawn(world, job, args=(), timeout=240):
+    import multiprocessing as mp
+    assert world <= 5                              # (+ the parent: at most 6 processes hold the GPU)
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    tag = "evpk_therm2_" + uuid.uuid4().hex[:12]
+    procs = [ctx.Process(target=_worker, args=(r, world, tag, job, args, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = {}
+    try:
+        for _ in procs:
+            rank, err, out = q.get(timeout=timeout)
+            assert err is None, f"rank {rank}: {err}"
+            res[rank] = out
+    finally:
+        for p in procs:
+            p.join(timeout=1 if len(res) < world else 30)
+            if p.is_alive():
+                p.kill()
+        try:
+            os.unlink(f"/dev/shm/{tag}_0")
+        except OSError:
+            pass
+    return [res[r] for r in range(world)]
+
+
+def test_ranks_equal_the_one_rank_result(contexts):
+    """three rank processes on one GPU, of which two own block columns and the third owns none: put together, the ranks' blocks equal the
+    one-rank device result on every element; the rank without a block column returns 0"""
+    tcase, kitd, ktherm = "topo_ponds", 1, 2
+    x = inputs(CFG, tcase)
+    one = outputs(x)
+    assert step(contexts(CFG), x, one, kitd, ktherm) is None
+    outs = _spawn(3, "job_therm2", (tcase, kitd, ktherm))
+    assert [len(loc) > 0 for loc, _, _ in outs] == [True, True, False] and all(stop is None for _, _, stop in outs)
+    seen = sorted(n for loc, _, _ in outs for n in loc)
+    assert seen == list(range(x["aicen"].shape[0]))
+    for loc, y, _ in outs[:2]:
+        for k in tv.OUT:
+            assert eq(y[k], one[k][loc]), k
+    for k in tv.OUT:                                # the idle rank's (empty) arrays are what it passed
+        assert outs[2][1][k].shape[0] == 0
