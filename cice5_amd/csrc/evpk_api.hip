@@ -34,6 +34,7 @@
 #include "evpk_ridge.hip"
 #include "evpk_itd.hip"
 #include "evpk_therm2.hip"
+#include "evpk_therm1.hip"
 #include "evpk_eap.hip"
 
 using namespace evpk;
@@ -616,10 +617,12 @@ template <class T> static hipError_t grow(evpk_ctx *c, T *&p, size_t &n, size_t 
 }
 
 // the caller's arrays of one call: in place where the device sees them (mapped_alias, array by array), else through a staging copy -- up
-// into one pool, and down again at the end if the array is an output.  A NULL or empty array gets a null device pointer.
+// into one pool, and down again at the end if the array is an output.  A NULL or empty array gets a null device pointer.  in = false: an
+// array the call writes on every element before it reads it -- it gets its place in the pool and is not copied up.
 struct HostArr {
-    void *host; size_t bytes; void **slot; bool out; bool staged = false;
-    template <class T, class U> HostArr(T *h, size_t count, U **dev, bool o) : host((void *)h), bytes(sizeof(T) * count), slot((void **)dev), out(o) {}
+    void *host; size_t bytes; void **slot; bool out; bool in; bool staged = false;
+    template <class T, class U> HostArr(T *h, size_t count, U **dev, bool o, bool i = true)
+        : host((void *)h), bytes(sizeof(T) * count), slot((void **)dev), out(o), in(i) {}
 };
 // (the upward copies are asynchronous on c->stream: the caller synchronises once, with whatever else it sends from pageable memory)
 static int stage_in(evpk_ctx *c, std::vector<HostArr> &arr, bool dyn = false) {
@@ -634,7 +637,7 @@ static int stage_in(evpk_ctx *c, std::vector<HostArr> &arr, bool dyn = false) {
     double *q = pool;
     for (HostArr &a : arr)
         if (a.staged) {
-            HIPCHK(c, hipMemcpyAsync(q, a.host, a.bytes, hipMemcpyHostToDevice, c->stream));
+            if (a.in) HIPCHK(c, hipMemcpyAsync(q, a.host, a.bytes, hipMemcpyHostToDevice, c->stream));
             *a.slot = q; q += (a.bytes + 7) / 8;
         }
     return 0;
@@ -4403,6 +4406,81 @@ extern "C" int evpk_step_therm2(evpk_ctx *c, const evpk_therm2_args *a, int32_t 
     if (stage_out(c, arr)) return 1;
     if (rc) c->err = keep;
     return rc;
+}
+
+// ---- thermo_vertical (source/ice_therm_vertical.F90:79-531), BL99, for every category of every block in one launch (kernel in
+// evpk_therm1.hip) ----
+extern "C" int evpk_thermo_vertical(evpk_ctx *c, const evpk_thermo_args *a, int32_t stop[5]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
+    RANKS_ENTRY(c, "evpk_thermo_vertical");
+    if (!a || !stop) FAIL(c, "evpk_thermo_vertical: a required argument is missing");
+    const evpk_itd_tracers &t = a->t;
+    if (a->ktherm != 1) FAIL(c, "evpk_thermo_vertical: ktherm = %d: only ktherm = 1 (BL99) is supported", a->ktherm);
+    if (a->calc_Tsfc != 1) FAIL(c, "evpk_thermo_vertical: calc_Tsfc = .false. is not supported");
+    if (a->heat_capacity != 1) FAIL(c, "evpk_thermo_vertical: heat_capacity = .false. (zero-layer) is not supported");
+    if (a->l_brine != 1) FAIL(c, "evpk_thermo_vertical: l_brine = .false. (fresh ice) is not supported");
+    if (a->conduct != 0 && a->conduct != 1) FAIL(c, "evpk_thermo_vertical: conduct = %d not 0 (MU71) or 1 (bubbly)", a->conduct);
+    if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->flw || !a->potT || !a->Qa || !a->rhoa || !a->fsnow || !a->fbot || !a->Tbot ||
+        !a->sss || !a->shcoef || !a->lhcoef || !a->fswsfcn || !a->fswintn || !a->Sswabsn || !a->Iswabsn || !a->mlt_onset || !a->frz_onset ||
+        !a->flwoutn || !a->evapn || !a->freshn || !a->fsaltn || !a->fhocnn || !a->fsensn || !a->flatn || !a->fsurfn || !a->fcondtopn ||
+        !a->melttn || !a->meltsn || !a->meltbn || !a->congeln || !a->snoicen || !a->dsnown || a->ntrcr < 1 || a->ntrcr_dim < a->ntrcr)
+        FAIL(c, "evpk_thermo_vertical: a required argument is missing");
+    if (!c->connected) FAIL(c, "evpk_thermo_vertical: the context is not connected yet (evpk_connect)");
+    if (!c->have_params) FAIL(c, "evpk_thermo_vertical: evpk_set_params has not been called (rhow, rhoi, rhos)");
+    if (!(a->dt > 0.0)) FAIL(c, "evpk_thermo_vertical: dt = %g", a->dt);
+    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "evpk_thermo_vertical: ncat = %d not in 1..%d", a->ncat, MAXCAT);
+    if (a->ntrcr > RG_MAXT) FAIL(c, "evpk_thermo_vertical: ntrcr = %d exceeds %d", a->ntrcr, RG_MAXT);
+    if (a->k.puny != 1.0e-11) FAIL(c, "evpk_thermo_vertical: puny = %g: the device code is built with 1e-11", a->k.puny);
+    if (t.nt_Tsfc < 1 || t.nt_qice < 1 || t.nt_qsno < 1 || a->nt_sice < 1) FAIL(c, "evpk_thermo_vertical: nt_Tsfc, nt_qice, nt_qsno and nt_sice are required");
+    if (t.nilyr < 1 || t.nslyr < 1 || t.nilyr > T1_MAXL || t.nslyr > T1_MAXL)
+        FAIL(c, "evpk_thermo_vertical: nilyr = %d, nslyr = %d not in 1..%d", t.nilyr, t.nslyr, T1_MAXL);
+    if (t.nt_Tsfc > a->ntrcr || t.nt_qice + t.nilyr - 1 > a->ntrcr || t.nt_qsno + t.nslyr - 1 > a->ntrcr || a->nt_sice + t.nilyr - 1 > a->ntrcr)
+        FAIL(c, "evpk_thermo_vertical: a tracer index lies beyond ntrcr = %d", a->ntrcr);
+    if (t.tr_pond_topo && (!a->fpond || t.nt_apnd < 1 || t.nt_hpnd < 1 || t.nt_apnd > a->ntrcr || t.nt_hpnd > a->ntrcr))
+        FAIL(c, "evpk_thermo_vertical: tr_pond_topo needs fpond, nt_apnd and nt_hpnd");
+    if (c->nblocks >= 65536) FAIL(c, "evpk_thermo_vertical: %d blocks exceed the stop key", c->nblocks);
+    if (!c->nblocks) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    ThermoArgs T{};
+    T.ncat = a->ncat; T.ntrcr_dim = a->ntrcr_dim; T.nxb = c->nxb; T.nyb = c->nyb; T.nilyr = t.nilyr; T.nslyr = t.nslyr;
+    T.nt_Tsfc = t.nt_Tsfc; T.nt_qice = t.nt_qice; T.nt_qsno = t.nt_qsno; T.nt_sice = a->nt_sice; T.nt_apnd = t.nt_apnd; T.nt_hpnd = t.nt_hpnd;
+    T.tr_pond_topo = t.tr_pond_topo ? 1 : 0; T.conduct = a->conduct;
+    T.dt = a->dt; T.yday = a->yday; T.min_salin = a->min_salin; T.puny = a->k.puny; T.rhoi = c->p.rhoi; T.rhos = c->p.rhos; T.rhow = c->p.rhow;
+    T.cp_ice = a->k.cp_ice; T.Lfresh = a->k.Lfresh; T.hs_min = a->k.hs_min; T.Tmin = a->k.Tmin; T.salinity = a->k.ice_ref_salinity;
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
+    std::vector<HostArr> arr = {            // (sss is not staged: ktherm = 1 does not read it; the fifteen outputs are not copied up)
+        {a->aicen, n3, &T.aicen, true}, {a->vicen, n3, &T.vicen, true}, {a->vsnon, n3, &T.vsnon, true}, {a->trcrn, n3 * a->ntrcr_dim, &T.trcrn, true},
+        {a->flw, N, &T.flw, false}, {a->potT, N, &T.potT, false}, {a->Qa, N, &T.Qa, false}, {a->rhoa, N, &T.rhoa, false},
+        {a->fsnow, N, &T.fsnow, false}, {a->fbot, N, &T.fbot, false}, {a->Tbot, N, &T.Tbot, false},
+        {a->shcoef, n3, &T.shcoef, false}, {a->lhcoef, n3, &T.lhcoef, false},
+        {a->fswsfcn, n3, &T.fswsfcn, true}, {a->fswintn, n3, &T.fswintn, true}, {a->Sswabsn, n3 * t.nslyr, &T.Sswabsn, true},
+        {a->Iswabsn, n3 * t.nilyr, &T.Iswabsn, true}, {t.tr_pond_topo ? a->fpond : nullptr, N, &T.fpond, true},
+        {a->mlt_onset, N, &T.mlt_onset, true}, {a->frz_onset, N, &T.frz_onset, true},
+        {a->flwoutn, n3, &T.flwoutn, true, false}, {a->evapn, n3, &T.evapn, true, false}, {a->freshn, n3, &T.freshn, true, false}, {a->fsaltn, n3, &T.fsaltn, true, false},
+        {a->fhocnn, n3, &T.fhocnn, true, false}, {a->fsensn, n3, &T.fsensn, true, false}, {a->flatn, n3, &T.flatn, true, false}, {a->fsurfn, n3, &T.fsurfn, true, false},
+        {a->fcondtopn, n3, &T.fcondtopn, true, false}, {a->melttn, n3, &T.melttn, true, false}, {a->meltsn, n3, &T.meltsn, true, false},
+        {a->meltbn, n3, &T.meltbn, true, false}, {a->congeln, n3, &T.congeln, true, false}, {a->snoicen, n3, &T.snoicen, true, false}, {a->dsnown, n3, &T.dsnown, true, false}};
+    if (stage_in(c, arr, true)) return 1;
+    if (!c->itd_key) HIPCHK(c, hipMalloc(&c->itd_key, sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->itd_key, 0xff, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    const dim3 b(64), g = block_grid(c);
+    if (a->ncat == 5 && t.nilyr == 4 && t.nslyr == 1)
+        hipLaunchKernelGGL((k_thermo_vertical<5, 4, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, T, c->itd_key);
+    else
+        hipLaunchKernelGGL((k_thermo_vertical<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, T, c->itd_key);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long key = ~0ull;
+    HIPCHK(c, hipMemcpyAsync(&key, c->itd_key, sizeof(key), hipMemcpyDeviceToHost, c->stream));
+    if (stage_out(c, arr)) return 1;
+    if (key == ~0ull) return 0;
+    const int seq = (int)((key >> 32) & 0xff), ns = t.nslyr, nl = t.nilyr;
+    const size_t o = (size_t)(key & 0xffffffffull);
+    stop[0] = seq < ns ? T1_STOP_TSN_HIGH : seq < 2 * ns ? T1_STOP_TSN_LOW : seq < 2 * ns + 3 * nl ? T1_STOP_SALIN + (seq - 2 * ns) % 3
+              : seq == 2 * ns + 3 * nl ? T1_STOP_NITER : T1_STOP_ENERGY;
+    stop[1] = (int32_t)(key >> 48) + 1; stop[2] = (int32_t)((key >> 40) & 0xff) + 1; stop[3] = (int32_t)(o % c->nxb) + 1; stop[4] = (int32_t)(o / c->nxb) + 1;
+    return EVPK_THERMO_STOP;
 }
 
 extern "C" int evpk_calibrate(evpk_ctx *c, int32_t nrep) {

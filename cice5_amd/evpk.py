@@ -98,7 +98,7 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_eap_init", "evpk_eap_upload", "evpk_eap_download", "evpk_halo_update", "evpk_halo_update_stress",
            "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
            "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics", "evpk_linear_itd",
-           "evpk_new_ice_lateral_melt", "evpk_step_therm2"]
+           "evpk_new_ice_lateral_melt", "evpk_step_therm2", "evpk_thermo_vertical"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -167,6 +167,25 @@ THERM2_STAGES = {1: "linear_itd", 3: "cleanup_itd"}
 THERM2_STATE = ["aicen_init", "vicen_init", "aicen", "vicen", "vsnon", "trcrn", "aice", "aice0"]
 THERM2_FORCING = ["frain", "frzmlt", "Tf", "sss", "rside", "salinz"]
 THERM2_FLUXES = ["frazil", "frz_onset", "meltl", "fpond", "fresh", "fsalt", "fhocn"]
+
+
+THERMO_STOP = 16
+THERMO_STOP_REASONS = {1: "zTsn > Tmax", 2: "zTsn < Tmin", 3: "zSin < min_salin - puny", 4: "zTin > Tmlts", 5: "zTin < Tmin",
+                       6: "no convergence after nitermax", 7: "ferr > ferrmax"}
+THERMO_STATE = ["aicen", "vicen", "vsnon", "trcrn"]
+THERMO_FORCING = ["flw", "potT", "Qa", "rhoa", "fsnow", "fbot", "Tbot", "sss", "shcoef", "lhcoef"]
+THERMO_INOUT = ["fswsfcn", "fswintn", "Sswabsn", "Iswabsn", "fpond", "mlt_onset", "frz_onset"]
+THERMO_OUT = ["flwoutn", "evapn", "freshn", "fsaltn", "fhocnn", "fsensn", "flatn", "fsurfn", "fcondtopn", "melttn", "meltsn", "meltbn",
+              "congeln", "snoicen", "dsnown"]
+
+
+class ThermoArgs(ct.Structure):
+    """evpk_thermo_args (include/evpk.h), member for member"""
+    _fields_ = ([("dt", ct.c_double), ("yday", ct.c_double)] +
+                [(n, ct.c_int32) for n in ("ktherm", "calc_Tsfc", "heat_capacity", "l_brine", "conduct")] + [("min_salin", ct.c_double)] +
+                [("ncat", ct.c_int32), ("ntrcr", ct.c_int32), ("ntrcr_dim", ct.c_int32), ("t", ItdTracers), ("nt_sice", ct.c_int32),
+                 ("k", ItdConstants)] +
+                [(n, c_f64p) for n in THERMO_STATE + THERMO_FORCING + THERMO_INOUT + THERMO_OUT])
 
 
 def remap_tracer_tables(trcr_depend):
@@ -252,6 +271,7 @@ def lib():
         L.evpk_step_dynamics.argtypes = [ctxp, ct.POINTER(DynArgs), c_i32p]
         L.evpk_new_ice_lateral_melt.argtypes = [ctxp, ct.POINTER(Therm2Args)]
         L.evpk_step_therm2.argtypes = [ctxp, ct.POINTER(Therm2Args), c_i32p]
+        L.evpk_thermo_vertical.argtypes = [ctxp, ct.POINTER(ThermoArgs), c_i32p]
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -740,6 +760,37 @@ class Context:
         if rc in (LITD_STOP, ITD_STOP):
             return (int(rc),) + tuple(int(v) for v in stop)
         self._chk(rc, "evpk_step_therm2")
+        return None
+
+    def thermo_vertical(self, dt: float, state, forcing, inout, out, ntrcr: int, tracers, yday=0.0, conduct=0, min_salin=0.1, constants=None,
+                        ktherm=1, calc_Tsfc=True, heat_capacity=True, l_brine=True):
+        """evpk_thermo_vertical: thermo_vertical (BL99) for every category of every block in one launch.  state: dict of THERMO_STATE --
+        aicen / vicen / vsnon (nb, ncat, ny, nx), trcrn (nb, ncat, ntrcr_dim, ny, nx), in place on the listed cells; forcing: dict of
+        THERMO_FORCING, (nb, ny, nx) and shcoef / lhcoef (nb, ncat, ny, nx); inout: dict of THERMO_INOUT -- fswsfcn / fswintn (nb, ncat, ny,
+        nx), Sswabsn (nb, ncat, nslyr, ny, nx), Iswabsn (nb, ncat, nilyr, ny, nx), fpond (needed with tr_pond_topo only), mlt_onset,
+        frz_onset (nb, ny, nx); out: dict of THERMO_OUT (nb, ncat, ny, nx), written on every cell.  tracers: dict of ITD_TRACER_FIELDS plus
+        nt_sice; conduct: 0 / 'MU71' or 1 / 'bubbly'.
+        Returns None, or (reason, block, category, i, j) for the reference's l_stop cases (THERMO_STOP_REASONS); raises on a refusal,
+        which leaves every array untouched."""
+        from . import constants as C
+        a = ThermoArgs()
+        a.dt, a.yday, a.min_salin = float(dt), float(yday), float(min_salin)
+        a.ktherm, a.calc_Tsfc, a.heat_capacity, a.l_brine = int(ktherm), int(bool(calc_Tsfc)), int(bool(heat_capacity)), int(bool(l_brine))
+        a.conduct = int({"MU71": 0, "bubbly": 1}.get(conduct, conduct))
+        aicen, trcrn = state.get("aicen"), state.get("trcrn")
+        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
+        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
+        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        a.nt_sice = int(tracers.get("nt_sice", 0))
+        a.k = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
+        for names, src in ((THERMO_STATE, state), (THERMO_FORCING, forcing), (THERMO_INOUT, inout), (THERMO_OUT, out)):
+            for n in names:
+                setattr(a, n, _p64(src.get(n)))
+        stop = np.zeros(5, dtype=np.int32)
+        rc = self._L.evpk_thermo_vertical(self._ctx, ct.byref(a), _p32(stop))
+        if rc == THERMO_STOP:
+            return tuple(int(v) for v in stop)
+        self._chk(rc, "evpk_thermo_vertical")
         return None
 
     def eap_init(self, tables):

@@ -164,6 +164,27 @@
          type (c_ptr) :: fsalt = c_null_ptr, fhocn = c_null_ptr, first_ice = c_null_ptr
       end type evpk_therm2_args
 
+      ! evpk_thermo_args (include/evpk.h): the arguments of evpk_thermo_vertical, member for member
+      type, bind(C) :: evpk_thermo_args
+         real (c_double) :: dt, yday
+         integer (c_int32_t) :: ktherm = 1, calc_Tsfc = 1, heat_capacity = 1, l_brine = 1, conduct = 0
+         real (c_double) :: min_salin
+         integer (c_int32_t) :: ncat, ntrcr, ntrcr_dim
+         type (evpk_itd_tracers) :: t
+         integer (c_int32_t) :: nt_sice = 0
+         type (evpk_itd_constants) :: k
+         type (c_ptr) :: aicen = c_null_ptr, vicen = c_null_ptr, vsnon = c_null_ptr, trcrn = c_null_ptr
+         type (c_ptr) :: flw = c_null_ptr, potT = c_null_ptr, Qa = c_null_ptr, rhoa = c_null_ptr, fsnow = c_null_ptr, fbot = c_null_ptr
+         type (c_ptr) :: Tbot = c_null_ptr, sss = c_null_ptr
+         type (c_ptr) :: shcoef = c_null_ptr, lhcoef = c_null_ptr
+         type (c_ptr) :: fswsfcn = c_null_ptr, fswintn = c_null_ptr, Sswabsn = c_null_ptr, Iswabsn = c_null_ptr
+         type (c_ptr) :: fpond = c_null_ptr, mlt_onset = c_null_ptr, frz_onset = c_null_ptr
+         type (c_ptr) :: flwoutn = c_null_ptr, evapn = c_null_ptr, freshn = c_null_ptr, fsaltn = c_null_ptr, fhocnn = c_null_ptr
+         type (c_ptr) :: fsensn = c_null_ptr, flatn = c_null_ptr, fsurfn = c_null_ptr, fcondtopn = c_null_ptr
+         type (c_ptr) :: melttn = c_null_ptr, meltsn = c_null_ptr, meltbn = c_null_ptr, congeln = c_null_ptr, snoicen = c_null_ptr
+         type (c_ptr) :: dsnown = c_null_ptr
+      end type evpk_thermo_args
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -176,12 +197,14 @@
                 evpk_ridge_tracers, evpk_ridge_diag, evpk_ridge_ice, EVPK_RIDGE_STOP, &
                 evpk_itd_tracers, evpk_itd_constants, evpk_cleanup_itd, evpk_aggregate, EVPK_ITD_STOP, &
                 evpk_dyn_args, evpk_bound_state, evpk_step_dynamics, evpk_linear_itd, EVPK_LITD_STOP, &
-                evpk_therm2_args, evpk_new_ice_lateral_melt, evpk_step_therm2
+                evpk_therm2_args, evpk_new_ice_lateral_melt, evpk_step_therm2, &
+                evpk_thermo_args, evpk_thermo_vertical, EVPK_THERMO_STOP
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
       integer (c_int), parameter :: EVPK_ITD_STOP = 14
       integer (c_int), parameter :: EVPK_LITD_STOP = 15
+      integer (c_int), parameter :: EVPK_THERMO_STOP = 16
 
       interface
          integer (c_int) function evpk_get_unique_id (id) bind(C, name='evpk_get_unique_id')
@@ -391,6 +414,14 @@
             import :: c_int, c_ptr, c_int32_t, evpk_therm2_args
             type (c_ptr), value :: ctx
             type (evpk_therm2_args), intent(in) :: a
+            integer (c_int32_t), intent(out) :: stop(5)
+         end function
+         ! thermo_vertical (ice_therm_vertical.F90:79-531, BL99: ktherm = 1, heat_capacity, calc_Tsfc, l_brine) for every category of every
+         ! block in one launch: the call of ice_step_mod.F90:513-540; stop(5): reason 1 .. 7, block, category, i, j
+         integer (c_int) function evpk_thermo_vertical (ctx, a, stop) bind(C, name='evpk_thermo_vertical')
+            import :: c_int, c_ptr, c_int32_t, evpk_thermo_args
+            type (c_ptr), value :: ctx
+            type (evpk_thermo_args), intent(in) :: a
             integer (c_int32_t), intent(out) :: stop(5)
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then

@@ -587,6 +587,83 @@ typedef struct {
 int evpk_new_ice_lateral_melt(evpk_ctx *c, const evpk_therm2_args *a);
 int evpk_step_therm2(evpk_ctx *c, const evpk_therm2_args *a, int32_t stop[5] /* out: stage, reason, block, i, j */);
 
+/* thermo_vertical (source/ice_therm_vertical.F90:79-531) as step_therm1 calls it once per category and block
+ * (source/ice_step_mod.F90:364-540), in ONE launch for every category of every block of the context, on state staged once: the BL99
+ * path -- ktherm = 1, heat_capacity = .true., calc_Tsfc = .true., l_brine = .true.  With it a host whose thickness distribution lives
+ * in device memory runs the vertical thermodynamics, evpk_step_therm2 and evpk_step_dynamics with no state transfer.
+ * Per listed cell and category n = 1 .. ncat, in the reference's order and operation order (k_thermo_vertical, csrc/evpk_therm1.hip):
+ *   init_vertical_profile (:845-1273)       hin, hsn, hilyr, hslyr; zqsn / zTsn with the hs_min rule and the zTsn > 0 reset; zSin, Tmlts,
+ *                                           zqin; zTin through calculate_Tin_from_qin (ice_therm_shared.F90:62-90) with the zTin > 0 reset;
+ *                                           einit; the five stop checks
+ *   temperature_changes (ice_therm_bl99.F90:51-928)   conductivity (:940-1062; conduct 0 'MU71', 1 'bubbly'); the move of excess Iswabs /
+ *                                           Sswabs into fswsfc with the non-CCSM constants frac = 0.9, dTemp = 0.02; the iteration up to
+ *                                           nitermax = 500: surface_heat_flux and dsurface_heat_flux_dTsf (ice_therm_shared.F90:98-226),
+ *                                           the Tsf = -puny reset, get_matrix_elements_calc_Tsfc (:1172-1480, all four l_snow x l_cold
+ *                                           cases), tridiag_solver (:1763-1840), conditions 1 - 5 with avg_Tsf / avg_Tsi, dqmat / einex,
+ *                                           reduce_kh and the reduced conductivity of the next iteration -- a cell leaves the iteration
+ *                                           when its `converged` is true; the final update of flwoutn, fsensn, flatn
+ *   thickness_changes (:1283-2020)          condensation onto snow or ice, bottom growth with qbot and qbotmax, congel, frz_onset,
+ *                                           sublimation and top melt of snow then ice, bottom melt of ice then snow, mlt_onset, melts,
+ *                                           meltt, meltb, fhocnn, snowfall, dsnow, freeboard (:2031-2170, snoice), both adjust_enthalpy
+ *                                           calls (:2177-2280), efinal.  einter is not built: it is only printed
+ *   conservation_check_vthermo (:2283-2406) live code in the reference, hence a stop here
+ *   :482-503                                freshn, fsaltn, fhocnn, and fpond under tr_pond_topo (a category that melted away)
+ *   update_state_vthermo (:2417-2540)       given Tbot as its Tf: a category that melts away gets zero state and Tsfc = Tbot
+ * iage passes through unchanged (the reference's update is commented out, :1599, :2154).  sss is not read when ktherm = 1.
+ * Operation order: min / max are a comparison and a select; exp is the fixed algorithm of ice_strength (dev_exp); x**2, x**3 and x**4
+ * are x*x, x*x*x and (x*x)*(x*x); sqrt is the IEEE one.
+ * Departure: the cell list of ice_step_mod.F90:378-389 (physical cells with aicen(i,j,n) > puny) also requires tmask, as in
+ * evpk_new_ice_lateral_melt; land and ghost cells of the in / out arrays keep the caller's values.
+ * The reference zeroes flwoutn, evapn, freshn, fsaltn, fhocnn, fsensn, flatn, fsurfn, fcondtopn, melttn, meltsn, meltbn, congeln,
+ * snoicen, dsnown on every cell of the block before it starts (:251-280, ice_step_mod.F90:366-371).  Here they are per-category planes
+ * (nx_block, ny_block, ncat, nblocks), written on every cell, ghost cells included: zero wherever the cell is not listed.
+ * Constants: rhow, rhoi, rhos come from evpk_params; ice_ref_salinity, hs_min, cp_ice, Lfresh, Tmin, puny from k.  Compiled in
+ * (drivers/cice/ice_constants.F90 unless another file is named): cp_ocn = 4218 (:29), Lvap = 2.501e6 (:52), Tffresh = 273.15 (:50),
+ * TTTice = 5897.8 (:92), qqqice = 11637800 (:91), emissivity = 0.95 (:27), stefan_boltzmann = 567e-10 (:49), depressT = 0.054 (:31),
+ * ksno = 0.30 (:75), kice = 2.03 (:71); betak = 0.13, kimin = 0.10 (source/ice_therm_bl99.F90:27-28), Tsf_errmax = 5e-4 (:152),
+ * nitermax = 500 (:148); ferrmax = 1e-3 (source/ice_therm_shared.F90:31).
+ * **Parity is unpinned for all of thermo_vertical**: it is held bit for bit to a numpy restatement written from the Fortran
+ * (tests/nptherm1.py); no reference-built record of it exists yet.
+ * Members (one struct of borrowed pointers; arrays (nx_block, ny_block[, ncat], nblocks) unless given):
+ *   dt, yday, ktherm, calc_Tsfc, heat_capacity, l_brine (only 1, 1, 1, 1 are accepted), conduct (0 MU71 / 1 bubbly), min_salin
+ *   ncat, ntrcr, ntrcr_dim, t (nt_Tsfc, nt_qice, nilyr, nt_qsno, nslyr; nt_apnd, nt_hpnd with tr_pond_topo), nt_sice, k
+ *   aicen, vicen, vsnon, trcrn                               in / out
+ *   flw, potT, Qa, rhoa, fsnow, fbot, Tbot, sss              in, 2-D
+ *   shcoef, lhcoef                                           in, per category
+ *   fswsfcn, fswintn, Sswabsn (nx_block, ny_block, nslyr, ncat, nblocks), Iswabsn (.., nilyr, ncat, ..)     in / out, per category
+ *   fpond (may be NULL unless tr_pond_topo), mlt_onset, frz_onset     in / out, 2-D
+ *   the fifteen per-category outputs named above             out
+ * Returns 0; or EVPK_THERMO_STOP with stop[] = {reason, block (local, 1-based), category, i, j}: reason 1 zTsn > Tmax, 2 zTsn < Tmin,
+ * 3 zSin < min_salin - puny, 4 zTin > Tmlts, 5 zTin < Tmin, 6 no convergence after nitermax, 7 ferr > ferrmax -- the stop the reference
+ * would meet first: the lowest block, in it the lowest category, in it the reference's check sequence (reason 1 over the snow layers,
+ * reason 2 over the snow layers, then ice layer by ice layer reasons 3, 4, 5, then 6, then 7), in it the first cell with j outer and i
+ * inner.  After a stop the arrays are undefined.  (Reason 4 cannot occur: zTin = min(root, Tmlts) never exceeds Tmlts.  The check is made.)
+ * Or 1 with evpk_last_error, before any copy, touching nothing: ktherm != 1; calc_Tsfc, heat_capacity or l_brine not 1; conduct not 0
+ * or 1; a missing pointer; nt_Tsfc, nt_qice, nt_qsno or nt_sice not given; nilyr or nslyr > 8; ncat > 16; ntrcr > 32; puny != 1e-11;
+ * tr_pond_topo without fpond, nt_apnd, nt_hpnd; a context of several ranks (nranks > 1) on which evpk_connect has not run.
+ * x-slab ranks: not collective -- each rank runs its own blocks, and a rank without a block column returns 0.
+ * Out of scope: frzmlt_bottom_lateral (its deltaT**m2 is a real power: it needs a fixed-algorithm pow first); atmo_boundary_layer,
+ * increment_age, update_FYarea, the pond routines, merge_fluxes (with these step_therm1 becomes one call); ktherm = 2, zero-layer
+ * thermodynamics, calc_Tsfc = .false., fresh ice (l_brine = .false.); aerosols. */
+#define EVPK_HAS_THERMO_VERTICAL 1
+#define EVPK_THERMO_STOP 16
+typedef struct {
+    double dt, yday;
+    int32_t ktherm, calc_Tsfc, heat_capacity, l_brine, conduct;
+    double min_salin;
+    int32_t ncat, ntrcr, ntrcr_dim;
+    evpk_itd_tracers t; int32_t nt_sice;
+    evpk_itd_constants k;
+    double *aicen, *vicen, *vsnon, *trcrn;                                    /* in / out */
+    const double *flw, *potT, *Qa, *rhoa, *fsnow, *fbot, *Tbot, *sss;         /* in */
+    const double *shcoef, *lhcoef;                                            /* in, per category */
+    double *fswsfcn, *fswintn, *Sswabsn, *Iswabsn;                            /* in / out, per category */
+    double *fpond, *mlt_onset, *frz_onset;                                    /* in / out */
+    double *flwoutn, *evapn, *freshn, *fsaltn, *fhocnn, *fsensn, *flatn, *fsurfn, *fcondtopn;     /* out, per category, every cell */
+    double *melttn, *meltsn, *meltbn, *congeln, *snoicen, *dsnown;
+} evpk_thermo_args;
+int evpk_thermo_vertical(evpk_ctx *c, const evpk_thermo_args *a, int32_t stop[5] /* out: reason, block, category, i, j */);
+
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared
  * (:79-80), stress_eap (:1052-1467) with update_stress_rdg (:1474-1658) takes the place of stress, stepa (:1664-1787, with
