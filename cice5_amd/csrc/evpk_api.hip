@@ -35,6 +35,7 @@
 #include "evpk_itd.hip"
 #include "evpk_therm2.hip"
 #include "evpk_therm1.hip"
+#include "evpk_therm1s.hip"
 #include "evpk_eap.hip"
 
 using namespace evpk;
@@ -350,6 +351,8 @@ struct evpk_ctx {
     // evpk_cleanup_itd: the per-block masks of the boundaries at which a block shifts, the stop key
     unsigned *itd_bmask = nullptr; size_t itd_bmask_n = 0;
     unsigned long long *itd_key = nullptr;
+    // evpk_step_therm1: the per-category planes of atmo_boundary_layer (eight) and fbot, Tbot where the caller does not ask for them
+    double *th1_pool = nullptr; size_t th1_pool_n = 0;
     // evpk_bound_state: whether the blocks are the uniform tiling k_bound_state's block table assumes (0 not looked at yet, 1 yes, -1 no)
     int bs_uniform = 0;
     // ... on x-slab ranks (itd_bound_ranks): local message buffers of the transports without mapped slots, [send | recv] per partner;
@@ -1375,7 +1378,7 @@ static void destroy_impl(evpk_ctx *c) {
     if (c->relay) { c->relay->close_(); delete c->relay; }
     if (c->ipc) { if (c->stream2) (void)hipStreamSynchronize(c->stream2); c->ipc->close_(); delete c->ipc; }
     void *ptrs[] = {c->itd, c->stage_itd, c->d_zflags, c->d_zrows, c->s.F, c->s.tmask, c->s.umask, c->s.iceumask, c->s.cmask, c->s.tmphm, c->d_bd, c->stage, c->d_flags,
-                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->call_stage, c->rm_grid, c->rm_pool, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->dyn_stage, c->d_ns2, c->d_bmap, c->br_buf, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
+                    c->d_strips, c->d_counts, c->tile_buf, c->d_tune, c->d_flags2, c->d_strips2, c->d_strips2e, c->d_strips2i, c->d_band, c->cbuf, c->sendbuf, c->recvbuf, c->foldbuf, c->foldloc, c->foldall, c->d_slab_i0, c->foldseg, c->foldrcv, c->io_raw, c->io_act, c->tp_a, c->tp_b, c->call_stage, c->rm_grid, c->rm_pool, c->rm_tab, c->rm_sgn, c->rm_bad, c->uw_pool, c->uw_tab, c->uw_sgn, c->rg_pool, c->rg_mask, c->rg_flags, c->rg_ctl, c->itd_bmask, c->itd_key, c->th1_pool, c->dyn_stage, c->d_ns2, c->d_bmap, c->br_buf, c->m.F, c->m.cmask, c->d_mslab, c->xb_send, c->xb_recv, c->d_mstrips, c->eap_pool, c->eap_tab, c->sigB, c->sigB1, c->d_dbg, c->up_dat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -4410,36 +4413,43 @@ extern "C" int evpk_step_therm2(evpk_ctx *c, const evpk_therm2_args *a, int32_t 
 
 // ---- thermo_vertical (source/ice_therm_vertical.F90:79-531), BL99, for every category of every block in one launch (kernel in
 // evpk_therm1.hip) ----
+// what evpk_thermo_vertical refuses (coefs: fbot, Tbot, shcoef, lhcoef are inputs; evpk_step_therm1 makes them itself)
+static int thermo_check(evpk_ctx *c, const char *who, const evpk_thermo_args *a, bool coefs) {
+    const evpk_itd_tracers &t = a->t;
+    if (a->ktherm != 1) FAIL(c, "%s: ktherm = %d: only ktherm = 1 (BL99) is supported", who, a->ktherm);
+    if (a->calc_Tsfc != 1) FAIL(c, "%s: calc_Tsfc = .false. is not supported", who);
+    if (a->heat_capacity != 1) FAIL(c, "%s: heat_capacity = .false. (zero-layer) is not supported", who);
+    if (a->l_brine != 1) FAIL(c, "%s: l_brine = .false. (fresh ice) is not supported", who);
+    if (a->conduct != 0 && a->conduct != 1) FAIL(c, "%s: conduct = %d not 0 (MU71) or 1 (bubbly)", who, a->conduct);
+    if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->flw || !a->potT || !a->Qa || !a->rhoa || !a->fsnow || (coefs && (!a->fbot || !a->Tbot)) ||
+        !a->sss || (coefs && (!a->shcoef || !a->lhcoef)) || !a->fswsfcn || !a->fswintn || !a->Sswabsn || !a->Iswabsn || !a->mlt_onset || !a->frz_onset ||
+        !a->flwoutn || !a->evapn || !a->freshn || !a->fsaltn || !a->fhocnn || !a->fsensn || !a->flatn || !a->fsurfn || !a->fcondtopn ||
+        !a->melttn || !a->meltsn || !a->meltbn || !a->congeln || !a->snoicen || !a->dsnown || a->ntrcr < 1 || a->ntrcr_dim < a->ntrcr)
+        FAIL(c, "%s: a required argument is missing", who);
+    if (!c->connected) FAIL(c, "%s: the context is not connected yet (evpk_connect)", who);
+    if (!c->have_params) FAIL(c, "%s: evpk_set_params has not been called (rhow, rhoi, rhos)", who);
+    if (!(a->dt > 0.0)) FAIL(c, "%s: dt = %g", who, a->dt);
+    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, a->ncat, MAXCAT);
+    if (a->ntrcr > RG_MAXT) FAIL(c, "%s: ntrcr = %d exceeds %d", who, a->ntrcr, RG_MAXT);
+    if (a->k.puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->k.puny);
+    if (t.nt_Tsfc < 1 || t.nt_qice < 1 || t.nt_qsno < 1 || a->nt_sice < 1) FAIL(c, "%s: nt_Tsfc, nt_qice, nt_qsno and nt_sice are required", who);
+    if (t.nilyr < 1 || t.nslyr < 1 || t.nilyr > T1_MAXL || t.nslyr > T1_MAXL)
+        FAIL(c, "%s: nilyr = %d, nslyr = %d not in 1..%d", who, t.nilyr, t.nslyr, T1_MAXL);
+    if (t.nt_Tsfc > a->ntrcr || t.nt_qice + t.nilyr - 1 > a->ntrcr || t.nt_qsno + t.nslyr - 1 > a->ntrcr || a->nt_sice + t.nilyr - 1 > a->ntrcr)
+        FAIL(c, "%s: a tracer index lies beyond ntrcr = %d", who, a->ntrcr);
+    if (t.tr_pond_topo && (!a->fpond || t.nt_apnd < 1 || t.nt_hpnd < 1 || t.nt_apnd > a->ntrcr || t.nt_hpnd > a->ntrcr))
+        FAIL(c, "%s: tr_pond_topo needs fpond, nt_apnd and nt_hpnd", who);
+    if (c->nblocks >= 65536) FAIL(c, "%s: %d blocks exceed the stop key", who, c->nblocks);
+    return 0;
+}
+
 extern "C" int evpk_thermo_vertical(evpk_ctx *c, const evpk_thermo_args *a, int32_t stop[5]) {
     if (!c) return 1;
     if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
     RANKS_ENTRY(c, "evpk_thermo_vertical");
     if (!a || !stop) FAIL(c, "evpk_thermo_vertical: a required argument is missing");
+    if (thermo_check(c, "evpk_thermo_vertical", a, true)) return 1;
     const evpk_itd_tracers &t = a->t;
-    if (a->ktherm != 1) FAIL(c, "evpk_thermo_vertical: ktherm = %d: only ktherm = 1 (BL99) is supported", a->ktherm);
-    if (a->calc_Tsfc != 1) FAIL(c, "evpk_thermo_vertical: calc_Tsfc = .false. is not supported");
-    if (a->heat_capacity != 1) FAIL(c, "evpk_thermo_vertical: heat_capacity = .false. (zero-layer) is not supported");
-    if (a->l_brine != 1) FAIL(c, "evpk_thermo_vertical: l_brine = .false. (fresh ice) is not supported");
-    if (a->conduct != 0 && a->conduct != 1) FAIL(c, "evpk_thermo_vertical: conduct = %d not 0 (MU71) or 1 (bubbly)", a->conduct);
-    if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->flw || !a->potT || !a->Qa || !a->rhoa || !a->fsnow || !a->fbot || !a->Tbot ||
-        !a->sss || !a->shcoef || !a->lhcoef || !a->fswsfcn || !a->fswintn || !a->Sswabsn || !a->Iswabsn || !a->mlt_onset || !a->frz_onset ||
-        !a->flwoutn || !a->evapn || !a->freshn || !a->fsaltn || !a->fhocnn || !a->fsensn || !a->flatn || !a->fsurfn || !a->fcondtopn ||
-        !a->melttn || !a->meltsn || !a->meltbn || !a->congeln || !a->snoicen || !a->dsnown || a->ntrcr < 1 || a->ntrcr_dim < a->ntrcr)
-        FAIL(c, "evpk_thermo_vertical: a required argument is missing");
-    if (!c->connected) FAIL(c, "evpk_thermo_vertical: the context is not connected yet (evpk_connect)");
-    if (!c->have_params) FAIL(c, "evpk_thermo_vertical: evpk_set_params has not been called (rhow, rhoi, rhos)");
-    if (!(a->dt > 0.0)) FAIL(c, "evpk_thermo_vertical: dt = %g", a->dt);
-    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "evpk_thermo_vertical: ncat = %d not in 1..%d", a->ncat, MAXCAT);
-    if (a->ntrcr > RG_MAXT) FAIL(c, "evpk_thermo_vertical: ntrcr = %d exceeds %d", a->ntrcr, RG_MAXT);
-    if (a->k.puny != 1.0e-11) FAIL(c, "evpk_thermo_vertical: puny = %g: the device code is built with 1e-11", a->k.puny);
-    if (t.nt_Tsfc < 1 || t.nt_qice < 1 || t.nt_qsno < 1 || a->nt_sice < 1) FAIL(c, "evpk_thermo_vertical: nt_Tsfc, nt_qice, nt_qsno and nt_sice are required");
-    if (t.nilyr < 1 || t.nslyr < 1 || t.nilyr > T1_MAXL || t.nslyr > T1_MAXL)
-        FAIL(c, "evpk_thermo_vertical: nilyr = %d, nslyr = %d not in 1..%d", t.nilyr, t.nslyr, T1_MAXL);
-    if (t.nt_Tsfc > a->ntrcr || t.nt_qice + t.nilyr - 1 > a->ntrcr || t.nt_qsno + t.nslyr - 1 > a->ntrcr || a->nt_sice + t.nilyr - 1 > a->ntrcr)
-        FAIL(c, "evpk_thermo_vertical: a tracer index lies beyond ntrcr = %d", a->ntrcr);
-    if (t.tr_pond_topo && (!a->fpond || t.nt_apnd < 1 || t.nt_hpnd < 1 || t.nt_apnd > a->ntrcr || t.nt_hpnd > a->ntrcr))
-        FAIL(c, "evpk_thermo_vertical: tr_pond_topo needs fpond, nt_apnd and nt_hpnd");
-    if (c->nblocks >= 65536) FAIL(c, "evpk_thermo_vertical: %d blocks exceed the stop key", c->nblocks);
     if (!c->nblocks) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     ThermoArgs T{};
@@ -4481,6 +4491,108 @@ extern "C" int evpk_thermo_vertical(evpk_ctx *c, const evpk_thermo_args *a, int3
               : seq == 2 * ns + 3 * nl ? T1_STOP_NITER : T1_STOP_ENERGY;
     stop[1] = (int32_t)(key >> 48) + 1; stop[2] = (int32_t)((key >> 40) & 0xff) + 1; stop[3] = (int32_t)(o % c->nxb) + 1; stop[4] = (int32_t)(o / c->nxb) + 1;
     return EVPK_THERMO_STOP;
+}
+
+// ---- step_therm1 (source/ice_step_mod.F90:154-733) in one call: k_therm1_open, k_thermo_vertical, k_therm1_merge (evpk_therm1s.hip) on
+// state staged once ----
+extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t stop[5]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
+    RANKS_ENTRY(c, "evpk_step_therm1");
+    if (!a || !stop) FAIL(c, "evpk_step_therm1: a required argument is missing");
+    const char *who = "evpk_step_therm1";
+    const evpk_thermo_args &v = a->tv;
+    const evpk_itd_tracers &t = v.t;
+    if (a->formdrag) FAIL(c, "%s: formdrag (neutral_drag_coeffs) is not supported", who);
+    if (a->highfreq) FAIL(c, "%s: highfreq coupling is not supported", who);
+    if (a->atmbndy_constant) FAIL(c, "%s: atmbndy = 'constant' (atmo_boundary_const) is not supported", who);
+    if (a->fbot_xfer_Cdn_ocn) FAIL(c, "%s: fbot_xfer_type = 'Cdn_ocn' is not supported", who);
+    if (t.tr_pond_lvl) FAIL(c, "%s: tr_pond_lvl (compute_ponds_lvl) is not supported", who);
+    if (t.tr_pond_topo) FAIL(c, "%s: tr_pond_topo (compute_ponds_topo) is not supported", who);
+    if (a->tr_aero) FAIL(c, "%s: aerosol tracers (tr_aero, update_aerosol) are not supported", who);
+    if (thermo_check(c, who, &v, false)) return 1;
+    if (a->natmiter < 1) FAIL(c, "%s: natmiter = %d", who, a->natmiter);
+    if (!a->aice || !a->frzmlt || !a->sst || !a->Tf || !a->strocnxT || !a->strocnyT || !a->uatm || !a->vatm || !a->wind || !a->zlvl || !a->fswthrun ||
+        !a->Cdn_atm || !a->rside || !a->aice_init || !a->aicen_init || !a->vicen_init)
+        FAIL(c, "%s: a required argument is missing", who);
+    double *const merged[T1S_NMERGE] = {a->strairxT, a->strairyT, a->Cdn_atm_ratio, a->fsurf, a->fcondtop, a->fsens, a->flat, a->fswabs, a->flwout, a->evap,
+                                        a->Tref, a->Qref, a->Uref, a->fresh, a->fsalt, a->fhocn, a->fswthru, a->meltt, a->meltb, a->melts, a->congel, a->snoice};
+    for (double *q : merged) if (!q) FAIL(c, "%s: a required argument is missing", who);
+    if (a->tr_iage && (a->nt_iage < 1 || a->nt_iage > v.ntrcr)) FAIL(c, "%s: tr_iage without nt_iage in 1..ntrcr = %d", who, v.ntrcr);
+    if (a->tr_FY && (a->nt_FY < 1 || a->nt_FY > v.ntrcr)) FAIL(c, "%s: tr_FY without nt_FY in 1..ntrcr = %d", who, v.ntrcr);
+    if (a->tr_FY && (!a->lmask_n || !a->lmask_s)) FAIL(c, "%s: tr_FY needs lmask_n and lmask_s", who);
+    if (t.tr_pond_cesm && (t.nt_apnd < 1 || t.nt_hpnd < 1 || t.nt_apnd > v.ntrcr || t.nt_hpnd > v.ntrcr))
+        FAIL(c, "%s: tr_pond_cesm without nt_apnd / nt_hpnd in 1..ntrcr = %d", who, v.ntrcr);
+    if (t.tr_pond_cesm && !a->frain) FAIL(c, "%s: tr_pond_cesm needs frain", who);
+    if (t.tr_pond_cesm && !(a->pndaspect > 0.0)) FAIL(c, "%s: pndaspect = %g", who, a->pndaspect);
+    if (!c->nblocks) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * v.ncat;
+    evpk_thermo_args x = v;                 // thermo_vertical's arguments on device pointers
+    Therm1sArgs A{};
+    double *d_opt[8] = {};                  // shcoef, lhcoef, strairxn, strairyn, Cdn_atm_ratio_n, Trefn, Qrefn, Urefn where the caller gives them
+    double *d_fbot = nullptr, *d_Tbot = nullptr;
+    double *const h_opt[8] = {const_cast<double *>(v.shcoef), const_cast<double *>(v.lhcoef), a->strairxn, a->strairyn, a->Cdn_atm_ratio_n, a->Trefn,
+                              a->Qrefn, a->Urefn};
+    std::vector<HostArr> arr = {            // (sss is not staged: ktherm = 1 does not read it; arrays a call only writes are not copied up)
+        {v.aicen, n3, &x.aicen, true}, {v.vicen, n3, &x.vicen, true}, {v.vsnon, n3, &x.vsnon, true}, {v.trcrn, n3 * v.ntrcr_dim, &x.trcrn, true},
+        {v.flw, N, &x.flw, false}, {v.potT, N, &x.potT, false}, {v.Qa, N, &x.Qa, false}, {v.rhoa, N, &x.rhoa, false}, {v.fsnow, N, &x.fsnow, false},
+        {v.fswsfcn, n3, &x.fswsfcn, true}, {v.fswintn, n3, &x.fswintn, true}, {v.Sswabsn, n3 * t.nslyr, &x.Sswabsn, true},
+        {v.Iswabsn, n3 * t.nilyr, &x.Iswabsn, true}, {v.mlt_onset, N, &x.mlt_onset, true}, {v.frz_onset, N, &x.frz_onset, true},
+        {v.flwoutn, n3, &x.flwoutn, true, false}, {v.evapn, n3, &x.evapn, true, false}, {v.freshn, n3, &x.freshn, true, false}, {v.fsaltn, n3, &x.fsaltn, true, false},
+        {v.fhocnn, n3, &x.fhocnn, true, false}, {v.fsensn, n3, &x.fsensn, true, false}, {v.flatn, n3, &x.flatn, true, false}, {v.fsurfn, n3, &x.fsurfn, true, false},
+        {v.fcondtopn, n3, &x.fcondtopn, true, false}, {v.melttn, n3, &x.melttn, true, false}, {v.meltsn, n3, &x.meltsn, true, false},
+        {v.meltbn, n3, &x.meltbn, true, false}, {v.congeln, n3, &x.congeln, true, false}, {v.snoicen, n3, &x.snoicen, true, false}, {v.dsnown, n3, &x.dsnown, true, false},
+        {const_cast<double *>(v.fbot), N, &d_fbot, true, false}, {const_cast<double *>(v.Tbot), N, &d_Tbot, true, false},
+        {a->aice, N, &A.aice, false}, {a->frzmlt, N, &A.frzmlt, false}, {a->sst, N, &A.sst, false}, {a->Tf, N, &A.Tf, false},
+        {a->strocnxT, N, &A.strocnxT, false}, {a->strocnyT, N, &A.strocnyT, false}, {a->uatm, N, &A.uatm, false}, {a->vatm, N, &A.vatm, false},
+        {a->wind, N, &A.wind, false}, {a->zlvl, N, &A.zlvl, false}, {t.tr_pond_cesm ? a->frain : nullptr, N, &A.frain, false},
+        {a->fswthrun, n3, &A.fswthrun, false}, {a->tr_FY ? a->lmask_n : nullptr, N, &A.lmask_n, false}, {a->tr_FY ? a->lmask_s : nullptr, N, &A.lmask_s, false},
+        {a->Cdn_atm, N, &A.Cdn_atm, true}, {a->rside, N, &A.rside, true, false}, {a->aice_init, N, &A.aice_init, true, false},
+        {a->aicen_init, n3, &A.aicen_init, true, false}, {a->vicen_init, n3, &A.vicen_init, true, false}};
+    for (int q = 0; q < 8; q++) arr.push_back({h_opt[q], n3, &d_opt[q], true, false});
+    for (int q = 0; q < T1S_NMERGE; q++) arr.push_back({merged[q], N, &A.m[q], true});
+    if (stage_in(c, arr, true)) return 1;
+    HIPCHK(c, grow(c, c->th1_pool, c->th1_pool_n, 8 * n3 + 2 * N));        // one pool, grown once
+    for (int q = 0; q < 8; q++) if (!d_opt[q]) d_opt[q] = c->th1_pool + (size_t)q * n3;
+    if (!d_fbot) d_fbot = c->th1_pool + 8 * n3;
+    if (!d_Tbot) d_Tbot = c->th1_pool + 8 * n3 + N;
+    x.fbot = d_fbot; x.Tbot = d_Tbot; x.shcoef = d_opt[0]; x.lhcoef = d_opt[1];
+    x.sss = v.sss;                            // (not read: any non-null pointer passes the check)
+    A.potT = x.potT; A.Qa = x.Qa; A.rhoa = x.rhoa; A.flw = x.flw;
+    A.aicen = x.aicen; A.vicen = x.vicen; A.vsnon = x.vsnon; A.trcrn = x.trcrn;
+    A.fbot = d_fbot; A.Tbot = d_Tbot;
+    A.shcoef = d_opt[0]; A.lhcoef = d_opt[1]; A.strairxn = d_opt[2]; A.strairyn = d_opt[3]; A.Cdn_atm_ratio_n = d_opt[4]; A.Trefn = d_opt[5];
+    A.Qrefn = d_opt[6]; A.Urefn = d_opt[7];
+    A.fswsfcn = x.fswsfcn; A.fswintn = x.fswintn; A.flwoutn = x.flwoutn; A.evapn = x.evapn; A.freshn = x.freshn; A.fsaltn = x.fsaltn; A.fhocnn = x.fhocnn;
+    A.fsensn = x.fsensn; A.flatn = x.flatn; A.fsurfn = x.fsurfn; A.fcondtopn = x.fcondtopn; A.melttn = x.melttn; A.meltsn = x.meltsn; A.meltbn = x.meltbn;
+    A.congeln = x.congeln; A.snoicen = x.snoicen;
+    A.ncat = v.ncat; A.ntrcr_dim = v.ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nilyr = t.nilyr; A.nslyr = t.nslyr; A.nt_Tsfc = t.nt_Tsfc;
+    A.nt_qice = t.nt_qice; A.nt_qsno = t.nt_qsno; A.nt_apnd = t.nt_apnd; A.nt_hpnd = t.nt_hpnd; A.nt_iage = a->nt_iage; A.nt_FY = a->nt_FY;
+    A.tr_iage = a->tr_iage ? 1 : 0; A.tr_FY = a->tr_FY ? 1 : 0; A.tr_pond_cesm = t.tr_pond_cesm ? 1 : 0; A.calc_strair = a->calc_strair ? 1 : 0;
+    A.natmiter = a->natmiter;
+    A.dt = v.dt; A.yday = v.yday; A.puny = v.k.puny; A.rhoi = c->p.rhoi; A.rhos = c->p.rhos; A.rhow = c->p.rhow; A.chio = a->chio;
+    A.ustar_min = a->ustar_min; A.hi_min = a->hi_min; A.pndaspect = a->pndaspect; A.rfracmin = a->rfracmin; A.rfracmax = a->rfracmax;
+    const dim3 b(64), g = block_grid(c);
+    if (v.ncat == 5)
+        hipLaunchKernelGGL(k_therm1_open<5>, g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    else
+        hipLaunchKernelGGL(k_therm1_open<0>, g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    HIPCHK(c, hipGetLastError());
+    // thermo_vertical on the staged arrays: its own staging finds device pointers and copies nothing
+    const int rc = evpk_thermo_vertical(c, &x, stop);
+    if (rc == 1) return 1;
+    const std::string keep = c->err;
+    if (rc == 0) {                            // (no merge after a stop)
+        if (v.ncat == 5)
+            hipLaunchKernelGGL(k_therm1_merge<5>, g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+        else
+            hipLaunchKernelGGL(k_therm1_merge<0>, g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (stage_out(c, arr)) return 1;
+    if (rc) c->err = keep;
+    return rc;
 }
 
 extern "C" int evpk_calibrate(evpk_ctx *c, int32_t nrep) {

@@ -98,7 +98,7 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_eap_init", "evpk_eap_upload", "evpk_eap_download", "evpk_halo_update", "evpk_halo_update_stress",
            "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
            "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics", "evpk_linear_itd",
-           "evpk_new_ice_lateral_melt", "evpk_step_therm2", "evpk_thermo_vertical"]
+           "evpk_new_ice_lateral_melt", "evpk_step_therm2", "evpk_thermo_vertical", "evpk_step_therm1"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -188,6 +188,24 @@ class ThermoArgs(ct.Structure):
                 [(n, c_f64p) for n in THERMO_STATE + THERMO_FORCING + THERMO_INOUT + THERMO_OUT])
 
 
+THERM1_IN2D = ["aice", "frzmlt", "sst", "Tf", "strocnxT", "strocnyT", "uatm", "vatm", "wind", "zlvl", "frain"]
+THERM1_MASKS = ["lmask_n", "lmask_s"]
+THERM1_OUT = ["rside", "aice_init", "aicen_init", "vicen_init"]
+THERM1_MERGED = ["strairxT", "strairyT", "Cdn_atm_ratio", "fsurf", "fcondtop", "fsens", "flat", "fswabs", "flwout", "evap", "Tref", "Qref", "Uref",
+                 "fresh", "fsalt", "fhocn", "fswthru", "meltt", "meltb", "melts", "congel", "snoice"]
+THERM1_DIAG = ["strairxn", "strairyn", "Cdn_atm_ratio_n", "Trefn", "Qrefn", "Urefn"]
+THERM1_SCALARS = ["chio", "ustar_min", "hi_min", "pndaspect", "rfracmin", "rfracmax"]
+THERM1_FLAGS = ["natmiter", "calc_strair", "tr_iage", "tr_FY", "nt_iage", "nt_FY", "formdrag", "highfreq", "atmbndy_constant", "fbot_xfer_Cdn_ocn",
+                "tr_aero"]
+
+
+class Therm1Args(ct.Structure):
+    """evpk_therm1_args (include/evpk.h), member for member"""
+    _fields_ = ([("tv", ThermoArgs)] + [(n, c_f64p) for n in THERM1_IN2D] + [("fswthrun", c_f64p)] + [(n, c_i32p) for n in THERM1_MASKS] +
+                [("Cdn_atm", c_f64p)] + [(n, c_f64p) for n in THERM1_OUT + THERM1_MERGED + THERM1_DIAG] +
+                [(n, ct.c_double) for n in THERM1_SCALARS] + [(n, ct.c_int32) for n in THERM1_FLAGS])
+
+
 def remap_tracer_tables(trcr_depend):
     """tracer_type, depend, has_dependents of transport_remap as init_transport builds them from trcr_depend
     (ice_transport_driver.F90:90-118): hice and hsno first (type 1, no parent); a tracer of the area is type 1, one that hangs on a
@@ -272,6 +290,7 @@ def lib():
         L.evpk_new_ice_lateral_melt.argtypes = [ctxp, ct.POINTER(Therm2Args)]
         L.evpk_step_therm2.argtypes = [ctxp, ct.POINTER(Therm2Args), c_i32p]
         L.evpk_thermo_vertical.argtypes = [ctxp, ct.POINTER(ThermoArgs), c_i32p]
+        L.evpk_step_therm1.argtypes = [ctxp, ct.POINTER(Therm1Args), c_i32p]
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -760,6 +779,51 @@ class Context:
         if rc in (LITD_STOP, ITD_STOP):
             return (int(rc),) + tuple(int(v) for v in stop)
         self._chk(rc, "evpk_step_therm2")
+        return None
+
+    def step_therm1(self, dt: float, state, forcing, inout, out, merged, ntrcr: int, tracers, yday=0.0, conduct=0, min_salin=0.1, constants=None,
+                    ktherm=1, calc_Tsfc=True, heat_capacity=True, l_brine=True, chio=0.006, ustar_min=0.0005, natmiter=5, calc_strair=True,
+                    hi_min=0.01, pndaspect=0.8, rfracmin=0.15, rfracmax=1.0, formdrag=False, highfreq=False, atmbndy="default",
+                    fbot_xfer_type="constant", tr_aero=False):
+        """evpk_step_therm1: step_therm1 in one call -- frzmlt_bottom_lateral, atmo_boundary_layer, increment_age, update_FYarea,
+        thermo_vertical (BL99), compute_ponds_cesm, merge_fluxes -- on arrays staged once.  state, inout as for thermo_vertical; forcing:
+        dict of THERMO_FORCING (fbot, Tbot, shcoef, lhcoef may be absent: given, they receive what the call computed) plus THERM1_IN2D
+        (nb, ny, nx; frain only with tr_pond_cesm), fswthrun (nb, ncat, ny, nx), lmask_n / lmask_s (int32 (nb, ny, nx), only with tr_FY);
+        out: dict of THERMO_OUT plus THERM1_OUT (rside, aice_init (nb, ny, nx); aicen_init, vicen_init (nb, ncat, ny, nx)) and, where
+        wanted, THERM1_DIAG (nb, ncat, ny, nx); merged: dict of Cdn_atm and THERM1_MERGED (nb, ny, nx), in / out.  tracers: dict of
+        ITD_TRACER_FIELDS plus nt_sice, tr_iage, tr_FY, nt_iage, nt_FY.
+        Returns None, or (reason, block, category, i, j) as thermo_vertical; raises on a refusal, which leaves every array untouched."""
+        from . import constants as C
+        a = Therm1Args()
+        v = a.tv
+        v.dt, v.yday, v.min_salin = float(dt), float(yday), float(min_salin)
+        v.ktherm, v.calc_Tsfc, v.heat_capacity, v.l_brine = int(ktherm), int(bool(calc_Tsfc)), int(bool(heat_capacity)), int(bool(l_brine))
+        v.conduct = int({"MU71": 0, "bubbly": 1}.get(conduct, conduct))
+        aicen, trcrn = state.get("aicen"), state.get("trcrn")
+        v.ncat = int(aicen.shape[1]) if aicen is not None else 0
+        v.ntrcr, v.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
+        v.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        v.nt_sice = int(tracers.get("nt_sice", 0))
+        v.k = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
+        for names, src in ((THERMO_STATE, state), (THERMO_FORCING, forcing), (THERMO_INOUT, inout), (THERMO_OUT, out)):
+            for n in names:
+                setattr(v, n, _p64(src.get(n)))
+        for names, src in ((THERM1_IN2D + ["fswthrun"], forcing), (THERM1_OUT + THERM1_DIAG, out), (["Cdn_atm"] + THERM1_MERGED, merged)):
+            for n in names:
+                setattr(a, n, _p64(src.get(n)))
+        for n in THERM1_MASKS:
+            setattr(a, n, _p32(forcing.get(n)))
+        a.chio, a.ustar_min, a.hi_min, a.pndaspect = float(chio), float(ustar_min), float(hi_min), float(pndaspect)
+        a.rfracmin, a.rfracmax = float(rfracmin), float(rfracmax)
+        a.natmiter, a.calc_strair = int(natmiter), int(bool(calc_strair))
+        a.tr_iage, a.tr_FY, a.nt_iage, a.nt_FY = (int(tracers.get(k, 0)) for k in ("tr_iage", "tr_FY", "nt_iage", "nt_FY"))
+        a.formdrag, a.highfreq, a.tr_aero = int(bool(formdrag)), int(bool(highfreq)), int(bool(tr_aero))
+        a.atmbndy_constant, a.fbot_xfer_Cdn_ocn = int(atmbndy == "constant"), int(fbot_xfer_type == "Cdn_ocn")
+        stop = np.zeros(5, dtype=np.int32)
+        rc = self._L.evpk_step_therm1(self._ctx, ct.byref(a), _p32(stop))
+        if rc == THERMO_STOP:
+            return tuple(int(v) for v in stop)
+        self._chk(rc, "evpk_step_therm1")
         return None
 
     def thermo_vertical(self, dt: float, state, forcing, inout, out, ntrcr: int, tracers, yday=0.0, conduct=0, min_salin=0.1, constants=None,

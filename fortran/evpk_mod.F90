@@ -185,6 +185,29 @@
          type (c_ptr) :: dsnown = c_null_ptr
       end type evpk_thermo_args
 
+      ! evpk_therm1_args (include/evpk.h): the arguments of evpk_step_therm1, member for member.  tv: shcoef, lhcoef, fbot, Tbot may stay
+      ! c_null_ptr (given, they receive what the call computed); lmask_n / lmask_s: integer (c_int32_t) block arrays, as evpk_geom's tmask
+      type, bind(C) :: evpk_therm1_args
+         type (evpk_thermo_args) :: tv
+         type (c_ptr) :: aice = c_null_ptr, frzmlt = c_null_ptr, sst = c_null_ptr, Tf = c_null_ptr, strocnxT = c_null_ptr
+         type (c_ptr) :: strocnyT = c_null_ptr, uatm = c_null_ptr, vatm = c_null_ptr, wind = c_null_ptr, zlvl = c_null_ptr, frain = c_null_ptr
+         type (c_ptr) :: fswthrun = c_null_ptr
+         type (c_ptr) :: lmask_n = c_null_ptr, lmask_s = c_null_ptr
+         type (c_ptr) :: Cdn_atm = c_null_ptr
+         type (c_ptr) :: rside = c_null_ptr, aice_init = c_null_ptr, aicen_init = c_null_ptr, vicen_init = c_null_ptr
+         type (c_ptr) :: strairxT = c_null_ptr, strairyT = c_null_ptr, Cdn_atm_ratio = c_null_ptr, fsurf = c_null_ptr, fcondtop = c_null_ptr
+         type (c_ptr) :: fsens = c_null_ptr, flat = c_null_ptr, fswabs = c_null_ptr, flwout = c_null_ptr, evap = c_null_ptr, Tref = c_null_ptr
+         type (c_ptr) :: Qref = c_null_ptr, Uref = c_null_ptr
+         type (c_ptr) :: fresh = c_null_ptr, fsalt = c_null_ptr, fhocn = c_null_ptr, fswthru = c_null_ptr, meltt = c_null_ptr, meltb = c_null_ptr
+         type (c_ptr) :: melts = c_null_ptr, congel = c_null_ptr, snoice = c_null_ptr
+         type (c_ptr) :: strairxn = c_null_ptr, strairyn = c_null_ptr, Cdn_atm_ratio_n = c_null_ptr, Trefn = c_null_ptr, Qrefn = c_null_ptr
+         type (c_ptr) :: Urefn = c_null_ptr
+         real (c_double) :: chio = 0.006_c_double, ustar_min = 0.0005_c_double, hi_min = 0.01_c_double, pndaspect = 0.8_c_double
+         real (c_double) :: rfracmin = 0.15_c_double, rfracmax = 1.0_c_double
+         integer (c_int32_t) :: natmiter = 5, calc_strair = 1, tr_iage = 0, tr_FY = 0, nt_iage = 0, nt_FY = 0
+         integer (c_int32_t) :: formdrag = 0, highfreq = 0, atmbndy_constant = 0, fbot_xfer_Cdn_ocn = 0, tr_aero = 0
+      end type evpk_therm1_args
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -198,7 +221,8 @@
                 evpk_itd_tracers, evpk_itd_constants, evpk_cleanup_itd, evpk_aggregate, EVPK_ITD_STOP, &
                 evpk_dyn_args, evpk_bound_state, evpk_step_dynamics, evpk_linear_itd, EVPK_LITD_STOP, &
                 evpk_therm2_args, evpk_new_ice_lateral_melt, evpk_step_therm2, &
-                evpk_thermo_args, evpk_thermo_vertical, EVPK_THERMO_STOP
+                evpk_thermo_args, evpk_thermo_vertical, EVPK_THERMO_STOP, &
+                evpk_therm1_args, evpk_step_therm1
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
@@ -422,6 +446,15 @@
             import :: c_int, c_ptr, c_int32_t, evpk_thermo_args
             type (c_ptr), value :: ctx
             type (evpk_thermo_args), intent(in) :: a
+            integer (c_int32_t), intent(out) :: stop(5)
+         end function
+
+         ! step_therm1 (ice_step_mod.F90:154-733) in one call: frzmlt_bottom_lateral, atmo_boundary_layer, increment_age, update_FYarea,
+         ! thermo_vertical, compute_ponds_cesm, merge_fluxes; stop(5) as evpk_thermo_vertical (EVPK_THERMO_STOP)
+         integer (c_int) function evpk_step_therm1 (ctx, a, stop) bind(C, name='evpk_step_therm1')
+            import :: c_int, c_ptr, c_int32_t, evpk_therm1_args
+            type (c_ptr), value :: ctx
+            type (evpk_therm1_args), intent(in) :: a
             integer (c_int32_t), intent(out) :: stop(5)
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then

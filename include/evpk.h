@@ -643,7 +643,7 @@ int evpk_step_therm2(evpk_ctx *c, const evpk_therm2_args *a, int32_t stop[5] /* 
  * tr_pond_topo without fpond, nt_apnd, nt_hpnd; a context of several ranks (nranks > 1) on which evpk_connect has not run.
  * x-slab ranks: not collective -- each rank runs its own blocks, and a rank without a block column returns 0.
  * Out of scope: frzmlt_bottom_lateral (its deltaT**m2 is a real power: it needs a fixed-algorithm pow first); atmo_boundary_layer,
- * increment_age, update_FYarea, the pond routines, merge_fluxes (with these step_therm1 becomes one call); ktherm = 2, zero-layer
+ * increment_age, update_FYarea, the pond routines, merge_fluxes (with these step_therm1 becomes one call: evpk_step_therm1, row f-11 below); ktherm = 2, zero-layer
  * thermodynamics, calc_Tsfc = .false., fresh ice (l_brine = .false.); aerosols. */
 #define EVPK_HAS_THERMO_VERTICAL 1
 #define EVPK_THERMO_STOP 16
@@ -663,6 +663,79 @@ typedef struct {
     double *melttn, *meltsn, *meltbn, *congeln, *snoicen, *dsnown;
 } evpk_thermo_args;
 int evpk_thermo_vertical(evpk_ctx *c, const evpk_thermo_args *a, int32_t stop[5] /* out: reason, block, category, i, j */);
+
+/* step_therm1 (source/ice_step_mod.F90:154-733) in ONE call, three launches on state staged once: k_therm1_open,
+ * k_thermo_vertical (row f-10, unchanged), k_therm1_merge (csrc/evpk_therm1s.hip).  With it a host whose thickness distribution lives in
+ * device memory calls evpk_step_therm1, evpk_step_therm2 and evpk_step_dynamics and moves only 2-D forcing and 2-D fluxes.
+ *   k_therm1_open   aice_init, aicen_init, vicen_init (:272-285: copies on every cell of the block arrays, ghost cells included);
+ *                   frzmlt_bottom_lateral (source/ice_therm_vertical.F90:611-834), AusCOM branch cpchr = -cp_ocn rhow chio: rside = 0,
+ *                   Tbot = Tf, fbot = 0 on every cell, then on physical cells with aice > puny and frzmlt < 0 deltaT, ustar with ustar_min,
+ *                   fbot clamped by frzmlt, wlat = m1 deltaT**m2 (the real power: evpk_pow_pos), rside clamped to [0, 1], etot and fside
+ *                   over the categories in order (snow layers before ice layers), the xtmp limiting;
+ *                   per category on the cell list of :378-389 AND tmask (the stated departure of evpk_thermo_vertical, kept so that
+ *                   all kernels list the same cells): atmo_boundary_layer (source/ice_atmo.F90:82-483; sfctype 'ice', highfreq and
+ *                   formdrag .false.) -- vmag = max(1, wind), rdn = vonkar / log(zref / iceruf) computed as written, Cdn_atm = rdn rdn,
+ *                   natmiter iterations of hol with its sign / min(abs, 10) clamp, stable, xqq, psimhs, psimhu, psixhu, rd, rh, re; with
+ *                   calc_strair strairxn, strairyn, Cdn_atm_ratio_n, without it (AusCOM, :458-464) strairxn = strairyn = 0; shcoef,
+ *                   lhcoef, Trefn, Qrefn, Urefn; then increment_age (tr_iage) and update_FYarea (tr_FY; yday, dt / secday, lmask_n,
+ *                   lmask_s).  atmo_boundary_layer of category n reads only Tsfc(n) of entry and frzmlt_bottom_lateral only the state
+ *                   of entry: running all of this before the first thermo_vertical is the reference's result, not a reordering.
+ *   k_therm1_merge  per category in order: fswabsn = fswsfcn + fswintn + fswthrun (:565-571; fswsfcn and fswintn as k_thermo_vertical
+ *                   left them); compute_ponds_cesm under tr_pond_cesm (source/ice_meltpond_cesm.F90:61-197) on its own list -- aicen >
+ *                   puny on the state AFTER the vertical thermodynamics, with tmask -- rfrac from rfracmin, rfracmax; merge_fluxes
+ *                   (source/ice_flux.F90:681-831): all 22 accumulations, weighted with aicen_init, over the list of entry; flwout with
+ *                   its (1 - emissivity) flw term.  One thread per cell, categories in order: the sums carry the reference's bits.
+ * The eight per-category results of atmo_boundary_layer (shcoef, lhcoef, strairxn, strairyn, Cdn_atm_ratio_n, Trefn, Qrefn, Urefn) are
+ * locals of step_therm1.  Here they are per-category planes the library owns (one pool, grown once), or the caller's where given; they
+ * are ZERO wherever the cell is not listed.  The Fortran's block-wide `icells > 0` test (:391) only decides whether locals that nobody
+ * reads hold zeros or the previous category's values.  Cdn_atm_ratio_n without calc_strair is left unset by the reference; here it is 0.
+ * Operation order: the Fortran's; min / max are a comparison and a select; sign(a, b) is copysign-exact, b = -0 included; x**2 is x*x; exp
+ * is dev_exp; log, atan and the real power are the fixed algorithms of csrc/evpk_fmath2.h (within 1 ulp of glibc on the CPU, held to 2);
+ * sqrt is the IEEE one.
+ * Constants: rhow, rhoi, rhos from evpk_params; puny from tv.k.  Compiled in (drivers/cice/ice_constants.F90 unless another file is named):
+ * vonkar = 0.4 (:47), zref = 10 (:76), iceruf = 0.0005 (:64), zvir = 0.606 (:46), cp_air = 1005 (:25), cp_wv = 1810 (:48), gravit = 9.80616
+ * (:36), Lsub = 2.835e6 (:51), pi (:153), secday = 86400 (:41), rhofresh = 1000 (:45), Timelt = 0 (:54), cp_ocn, Tffresh, qqqice, TTTice and
+ * emissivity as row f-10; m1 = 1.6e-6, m2 = 1.36, floediam = 300, floeshape = 0.66 (source/ice_therm_vertical.F90:682-687); zTrf = 2
+ * (source/ice_atmo.F90:196); Td = 2, rexp = 0.01, dpthhi = 0.9 (source/ice_meltpond_cesm.F90:116-119).
+ * The frain / fsnow scaling of :294-314 is behind ACCESS, which this project's build of the reference does not define: it is left out.
+ * **Parity unpinned**: no recipe under oracle/ builds these routines; the call is held bit for bit to a numpy restatement written from
+ * the Fortran (tests/nptherm1s.py, which calls tests/nptherm1.py for thermo_vertical).
+ * Members: tv -- evpk_thermo_args, whose shcoef, lhcoef, fbot, Tbot may be NULL; where given they RECEIVE what k_therm1_open computed
+ *   (they are outputs here, despite the const of the member);
+ *   aice, frzmlt, sst, Tf, strocnxT, strocnyT, uatm, vatm, wind, zlvl, frain   in, 2-D (frain only with tr_pond_cesm; else may be NULL)
+ *   fswthrun                                                  in, per category
+ *   lmask_n, lmask_s                                          in, int32 block arrays as evpk_geom's tmask (only with tr_FY; else may be NULL)
+ *   Cdn_atm                                                   in / out, 2-D: written on listed cells
+ *   rside, aice_init (2-D), aicen_init, vicen_init (per category)     out, every cell
+ *   strairxT .. snoice: merge_fluxes' 22 cumulative planes    in / out, 2-D, physical ocean cells
+ *   strairxn, strairyn, Cdn_atm_ratio_n, Trefn, Qrefn, Urefn  out if not NULL, per category, every cell
+ *   chio, ustar_min, hi_min, pndaspect, rfracmin, rfracmax; natmiter (the reference's default: 5), calc_strair, tr_iage, tr_FY, nt_iage,
+ *   nt_FY; tr_pond_cesm is tv.t.tr_pond_cesm; the flags of what is refused: formdrag, highfreq, atmbndy_constant, fbot_xfer_Cdn_ocn, tr_aero
+ * Returns 0; or EVPK_THERMO_STOP with the stop[] of evpk_thermo_vertical unchanged -- only k_thermo_vertical can stop; k_therm1_merge is
+ * not launched after a stop, and the arrays are undefined.
+ * Or 1 with evpk_last_error, before any copy, touching nothing: everything evpk_thermo_vertical refuses; formdrag; highfreq; atmbndy =
+ * 'constant'; fbot_xfer_type = 'Cdn_ocn'; tr_pond_lvl; tr_pond_topo (its compute_ponds_topo is a row of its own); aerosols; natmiter < 1;
+ * a tracer flag without its index (tr_iage / nt_iage, tr_FY / nt_FY, tr_pond_cesm / nt_apnd, nt_hpnd); a missing pointer.
+ * x-slab ranks: not collective -- a rank without a block column returns 0.
+ * Out of scope: neutral_drag_coeffs (formdrag), highfreq coupling, atmo_boundary_const, compute_ponds_lvl, compute_ponds_topo and the
+ * topo collection lines of :644-669, update_aerosol, set_sfcflux (calc_Tsfc = .false.), prep_radiation and the shortwave routines,
+ * ktherm = 2. */
+#define EVPK_HAS_STEP_THERM1 1
+typedef struct {
+    evpk_thermo_args tv;
+    const double *aice, *frzmlt, *sst, *Tf, *strocnxT, *strocnyT, *uatm, *vatm, *wind, *zlvl, *frain;       /* in */
+    const double *fswthrun;                                                   /* in, per category */
+    const int32_t *lmask_n, *lmask_s;                                         /* in */
+    double *Cdn_atm;                                                          /* in / out */
+    double *rside, *aice_init, *aicen_init, *vicen_init;                      /* out */
+    double *strairxT, *strairyT, *Cdn_atm_ratio, *fsurf, *fcondtop, *fsens, *flat, *fswabs, *flwout, *evap, *Tref, *Qref, *Uref;      /* in / out */
+    double *fresh, *fsalt, *fhocn, *fswthru, *meltt, *meltb, *melts, *congel, *snoice;
+    double *strairxn, *strairyn, *Cdn_atm_ratio_n, *Trefn, *Qrefn, *Urefn;    /* out if not NULL, per category */
+    double chio, ustar_min, hi_min, pndaspect, rfracmin, rfracmax;
+    int32_t natmiter, calc_strair, tr_iage, tr_FY, nt_iage, nt_FY;
+    int32_t formdrag, highfreq, atmbndy_constant, fbot_xfer_Cdn_ocn, tr_aero;
+} evpk_therm1_args;
+int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t stop[5] /* out: reason, block, category, i, j */);
 
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Constants of cice5_amd/csrc/evpk_fmath.h, derived with exact rational arithmetic (no libm): the three-part split of pi/2
-for the argument reduction of sin / cos, pi and pi/2 as hi + lo pairs, atan(k/16) as hi + lo pairs, Taylor coefficients.
+for the argument reduction of sin / cos, pi and pi/2 as hi + lo pairs, atan(k/16) as hi + lo pairs, Taylor coefficients; and of
+cice5_amd/csrc/evpk_fmath2.h (main2): ln 2 = 2 atanh(1/3) as a 32-bit head and its remainder, the coefficients 2 / (2k + 3) of 2 atanh.
 
     python scripts/gen_fmath.py          # prints the C initialisers
 """
@@ -99,6 +100,26 @@ def main():
     # sanity against libm (not used for the constants)
     assert abs(his[16] - math.atan(1.0)) < 1e-16 and abs(his[8] - math.atan(0.5)) < 1e-16
     assert abs(float(p1) + float(p2) + p3 - math.pi / 2) < 1e-16
+    main2()
+
+
+def ln2_rat(terms=200):
+    """ln 2 = 2 atanh(1/3) = 2 sum (1/3)^(2k+1) / (2k+1): the tail after `terms` terms is below 9^-terms"""
+    return 2 * sum(F(1, 3) ** (2 * k + 1) / (2 * k + 1) for k in range(terms))
+
+
+def main2():
+    """the constants of cice5_amd/csrc/evpk_fmath2.h: ln 2 as a 32-bit head and its remainder, 2 / (2k + 3) for the atanh series"""
+    ln2 = ln2_rat()
+    hi = trunc_bits(ln2, 32)
+    lo = to_double(ln2 - hi)
+    assert F(float(hi)) == hi
+    print("/* evpk_fmath2.h: ln 2 = HI (32 bits: k * HI exact for |k| < 2^21) + LO */")
+    print(f"#define EVPK_LN2_HI {float(hi)!r}\n#define EVPK_LN2_LO {lo!r}")
+    LG = [to_double(F(2, 2 * k + 3)) for k in range(10)]              # s^3 .. s^21
+    print("/* 2 atanh(s) = 2 s + s^3 (LG[0] + s^2 (LG[1] + ...)) */")
+    print("static const double evpk_LG[10] = {" + ", ".join(repr(x) for x in LG) + "};")
+    assert abs(float(hi) + lo - math.log(2.0)) < 1e-16
 
 
 if __name__ == "__main__":
