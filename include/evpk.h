@@ -437,8 +437,11 @@ int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t 
  * zeroes their tracers in a block that calls shift_ice); on a stop the arrays are undefined (the reference aborts).  A boundary that
  * is left with donor = 0 but daice > 0 -- only a negative vicen under aicen > puny can do that, through the second "entire category"
  * rule -- moves nothing (the reference indexes category 0 there).
- * Parity: held bit for bit to a numpy restatement written from the Fortran (tests/nplitd.py), whose shift_ice / compute_tracers are
- * pinned to reference-built output; fit_line and the boundary integrals are not pinned to reference-built output yet.
+ * Parity: PINNED to reference-built output.  The call equals, bit for bit on the physical ocean cells, the records of the reference's
+ * own compiled linear_itd -- fit_line and the boundary integrals included (tests/golden/ref_litd_*.npz, oracle/ref/therm2.mk;
+ * tests/test_therm2_ref_gpu.py), and so does the numpy restatement written from the Fortran (tests/nplitd.py, tests/test_therm2_ref.py).
+ * The reference leaves hin_max(ncat) = 999.9 in its module for whatever runs after it (ice_therm_itd.F90:208; recorded with every
+ * fixture); this call takes that value inside and leaves the caller's hin_max alone -- no routine after it reads hin_max(ncat).
  * Returns 0; EVPK_LITD_STOP with stop[] = {reason, block (local, 1-based), i, j}: reasons 2 .. 5 are EVPK_ITD_STOP's shift_ice reasons
  * (2 negative daice, 3 negative dvice, 4 daice > aicen, 5 dvice > vicen) -- the lowest block, in it the lowest boundary, in it the first
  * failing check, and the LAST failing listed cell in (j, i) order, as the non-exiting error loops report.  The reference's report loops
@@ -549,8 +552,14 @@ int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t stop[5] /* o
  * cell's own profile; the two agree whenever salinz is horizontally uniform, which is how init_thermo_vertical fills it
  * (ice_therm_vertical.F90:575-591) -- salinz must be horizontally uniform for parity.  (c) add_new_ice_bgc, aerosols and bgc tracers
  * are refused.
- * Parity: held bit for bit to a numpy restatement written from the Fortran (tests/nptherm2.py); add_new_ice, lateral_melt and the mushy
- * liquidus are NOT pinned to reference-built output yet.
+ * Parity: PINNED to reference-built output.  add_new_ice, lateral_melt, reduce_area and the mushy liquidus equal, bit for bit on the
+ * physical ocean cells, the records of the reference's own compiled routines (tests/golden/ref_therm2_*.npz, oracle/ref/therm2.mk),
+ * each on its own and chained, and evpk_step_therm2 equals the record after cleanup_itd (tests/test_therm2_ref_gpu.py); the numpy
+ * restatement written from the Fortran (tests/nptherm2.py) equals the records stage by stage (tests/test_therm2_ref.py).  The liquidus
+ * parameters derived in the module's expression order are the values the Fortran compiler folds: no difference was found.  The
+ * reference's AusCOM build fixes cp_ocn = 3989.24495292815 (drivers/auscom/ice_constants.F90:30); the records are made with it, and a
+ * caller that wants that build's numbers passes it.  Unpinned stay: step_therm2's call order (the driver restates it), a horizontally
+ * non-uniform salinz (departure (b)), aerosols / bgc (refused), l_conservation_check = .true. (compile-time .false. in the reference).
  *
  * evpk_step_therm2: the frain line (ice_step_mod.F90:804-809: fresh += frain * aice on every cell, ghost cells included, on the aice of
  * entry), aggregate_area on every cell, evpk_linear_itd when kitd == 1, evpk_new_ice_lateral_melt, evpk_cleanup_itd(dt) -- bit for bit

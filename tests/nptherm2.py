@@ -4,9 +4,11 @@
 independent of the HIP code: block by block, one cell list per block, the Fortran's loop order (the category loop outside the cell loop,
 the layer loop where the Fortran has it) and its operation order per cell.  linear_itd is tests/nplitd.py's, cleanup_itd tests/npitd.py's.
 
-PARITY IS UNPINNED for add_new_ice, lateral_melt and the mushy liquidus: there is no reference-built record of them (the recipes under
-oracle/ build ridge_ice, cleanup_itd and the dynamics only), so this file is held to the Fortran by reading, not by a fixture.  What it
-ends in -- cleanup_itd with shift_ice and compute_tracers -- is pinned (tests/test_itd_ref.py).
+PINNED to reference-built output: add_new_ice, update_vertical_tracers, the mushy liquidus, lateral_melt, reduce_area and the chain of
+step_therm2 equal the records of the reference's own compiled routines bit for bit, stage by stage (tests/golden/ref_therm2_*.npz, made
+by tests/golden/make_ref_therm2.py from oracle/ref/therm2.mk; tests/test_therm2_ref.py).  What stays unpinned: step_therm2's call order
+(the driver oracle/ref/ref_therm2.F90 restates it), a horizontally non-uniform salinz (the departure below), aerosols / bgc, and
+l_conservation_check = .true.
 
 l_conservation_check = .false. (ice_therm_itd.F90:37): those blocks are left out; tests/test_therm2_host.py makes the same check from
 outside.  tr_aero, tr_brine, skl_bgc, nbtrcr: not restated (evpk_step_therm2 refuses them).  Stated departures, shared with the device
@@ -335,10 +337,11 @@ def reduce_area_block(J, I, hin0, a, v, ai, vi, info):
             info["reduce_none"] += int(not did)
 
 
-def new_ice_lateral_melt(blocks, tmask, p, y, debug=None):
+def new_ice_lateral_melt(blocks, tmask, p, y, debug=None, after_new_ice=None):
     """ice_step_mod.F90:875-960 for every block in turn, on the arrays of the dict y (in place): aicen_init, vicen_init, aicen, vicen, vsnon,
     trcrn, aice, aice0, frzmlt, Tf, sss, rside, salinz, frazil, frz_onset (or None), meltl, fpond (or None), fresh, fsalt, fhocn.
-    Returns one info record of counts per block (INFO_KEYS).  debug: a list that receives add_new_ice's locals per block."""
+    Returns one info record of counts per block (INFO_KEYS).  debug: a list that receives add_new_ice's locals per block.
+    after_new_ice: called with the block number once add_new_ice has run on it and before lateral_melt does."""
     nb, ncat, ny, nx = y["aicen"].shape
     trcrn = y["trcrn"] if y.get("trcrn") is not None else np.zeros((nb, ncat, 0, ny, nx))
     infos = []
@@ -354,6 +357,8 @@ def new_ice_lateral_melt(blocks, tmask, p, y, debug=None):
                                 y["fresh"][b], y["fsalt"][b], y["Tf"][b], y["sss"][b], y["salinz"][b], info)
         if debug is not None:
             debug.append(dict(loc, J=J, I=I))
+        if after_new_ice is not None:
+            after_new_ice(b)
         ml = [(j, i) for j, i in lst if y["rside"][b, j, i] > C0]                       # (departure: tmask cells)
         for j, i in lst:
             r = y["rside"][b, j, i]
@@ -369,11 +374,22 @@ def new_ice_lateral_melt(blocks, tmask, p, y, debug=None):
     return infos
 
 
-def step_therm2(blocks, tmask, p, y, kitd, hi_min, first_ice=None):
+SNAP = ["aicen", "vicen", "vsnon", "trcrn", "aice", "aice0", "frazil", "frz_onset", "meltl", "fpond", "fresh", "fsalt", "fhocn"]
+
+
+def step_therm2(blocks, tmask, p, y, kitd, hi_min, first_ice=None, stages=None):
     """step_therm2 for every block: the frain line on every cell, aggregate_area, linear_itd (kitd = 1), add_new_ice, lateral_melt,
     reduce_area, cleanup_itd.  Every block runs one stage before any block runs the next, which equals the reference's block loop: no
-    stage looks beyond its block.  Returns (infos, stop): stop = (stage, reason, block, i, j) or None."""
+    stage looks beyond its block.  Returns (infos, stop): stop = (stage, reason, block, i, j) or None.
+    stages: a list that receives copies of the arrays of SNAP (and first_ice) after linear_itd, after add_new_ice, after lateral_melt /
+    reduce_area and after cleanup_itd -- what tests/test_therm2_ref.py holds to the reference's record stage by stage."""
     tr = p["tr"]
+
+    def snap():
+        one = {q: y[q].copy() for q in SNAP if y.get(q) is not None}
+        if first_ice is not None:
+            one["first_ice"] = first_ice.copy()
+        return one
     if y.get("frain") is not None:
         y["fresh"][:] = y["fresh"] + y["frain"] * y["aice"]                             # ice_step_mod.F90:804-809, ghost cells included
     for b in range(y["aicen"].shape[0]):
@@ -383,10 +399,23 @@ def step_therm2(blocks, tmask, p, y, kitd, hi_min, first_ice=None):
                                     y["aicen"], y["vicen"], y["vsnon"], y["trcrn"], y["aice"], y["aice0"], y.get("fpond"))
         if stop:
             return None, (1,) + tuple(stop)
-    infos = new_ice_lateral_melt(blocks, tmask, p, y)
+    hook = None
+    if stages is not None:
+        stages.append(snap())
+        mid = snap()                                                                    # block by block: as add_new_ice leaves it
+
+        def hook(b):
+            for q in mid:
+                mid[q][b] = first_ice[b] if q == "first_ice" else y[q][b]
+    infos = new_ice_lateral_melt(blocks, tmask, p, y, after_new_ice=hook)
+    if stages is not None:
+        stages.append(mid)
+        stages.append(snap())
     fl = {q: y[q] for q in ("fpond", "fresh", "fsalt", "fhocn") if y.get(q) is not None}
     _, stop = npitd.cleanup_itd(blocks, p["dt"], p["ntrcr"], p["dep"], tr, p["hin_max"], p["k"], y["aicen"], y["vicen"], y["vsnon"], y["trcrn"],
                                 y["aice0"], y["aice"], fl, first_ice)
+    if stages is not None:
+        stages.append(snap())
     if stop:
         return infos, (3,) + tuple(stop)
     return infos, None

@@ -1,6 +1,7 @@
 """evpk_linear_itd on the device against the numpy restatement tests/nplitd.py -- bit for bit: the routines use only + - x / , comparisons
-and selects, the library is built with -ffp-contract=off.  Parity with the reference is unpinned for fit_line and the boundary integrals
-(no reference-built record yet); shift_ice / compute_tracers of the restatement are pinned (tests/test_itd_ref.py).
+and selects, the library is built with -ffp-contract=off.  Parity with the reference is pinned: the restatement equals the reference's
+own compiled linear_itd, fit_line and the boundary integrals included (tests/test_therm2_ref.py), and tests/test_therm2_ref_gpu.py
+compares the device with those records directly; shift_ice / compute_tracers are pinned by tests/test_itd_ref.py as well.
 Inputs: tests/golden/litdvec.py (no shape larger than 26 x 18 cells); tests/test_litd_host.py shows that they take every branch.
 
 No stop case: linear_itd's own donor rules keep every transfer inside shift_ice's checks (tests/test_litd_host.py, include/evpk.h).

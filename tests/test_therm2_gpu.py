@@ -1,8 +1,9 @@
 """evpk_new_ice_lateral_melt and evpk_step_therm2 on the device against the numpy restatement tests/nptherm2.py -- bit for bit: the routines
-use only + - x / , comparisons and selects, the library is built with -ffp-contract=off.  Parity with the reference is unpinned for
-add_new_ice, lateral_melt and the mushy liquidus (no reference-built record); cleanup_itd, shift_ice and compute_tracers of the chain are
-pinned (tests/test_itd_ref.py).  Inputs: tests/golden/therm2vec.py (no shape larger than 26 x 18 cells); tests/test_therm2_host.py shows
-that they take every branch.
+use only + - x / , comparisons and selects, the library is built with -ffp-contract=off.  Parity with the reference is pinned: the
+restatement equals the reference's own compiled add_new_ice, lateral_melt, mushy liquidus and chain stage by stage
+(tests/test_therm2_ref.py), and tests/test_therm2_ref_gpu.py compares the device with those records directly; unpinned stay step_therm2's
+call order, a non-uniform salinz, aerosols / bgc and l_conservation_check = .true.  Inputs: tests/golden/therm2vec.py (no shape larger
+than 26 x 18 cells); tests/test_therm2_host.py shows that they take every branch.
 """
 import os
 import sys

@@ -2,7 +2,9 @@
 tests/nptherm2.py -- the checker of tests/test_therm2_gpu.py -- takes every branch of add_new_ice, lateral_melt and reduce_area on the
 inputs of tests/golden/therm2vec.py and conserves what the reference's own (compile-time disabled) check asks for.
 
-Parity with the reference is unpinned for add_new_ice, lateral_melt and the mushy liquidus: no reference-built record exists for them.
+Parity with the reference is pinned for add_new_ice, lateral_melt, reduce_area and the mushy liquidus: tests/test_therm2_ref.py holds the
+restatement to reference-built records stage by stage.  Unpinned stay step_therm2's call order, a non-uniform salinz, aerosols / bgc and
+l_conservation_check = .true.
 
 Reported, not asserted (a count that depends on rounding, not on a rule of the routine):
   fy_clamped    FY = 1 in category 1 makes (FY area1 + ai0new) / aicen(1) exceed 1 only when the division rounds up; the input FY = 1 is
