@@ -36,6 +36,7 @@
 #include "evpk_therm2.hip"
 #include "evpk_therm1.hip"
 #include "evpk_therm1s.hip"
+#include "evpk_rad.hip"
 #include "evpk_eap.hip"
 
 using namespace evpk;
@@ -4593,6 +4594,94 @@ extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t 
     if (stage_out(c, arr)) return 1;
     if (rc) c->err = keep;
     return rc;
+}
+
+// ---- step_radiation (source/ice_step_mod.F90:1364-1524, ccsm3) with the albedo lines of coupling_prep, and prep_radiation (:33-145):
+// one launch each (kernels in evpk_rad.hip) ----
+extern "C" int evpk_step_radiation(evpk_ctx *c, const evpk_rad_args *a) {
+    if (!c) return 1;
+    RANKS_ENTRY(c, "evpk_step_radiation");
+    const char *who = "evpk_step_radiation";
+    if (!a) FAIL(c, "%s: a required argument is missing", who);
+    const evpk_itd_tracers &t = a->t;
+    if (a->shortwave_dEdd) FAIL(c, "%s: shortwave = 'dEdd' (run_dEdd) is not supported", who);
+    if (a->calc_Tsfc != 1) FAIL(c, "%s: calc_Tsfc = .false. is not supported", who);
+    if (a->heat_capacity != 1) FAIL(c, "%s: heat_capacity = .false. (zero-layer) is not supported", who);
+    if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->swvdr || !a->swvdf || !a->swidr || !a->swidf || !a->alvdrn || !a->alidrn ||
+        !a->alvdfn || !a->alidfn || !a->albicen || !a->albsnon || !a->fswsfcn || !a->fswintn || !a->fswthrun || !a->Sswabsn || !a->Iswabsn ||
+        !a->coszen || !a->alvdr || !a->alidr || !a->alvdf || !a->alidf || !a->albice || !a->albsno || !a->scale_factor)
+        FAIL(c, "%s: a required argument is missing", who);
+    if (t.nilyr < 1 || t.nslyr < 1 || t.nilyr > T1_MAXL || t.nslyr > T1_MAXL)
+        FAIL(c, "%s: nilyr = %d, nslyr = %d not in 1..%d", who, t.nilyr, t.nslyr, T1_MAXL);
+    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, a->ncat, MAXCAT);
+    if (a->ntrcr < 1 || a->ntrcr_dim < a->ntrcr || t.nt_Tsfc < 1 || t.nt_Tsfc > a->ntrcr)
+        FAIL(c, "%s: nt_Tsfc = %d lies beyond ntrcr = %d (ntrcr_dim = %d)", who, t.nt_Tsfc, a->ntrcr, a->ntrcr_dim);
+    if (a->puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->puny);
+    if (!c->nblocks) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    RadArgs A{};
+    A.ncat = a->ncat; A.ntrcr_dim = a->ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nilyr = t.nilyr; A.nslyr = t.nslyr; A.nt_Tsfc = t.nt_Tsfc;
+    A.constant_albedos = a->albedo_constant ? 1 : 0;
+    A.puny = a->puny; A.albicev = a->albicev; A.albicei = a->albicei; A.albsnowv = a->albsnowv; A.albsnowi = a->albsnowi; A.ahmax = a->ahmax;
+    A.snowpatch = a->snowpatch; A.albocn = a->albocn; A.awtvdr = a->awtvdr; A.awtidr = a->awtidr; A.awtvdf = a->awtvdf; A.awtidf = a->awtidf;
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
+    std::vector<HostArr> arr = {            // (every output is written on every cell: none is copied up)
+        {a->aicen, n3, &A.aicen, false}, {a->vicen, n3, &A.vicen, false}, {a->vsnon, n3, &A.vsnon, false}, {a->trcrn, n3 * a->ntrcr_dim, &A.trcrn, false},
+        {a->swvdr, N, &A.swvdr, false}, {a->swvdf, N, &A.swvdf, false}, {a->swidr, N, &A.swidr, false}, {a->swidf, N, &A.swidf, false},
+        {a->ocn_albedo2D, N, &A.ocn_albedo2D, false},
+        {a->alvdrn, n3, &A.alvdrn, true, false}, {a->alidrn, n3, &A.alidrn, true, false}, {a->alvdfn, n3, &A.alvdfn, true, false},
+        {a->alidfn, n3, &A.alidfn, true, false}, {a->albicen, n3, &A.albicen, true, false}, {a->albsnon, n3, &A.albsnon, true, false},
+        {a->fswsfcn, n3, &A.fswsfcn, true, false}, {a->fswintn, n3, &A.fswintn, true, false}, {a->fswthrun, n3, &A.fswthrun, true, false},
+        {a->Sswabsn, n3 * t.nslyr, &A.Sswabsn, true, false}, {a->Iswabsn, n3 * t.nilyr, &A.Iswabsn, true, false},
+        {a->fswpenln, n3 * (t.nilyr + 1), &A.fswpenln, true, false},
+        {a->coszen, N, &A.coszen, true, false}, {a->alvdr, N, &A.alvdr, true, false}, {a->alidr, N, &A.alidr, true, false},
+        {a->alvdf, N, &A.alvdf, true, false}, {a->alidf, N, &A.alidf, true, false}, {a->albice, N, &A.albice, true, false},
+        {a->albsno, N, &A.albsno, true, false}, {a->scale_factor, N, &A.scale_factor, true, false}};
+    if (stage_in(c, arr, true)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    const dim3 b(64), g = block_grid(c);
+    if (a->ncat == 5 && t.nilyr == 4 && t.nslyr == 1)
+        hipLaunchKernelGGL((k_shortwave_ccsm3<5, 4, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    else
+        hipLaunchKernelGGL((k_shortwave_ccsm3<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    HIPCHK(c, hipGetLastError());
+    return stage_out(c, arr);
+}
+
+extern "C" int evpk_prep_radiation(evpk_ctx *c, const evpk_prep_rad_args *a) {
+    if (!c) return 1;
+    RANKS_ENTRY(c, "evpk_prep_radiation");
+    const char *who = "evpk_prep_radiation";
+    if (!a) FAIL(c, "%s: a required argument is missing", who);
+    if (!a->aice || !a->aicen || !a->swvdr || !a->swvdf || !a->swidr || !a->swidf || !a->alvdr_ai || !a->alvdf_ai || !a->alidr_ai || !a->alidf_ai ||
+        !a->scale_factor || !a->fswsfcn || !a->fswintn || !a->fswthrun || !a->Sswabsn || !a->Iswabsn || !a->fswfac)
+        FAIL(c, "%s: a required argument is missing", who);
+    if (a->nilyr < 1 || a->nslyr < 1 || a->nilyr > T1_MAXL || a->nslyr > T1_MAXL)
+        FAIL(c, "%s: nilyr = %d, nslyr = %d not in 1..%d", who, a->nilyr, a->nslyr, T1_MAXL);
+    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, a->ncat, MAXCAT);
+    if (a->puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->puny);
+    if (!c->nblocks) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    PrepRadArgs A{};
+    A.ncat = a->ncat; A.nxb = c->nxb; A.nyb = c->nyb; A.nilyr = a->nilyr; A.nslyr = a->nslyr; A.puny = a->puny;
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
+    std::vector<HostArr> arr = {            // (fswfac is copied up too: its ghost cells keep the caller's values)
+        {a->aice, N, &A.aice, false}, {a->aicen, n3, &A.aicen, false}, {a->swvdr, N, &A.swvdr, false}, {a->swvdf, N, &A.swvdf, false},
+        {a->swidr, N, &A.swidr, false}, {a->swidf, N, &A.swidf, false}, {a->alvdr_ai, N, &A.alvdr_ai, false}, {a->alvdf_ai, N, &A.alvdf_ai, false},
+        {a->alidr_ai, N, &A.alidr_ai, false}, {a->alidf_ai, N, &A.alidf_ai, false},
+        {a->scale_factor, N, &A.scale_factor, true}, {a->fswfac, N, &A.fswfac, true},
+        {a->fswsfcn, n3, &A.fswsfcn, true}, {a->fswintn, n3, &A.fswintn, true}, {a->fswthrun, n3, &A.fswthrun, true},
+        {a->fswpenln, n3 * (a->nilyr + 1), &A.fswpenln, true}, {a->Sswabsn, n3 * a->nslyr, &A.Sswabsn, true},
+        {a->Iswabsn, n3 * a->nilyr, &A.Iswabsn, true}};
+    if (stage_in(c, arr, true)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    const dim3 b(64), g = block_grid(c);
+    if (a->ncat == 5 && a->nilyr == 4 && a->nslyr == 1)
+        hipLaunchKernelGGL((k_prep_radiation<5, 4, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    else
+        hipLaunchKernelGGL((k_prep_radiation<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    HIPCHK(c, hipGetLastError());
+    return stage_out(c, arr);
 }
 
 extern "C" int evpk_calibrate(evpk_ctx *c, int32_t nrep) {

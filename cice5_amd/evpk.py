@@ -98,7 +98,8 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_eap_init", "evpk_eap_upload", "evpk_eap_download", "evpk_halo_update", "evpk_halo_update_stress",
            "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
            "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics", "evpk_linear_itd",
-           "evpk_new_ice_lateral_melt", "evpk_step_therm2", "evpk_thermo_vertical", "evpk_step_therm1"]
+           "evpk_new_ice_lateral_melt", "evpk_step_therm2", "evpk_thermo_vertical", "evpk_step_therm1", "evpk_step_radiation",
+           "evpk_prep_radiation"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -206,6 +207,33 @@ class Therm1Args(ct.Structure):
                 [(n, ct.c_double) for n in THERM1_SCALARS] + [(n, ct.c_int32) for n in THERM1_FLAGS])
 
 
+RAD_FLAGS = ["shortwave_dEdd", "calc_Tsfc", "heat_capacity", "albedo_constant"]
+RAD_SCALARS = ["albicev", "albicei", "albsnowv", "albsnowi", "ahmax", "snowpatch", "albocn", "awtvdr", "awtidr", "awtvdf", "awtidf"]
+RAD_STATE = ["aicen", "vicen", "vsnon", "trcrn"]
+RAD_FORCING = ["swvdr", "swvdf", "swidr", "swidf", "ocn_albedo2D"]
+RAD_OUT = ["alvdrn", "alidrn", "alvdfn", "alidfn", "albicen", "albsnon", "fswsfcn", "fswintn", "fswthrun"]       # (nb, ncat, ny, nx)
+RAD_OUT_LAYERS = ["Sswabsn", "Iswabsn", "fswpenln"]                                  # (nb, ncat, nslyr | nilyr | nilyr + 1, ny, nx)
+RAD_OUT2D = ["coszen", "alvdr", "alidr", "alvdf", "alidf", "albice", "albsno", "scale_factor"]
+# the reference's namelist defaults (source/ice_init.F90:305-321); albocn of ice_constants.F90
+RAD_DEFAULTS = dict(albicev=0.78, albicei=0.36, albsnowv=0.98, albsnowi=0.70, ahmax=0.3, snowpatch=0.02, albocn=0.06,
+                    awtvdr=0.00318, awtidr=0.00182, awtvdf=0.63282, awtidf=0.36218)
+PREP_RAD_IN = ["aice", "aicen", "swvdr", "swvdf", "swidr", "swidf", "alvdr_ai", "alvdf_ai", "alidr_ai", "alidf_ai"]
+PREP_RAD_INOUT = ["scale_factor", "fswsfcn", "fswintn", "fswthrun", "fswpenln", "Sswabsn", "Iswabsn"]
+
+
+class RadArgs(ct.Structure):
+    """evpk_rad_args (include/evpk.h), member for member"""
+    _fields_ = ([(n, ct.c_int32) for n in RAD_FLAGS] + [("ncat", ct.c_int32), ("ntrcr", ct.c_int32), ("ntrcr_dim", ct.c_int32),
+                                                       ("t", ItdTracers), ("puny", ct.c_double)] +
+                [(n, ct.c_double) for n in RAD_SCALARS] + [(n, c_f64p) for n in RAD_STATE + RAD_FORCING + RAD_OUT + RAD_OUT_LAYERS + RAD_OUT2D])
+
+
+class PrepRadArgs(ct.Structure):
+    """evpk_prep_rad_args (include/evpk.h), member for member"""
+    _fields_ = ([("ncat", ct.c_int32), ("nilyr", ct.c_int32), ("nslyr", ct.c_int32), ("puny", ct.c_double)] +
+                [(n, c_f64p) for n in PREP_RAD_IN + PREP_RAD_INOUT] + [("fswfac", c_f64p)])
+
+
 def remap_tracer_tables(trcr_depend):
     """tracer_type, depend, has_dependents of transport_remap as init_transport builds them from trcr_depend
     (ice_transport_driver.F90:90-118): hice and hsno first (type 1, no parent); a tracer of the area is type 1, one that hangs on a
@@ -291,6 +319,8 @@ def lib():
         L.evpk_step_therm2.argtypes = [ctxp, ct.POINTER(Therm2Args), c_i32p]
         L.evpk_thermo_vertical.argtypes = [ctxp, ct.POINTER(ThermoArgs), c_i32p]
         L.evpk_step_therm1.argtypes = [ctxp, ct.POINTER(Therm1Args), c_i32p]
+        L.evpk_step_radiation.argtypes = [ctxp, ct.POINTER(RadArgs)]
+        L.evpk_prep_radiation.argtypes = [ctxp, ct.POINTER(PrepRadArgs)]
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -825,6 +855,44 @@ class Context:
             return tuple(int(v) for v in stop)
         self._chk(rc, "evpk_step_therm1")
         return None
+
+    def step_radiation(self, state, forcing, out, ntrcr: int, tracers, albedo_type="default", shortwave="default", calc_Tsfc=True,
+                       heat_capacity=True, puny=1.0e-11, **scalars):
+        """evpk_step_radiation: step_radiation (shortwave_ccsm3) and the albedo lines of coupling_prep in one launch.  state: dict of
+        RAD_STATE -- aicen / vicen / vsnon (nb, ncat, ny, nx), trcrn (nb, ncat, ntrcr_dim, ny, nx), read only; forcing: dict of RAD_FORCING
+        (nb, ny, nx), ocn_albedo2D may be absent (then the scalar albocn is the ocean albedo of every cell); out: dict of RAD_OUT (nb, ncat,
+        ny, nx), RAD_OUT_LAYERS (Sswabsn (nb, ncat, nslyr, ny, nx), Iswabsn (nb, ncat, nilyr, ny, nx), fswpenln (nb, ncat, nilyr + 1, ny, nx),
+        which may be absent) and RAD_OUT2D (nb, ny, nx), all written on every cell.  tracers: dict with nt_Tsfc, nilyr, nslyr; scalars: any
+        of RAD_SCALARS (the rest take RAD_DEFAULTS).  Raises on a refusal, which leaves every array untouched."""
+        a = RadArgs()
+        a.shortwave_dEdd, a.calc_Tsfc, a.heat_capacity = int(shortwave == "dEdd"), int(bool(calc_Tsfc)), int(bool(heat_capacity))
+        a.albedo_constant = int(albedo_type == "constant")
+        aicen, trcrn = state.get("aicen"), state.get("trcrn")
+        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
+        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
+        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        a.puny = float(puny)
+        unknown = set(scalars) - set(RAD_SCALARS)
+        if unknown:
+            raise TypeError(f"step_radiation: unknown arguments {sorted(unknown)}")
+        for n in RAD_SCALARS:
+            setattr(a, n, float(scalars.get(n, RAD_DEFAULTS[n])))
+        for names, src in ((RAD_STATE, state), (RAD_FORCING, forcing), (RAD_OUT + RAD_OUT_LAYERS + RAD_OUT2D, out)):
+            for n in names:
+                setattr(a, n, _p64(src.get(n)))
+        self._chk(self._L.evpk_step_radiation(self._ctx, ct.byref(a)), "evpk_step_radiation")
+
+    def prep_radiation(self, arrays, nilyr: int, nslyr: int, puny=1.0e-11):
+        """evpk_prep_radiation: prep_radiation in one launch (an AusCOM host does not call it).  arrays: dict of PREP_RAD_IN (aice and the
+        eight 2-D planes (nb, ny, nx), aicen (nb, ncat, ny, nx)), PREP_RAD_INOUT (rescaled in place on the listed cells; fswpenln may be
+        absent) and fswfac (nb, ny, nx; written on the physical cells).  Raises on a refusal, which leaves every array untouched."""
+        a = PrepRadArgs()
+        aicen = arrays.get("aicen")
+        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
+        a.nilyr, a.nslyr, a.puny = int(nilyr), int(nslyr), float(puny)
+        for n in PREP_RAD_IN + PREP_RAD_INOUT + ["fswfac"]:
+            setattr(a, n, _p64(arrays.get(n)))
+        self._chk(self._L.evpk_prep_radiation(self._ctx, ct.byref(a)), "evpk_prep_radiation")
 
     def thermo_vertical(self, dt: float, state, forcing, inout, out, ntrcr: int, tracers, yday=0.0, conduct=0, min_salin=0.1, constants=None,
                         ktherm=1, calc_Tsfc=True, heat_capacity=True, l_brine=True):

@@ -208,6 +208,32 @@
          integer (c_int32_t) :: formdrag = 0, highfreq = 0, atmbndy_constant = 0, fbot_xfer_Cdn_ocn = 0, tr_aero = 0
       end type evpk_therm1_args
 
+      ! evpk_rad_args, evpk_prep_rad_args (include/evpk.h): the arguments of evpk_step_radiation and evpk_prep_radiation, member for
+      ! member.  ocn_albedo2D and fswpenln may stay c_null_ptr; of t only nt_Tsfc, nilyr, nslyr are read
+      type, bind(C) :: evpk_rad_args
+         integer (c_int32_t) :: shortwave_dEdd = 0, calc_Tsfc = 1, heat_capacity = 1, albedo_constant = 0
+         integer (c_int32_t) :: ncat, ntrcr, ntrcr_dim
+         type (evpk_itd_tracers) :: t
+         real (c_double) :: puny
+         real (c_double) :: albicev, albicei, albsnowv, albsnowi, ahmax, snowpatch, albocn, awtvdr, awtidr, awtvdf, awtidf
+         type (c_ptr) :: aicen = c_null_ptr, vicen = c_null_ptr, vsnon = c_null_ptr, trcrn = c_null_ptr
+         type (c_ptr) :: swvdr = c_null_ptr, swvdf = c_null_ptr, swidr = c_null_ptr, swidf = c_null_ptr, ocn_albedo2D = c_null_ptr
+         type (c_ptr) :: alvdrn = c_null_ptr, alidrn = c_null_ptr, alvdfn = c_null_ptr, alidfn = c_null_ptr, albicen = c_null_ptr
+         type (c_ptr) :: albsnon = c_null_ptr, fswsfcn = c_null_ptr, fswintn = c_null_ptr, fswthrun = c_null_ptr
+         type (c_ptr) :: Sswabsn = c_null_ptr, Iswabsn = c_null_ptr, fswpenln = c_null_ptr
+         type (c_ptr) :: coszen = c_null_ptr, alvdr = c_null_ptr, alidr = c_null_ptr, alvdf = c_null_ptr, alidf = c_null_ptr
+         type (c_ptr) :: albice = c_null_ptr, albsno = c_null_ptr, scale_factor = c_null_ptr
+      end type evpk_rad_args
+      type, bind(C) :: evpk_prep_rad_args
+         integer (c_int32_t) :: ncat, nilyr, nslyr
+         real (c_double) :: puny
+         type (c_ptr) :: aice = c_null_ptr, aicen = c_null_ptr, swvdr = c_null_ptr, swvdf = c_null_ptr, swidr = c_null_ptr, swidf = c_null_ptr
+         type (c_ptr) :: alvdr_ai = c_null_ptr, alvdf_ai = c_null_ptr, alidr_ai = c_null_ptr, alidf_ai = c_null_ptr
+         type (c_ptr) :: scale_factor = c_null_ptr, fswsfcn = c_null_ptr, fswintn = c_null_ptr, fswthrun = c_null_ptr, fswpenln = c_null_ptr
+         type (c_ptr) :: Sswabsn = c_null_ptr, Iswabsn = c_null_ptr
+         type (c_ptr) :: fswfac = c_null_ptr
+      end type evpk_prep_rad_args
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -222,7 +248,8 @@
                 evpk_dyn_args, evpk_bound_state, evpk_step_dynamics, evpk_linear_itd, EVPK_LITD_STOP, &
                 evpk_therm2_args, evpk_new_ice_lateral_melt, evpk_step_therm2, &
                 evpk_thermo_args, evpk_thermo_vertical, EVPK_THERMO_STOP, &
-                evpk_therm1_args, evpk_step_therm1
+                evpk_therm1_args, evpk_step_therm1, &
+                evpk_rad_args, evpk_prep_rad_args, evpk_step_radiation, evpk_prep_radiation
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
@@ -456,6 +483,18 @@
             type (c_ptr), value :: ctx
             type (evpk_therm1_args), intent(in) :: a
             integer (c_int32_t), intent(out) :: stop(5)
+         end function
+         ! step_radiation (ice_step_mod.F90:1364-1524, shortwave_ccsm3) with the albedo lines of coupling_prep in one launch, and
+         ! prep_radiation (:33-145), which an AusCOM host does not call (drivers/auscom/CICE_RunMod.F90:332-338)
+         integer (c_int) function evpk_step_radiation (ctx, a) bind(C, name='evpk_step_radiation')
+            import :: c_int, c_ptr, evpk_rad_args
+            type (c_ptr), value :: ctx
+            type (evpk_rad_args), intent(in) :: a
+         end function
+         integer (c_int) function evpk_prep_radiation (ctx, a) bind(C, name='evpk_prep_radiation')
+            import :: c_int, c_ptr, evpk_prep_rad_args
+            type (c_ptr), value :: ctx
+            type (evpk_prep_rad_args), intent(in) :: a
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then
          ! mm(nx_block,ny_block,0:ncat,max_blocks), tm(nx_block,ny_block,ntrace,ncat,max_blocks) advanced in place

@@ -28,7 +28,7 @@
 
       implicit none
       private
-      public :: evpk_step_dynamics_core
+      public :: evpk_step_dynamics_core, evpk_step_radiation_core
 
       contains
 
@@ -172,6 +172,73 @@
       first_ice = first_i /= 0
 
       end subroutine evpk_step_dynamics_core
+
+!=======================================================================
+
+! step_radiation for every block, and the albedo lines of coupling_prep, in one library call.
+!
+! In the reference's ice_step (drivers/auscom/CICE_RunMod.F90) the loop `call step_radiation (dt, iblk)` and, in coupling_prep, the
+! albedo aggregation (:503-548 without the albcnt, albpnd and apeff_ai lines), the four _ai copies (:564-567) and the scale_factor
+! line (:582-586) become
+!     use ice_step_dyn, only: evpk_step_radiation_core
+!     call evpk_step_radiation_core
+! over the reference's own module arrays.  alvdr_ai .. alidf_ai are plain copies of the four sums: they are made here on the host.
+! This routine only marshals arguments; what the call computes is evpk_step_radiation (include/evpk.h), which refuses
+! shortwave = 'dEdd', calc_Tsfc = .false. and the zero-layer model with its message.
+
+      subroutine evpk_step_radiation_core
+
+      use ice_constants, only: puny, albocn, awtvdr, awtidr, awtvdf, awtidf
+      use ice_domain_size, only: ncat, nilyr, nslyr, max_ntrcr
+      use ice_dyn_evp, only: evpk_context
+      use ice_exit, only: abort_ice
+      use ice_flux, only: swvdr, swvdf, swidr, swidf, coszen, alvdr, alidr, alvdf, alidf, albice, albsno, scale_factor, &
+          alvdr_ai, alidr_ai, alvdf_ai, alidf_ai
+      use ice_shortwave, only: shortwave, albedo_type, albicev, albicei, albsnowv, albsnowi, ahmax, snowpatch, &
+          alvdrn, alidrn, alvdfn, alidfn, albicen, albsnon, fswsfcn, fswintn, fswthrun, fswpenln, Sswabsn, Iswabsn
+#ifdef AusCOM
+      use ice_shortwave, only: ocn_albedo2D
+#endif
+      use ice_state, only: aicen, vicen, vsnon, trcrn, ntrcr, nt_Tsfc
+      use ice_therm_shared, only: heat_capacity, calc_Tsfc
+
+      type (evpk_rad_args) :: a
+      type (c_ptr) :: ctx
+      integer (c_int) :: rc
+
+      ctx = evpk_context ()
+      if (.not. c_associated(ctx)) call abort_ice('step_radiation: no context on the device: evp has not run yet')
+
+      a%shortwave_dEdd = merge(1_c_int32_t, 0_c_int32_t, trim(shortwave) == 'dEdd')
+      a%calc_Tsfc = merge(1_c_int32_t, 0_c_int32_t, calc_Tsfc)
+      a%heat_capacity = merge(1_c_int32_t, 0_c_int32_t, heat_capacity)
+      a%albedo_constant = merge(1_c_int32_t, 0_c_int32_t, trim(albedo_type) == 'constant')
+      a%ncat = int(ncat, c_int32_t)
+      a%ntrcr = int(ntrcr, c_int32_t)
+      a%ntrcr_dim = int(max_ntrcr, c_int32_t)
+      a%t%nt_Tsfc = int(nt_Tsfc, c_int32_t);  a%t%nilyr = int(nilyr, c_int32_t);  a%t%nslyr = int(nslyr, c_int32_t)
+      a%puny = puny
+      a%albicev = albicev;  a%albicei = albicei;  a%albsnowv = albsnowv;  a%albsnowi = albsnowi;  a%ahmax = ahmax
+      a%snowpatch = snowpatch;  a%albocn = albocn
+      a%awtvdr = awtvdr;  a%awtidr = awtidr;  a%awtvdf = awtvdf;  a%awtidf = awtidf
+
+      a%aicen = loc_r8(aicen);  a%vicen = loc_r8(vicen);  a%vsnon = loc_r8(vsnon);  a%trcrn = loc_r8(trcrn)
+      a%swvdr = loc_r8(swvdr);  a%swvdf = loc_r8(swvdf);  a%swidr = loc_r8(swidr);  a%swidf = loc_r8(swidf)
+#ifdef AusCOM
+      a%ocn_albedo2D = loc_r8(ocn_albedo2D)
+#endif
+      a%alvdrn = loc_r8(alvdrn);  a%alidrn = loc_r8(alidrn);  a%alvdfn = loc_r8(alvdfn);  a%alidfn = loc_r8(alidfn)
+      a%albicen = loc_r8(albicen);  a%albsnon = loc_r8(albsnon)
+      a%fswsfcn = loc_r8(fswsfcn);  a%fswintn = loc_r8(fswintn);  a%fswthrun = loc_r8(fswthrun)
+      a%Sswabsn = loc_r8(Sswabsn);  a%Iswabsn = loc_r8(Iswabsn);  a%fswpenln = loc_r8(fswpenln)
+      a%coszen = loc_r8(coszen);  a%alvdr = loc_r8(alvdr);  a%alidr = loc_r8(alidr);  a%alvdf = loc_r8(alvdf);  a%alidf = loc_r8(alidf)
+      a%albice = loc_r8(albice);  a%albsno = loc_r8(albsno);  a%scale_factor = loc_r8(scale_factor)
+
+      rc = evpk_step_radiation (ctx, a)
+      if (rc /= 0) call abort_ice('step_radiation: evpk_step_radiation: '//trim(evpk_error_string(ctx)))
+      alvdr_ai = alvdr;  alidr_ai = alidr;  alvdf_ai = alvdf;  alidf_ai = alidf      ! CICE_RunMod.F90:564-567
+
+      end subroutine evpk_step_radiation_core
 
 !=======================================================================
 

@@ -746,6 +746,92 @@ typedef struct {
 } evpk_therm1_args;
 int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t stop[5] /* out: reason, block, category, i, j */);
 
+/* the shortwave of ice_step (kernels in csrc/evpk_rad.hip).  With it the per-category radiation arrays that
+ * evpk_step_therm1 reads (fswsfcn, fswintn, fswthrun, Sswabsn, Iswabsn) are made on the device from the state the project leaves there.
+ *
+ * evpk_step_radiation: step_radiation (source/ice_step_mod.F90:1364-1524) on its calc_Tsfc / not-dEdd branch -- shortwave_ccsm3
+ * (source/ice_shortwave.F90:425-646; shortwave = 'default', reference/input_templates/gx1/ice_in.v4.1:116-119) -- and the albedo lines
+ * of coupling_prep that follow it at once in the reference's ice_step (drivers/auscom/CICE_RunMod.F90:503-548, :564-567, :582-586), in
+ * ONE launch (k_shortwave_ccsm3) for every category of every block: one thread per cell that walks the categories in order.
+ *   initialisation     on EVERY cell of the block arrays, ghost cells included (ice_step_mod.F90:1408-1423, ice_shortwave.F90:523,
+ *                      :538, :737-777, :1106-1116): coszen = 0.5; alvdrn, alidrn, alvdfn, alidfn = the ocean albedo of the cell;
+ *                      albicen, albsnon, fswsfcn, fswintn, fswthrun, every layer of Sswabsn, Iswabsn and fswpenln = 0
+ *   ocean albedo       the AusCOM build reads the 2-D ocn_albedo2D (:759-772, :798, :814), the stock build the scalar albocn: where
+ *                      ocn_albedo2D is NULL, albocn is used on every cell
+ *   cell list          per category (:527-536): physical cells with aicen > puny AND tmask -- the stated departure of
+ *                      evpk_thermo_vertical, kept so that every column kernel lists the same cells
+ *   compute_albedos    (:786-859) hi, hs; fh = min(atan(4 hi) / fhtan, 1), fhtan = atan(4 ahmax), both through evpk_atan; albo; the
+ *                      bare-ice albedos; fT = min(dTs / dT_melt - 1, 0); the max against the ocean albedo; the snow albedos under
+ *                      hs > puny; direct = diffuse; asnow = hs / (hs + snowpatch); the four combined albedos; albicen, albsnon with
+ *                      the four awt* weights summed left to right
+ *   constant_albedos   (:964-1009) with albedo_constant (albedo_type = 'constant') instead
+ *   absorbed_solar     (:1118-1211) asnow again; swabsv, swabsi, swabs with the parentheses as written; fswpenvdr, fswpenvdf
+ *                      multiplied left to right; fswpen, fswsfc; per layer k hilyr = hi / nilyr, tranbot = exp(((-kappav) hilyr) k)
+ *                      through dev_exp, Iswabs(k) = fswpen (trantop - tranbot), fswpenl(k), fswpenl(k+1); fswthru = fswpen tranbot,
+ *                      fswint = fswpen - fswthru.  Sswabsn stays zero: the CCSM3 scheme absorbs nothing in snow layers
+ *   aggregation        every cell, categories in order: alvdf, alidf, alvdr, alidr += al*n aicen; albice, albsno likewise under
+ *                      coszen > puny (always true here; the test is kept); scale_factor = swvdr (1 - alvdr) + swvdf (1 - alvdf) +
+ *                      swidr (1 - alidr) + swidf (1 - alidf) in that order.  alvdr_ai .. alidf_ai are plain copies of the four sums
+ *                      (:564-567): they are not separate outputs, the caller aliases them
+ * Operation order: the Fortran's; min / max are a comparison and a select; x**2 does not occur.
+ * Compiled in: kappav = 1.4, Timelt = 0 (drivers/auscom/ice_constants.F90:82, :65); dT_melt = 1, dalb_mlt = -0.075, dalb_mltv = -0.1,
+ * dalb_mlti = -0.15 (source/ice_shortwave.F90:709-716: local parameters that shadow the namelist variable); i0vis = 0.70 (:1079);
+ * warmice = 0.68, coldice = 0.70, warmsnow = 0.77, coldsnow = 0.81 (:923-927).
+ * **Parity unpinned**: no recipe under oracle/ builds these routines; both calls are held bit for bit to a numpy restatement written
+ * from the Fortran (tests/nprad.py).
+ * Members (one struct of borrowed pointers; arrays (nx_block, ny_block[, ncat], nblocks) unless given):
+ *   shortwave_dEdd, calc_Tsfc, heat_capacity (only 0, 1, 1 are accepted), albedo_constant (0 default / 1 'constant')
+ *   ncat, ntrcr, ntrcr_dim, t (nt_Tsfc, nilyr, nslyr are read) as in evpk_thermo_args; puny (must be 1e-11)
+ *   albicev, albicei, albsnowv, albsnowi, ahmax, snowpatch, albocn, awtvdr, awtidr, awtvdf, awtidf      the namelist's
+ *   aicen, vicen, vsnon, trcrn                               in
+ *   swvdr, swvdf, swidr, swidf, ocn_albedo2D                 in, 2-D; ocn_albedo2D may be NULL
+ *   alvdrn, alidrn, alvdfn, alidfn, albicen, albsnon, fswsfcn, fswintn, fswthrun      out, per category, every cell
+ *   Sswabsn (.., nslyr, ncat, ..), Iswabsn (.., nilyr, ncat, ..), fswpenln (.., nilyr+1, ncat, ..; may be NULL)    out, every cell
+ *   coszen, alvdr, alidr, alvdf, alidf, albice, albsno, scale_factor                  out, 2-D, every cell
+ * Nothing the call overwrites is copied up.
+ *
+ * evpk_prep_radiation: prep_radiation (source/ice_step_mod.F90:33-145), the rescaling in front of step_therm1 that drivers other than
+ * AusCOM call, in one launch (k_prep_radiation).  drivers/auscom/CICE_RunMod.F90:332-338 compiles the call out: an AusCOM host does
+ * NOT call it.  On every physical cell (land included, as in the reference): if aice > 0 and scale_factor > puny, scale_factor = netsw /
+ * scale_factor with netsw built in the order of :87-90 (the order of the line that made scale_factor), else scale_factor = 1; fswfac =
+ * scale_factor.  On the category list (physical, tmask, aicen > puny): fswsfcn, fswintn, fswthrun, the nilyr + 1 planes of fswpenln
+ * where given and the layers of Sswabsn and Iswabsn are multiplied by that factor.  Ghost cells of every array, and land cells of the
+ * category arrays, keep the caller's values.
+ *   ncat, nilyr, nslyr, puny
+ *   aice, aicen, swvdr, swvdf, swidr, swidf, alvdr_ai, alvdf_ai, alidr_ai, alidf_ai   in
+ *   scale_factor, fswsfcn, fswintn, fswthrun, fswpenln (may be NULL), Sswabsn, Iswabsn      in / out
+ *   fswfac                                                   out, physical cells
+ * Both return 0; or 1 with evpk_last_error, before any copy, touching nothing: shortwave = 'dEdd'; calc_Tsfc = .false.; heat_capacity =
+ * .false. (the zero-layer tail of absorbed_solar, :1218-1236); nilyr or nslyr outside 1..8; ncat outside 1..16; a tracer index beyond
+ * ntrcr; puny != 1e-11; a missing pointer; a context of several ranks (nranks > 1) on which evpk_connect has not run.
+ * x-slab ranks: neither call is collective -- a rank without a block column returns 0.
+ * Out of scope: Delta-Eddington (run_dEdd) and everything it feeds: albpndn, apeffn, snowfracn, albpnd, apeff_ai; the tr_pond_topo
+ * lines of the not-calc_Tsfc branch (:1482-1501); the remaining lines of coupling_prep: frzmlt_init, ocean_mixed_layer, albcnt, the
+ * fpond / fresh lines, the _ai flux copies, scale_fluxes, sfcflux_to_ocn; the halo update of scale_factor (CICE_RunMod.F90:395) --
+ * nothing here reads a ghost cell of it. */
+#define EVPK_HAS_STEP_RADIATION 1
+typedef struct {
+    int32_t shortwave_dEdd, calc_Tsfc, heat_capacity, albedo_constant;
+    int32_t ncat, ntrcr, ntrcr_dim;
+    evpk_itd_tracers t;
+    double puny;
+    double albicev, albicei, albsnowv, albsnowi, ahmax, snowpatch, albocn, awtvdr, awtidr, awtvdf, awtidf;
+    const double *aicen, *vicen, *vsnon, *trcrn;                              /* in */
+    const double *swvdr, *swvdf, *swidr, *swidf, *ocn_albedo2D;               /* in; ocn_albedo2D may be NULL */
+    double *alvdrn, *alidrn, *alvdfn, *alidfn, *albicen, *albsnon, *fswsfcn, *fswintn, *fswthrun;     /* out, per category, every cell */
+    double *Sswabsn, *Iswabsn, *fswpenln;                                     /* out; fswpenln may be NULL */
+    double *coszen, *alvdr, *alidr, *alvdf, *alidf, *albice, *albsno, *scale_factor;                  /* out, 2-D, every cell */
+} evpk_rad_args;
+typedef struct {
+    int32_t ncat, nilyr, nslyr;
+    double puny;
+    const double *aice, *aicen, *swvdr, *swvdf, *swidr, *swidf, *alvdr_ai, *alvdf_ai, *alidr_ai, *alidf_ai;       /* in */
+    double *scale_factor, *fswsfcn, *fswintn, *fswthrun, *fswpenln, *Sswabsn, *Iswabsn;       /* in / out; fswpenln may be NULL */
+    double *fswfac;                                                           /* out */
+} evpk_prep_rad_args;
+int evpk_step_radiation(evpk_ctx *c, const evpk_rad_args *a);
+int evpk_prep_radiation(evpk_ctx *c, const evpk_prep_rad_args *a);
+
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared
  * (:79-80), stress_eap (:1052-1467) with update_stress_rdg (:1474-1658) takes the place of stress, stepa (:1664-1787, with

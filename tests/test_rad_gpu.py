@@ -1,0 +1,389 @@
+"""evpk_step_radiation and evpk_prep_radiation on the device against the numpy restatement tests/nprad.py -- bit for bit: step_radiation
+writes every cell of every output, so its arrays are compared on every cell; prep_radiation's in / out arrays carry sentinels in their
+ghost cells (and the category arrays on land too), which must survive.  The kernels use + - x /, comparisons, selects and the
+fixed-algorithm exp and atan (csrc/evpk_fmath2.h, whose Python ports the restatement runs on), and the library is built with
+-ffp-contract=off.  **Parity with the reference is unpinned** (no reference-built record).  Inputs: tests/golden/radvec.py (no shape
+larger than 26 x 18 cells); tests/test_rad_host.py shows that they take every branch.
+"""
+import os
+import sys
+import traceback
+import uuid
+
+import numpy as np
+import pytest
+
+try:
+    import torch          # before libevpk: the process must end up with ONE HIP runtime (torch bundles its own)
+    torch.cuda.is_available()
+except ImportError:
+    torch = None
+
+from cice5_amd import evpk
+from tests import nptherm1s
+from tests.golden import itdvec as iv
+from tests.golden import radvec as rv
+from tests.golden import therm1svec as sv
+from tests.golden import therm1vec as tv
+from tests.test_rad_host import AI, physical, prep_arrays, prep_restate, restated
+from tests.test_therm1_gpu import cells, eq, geometry, params
+from tests.test_therm1s_gpu import call as call_therm1
+from tests.test_therm1s_host import arrays as therm1s_arrays
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SENTINEL = -777.25
+CFG = "g26x18_b8x5"
+PREP_WRITTEN = ["scale_factor", "fswfac"] + rv.RADIATION
+
+
+@pytest.fixture(scope="module")
+def contexts():
+    made = {}
+
+    def get(cfg):
+        if cfg not in made:
+            x = restated(cfg, "plain")[0]
+            _, d, f = geometry(cfg)
+            f["tmask"] = x["tmask"]                 # the land of the inputs
+            made[cfg] = evpk.Context(d, f)
+            made[cfg].set_params(params(x))
+        return made[cfg]
+    yield get
+    for c in made.values():
+        c.close()
+
+
+def put(a, m, v):
+    """a[..., cells of m] = v, the block axis first"""
+    np.moveaxis(a, (0, -2, -1), (0, 1, 2))[m] = v
+
+
+def outputs(x, penl=True):
+    y = {k: x[k].copy() for k in rv.WRITTEN}
+    if not penl:
+        y["fswpenln"] = None
+    return y
+
+
+def call(ctx, x, y, ocn2d=True, **kw):
+    g = lambda k: y[k] if k in y else x.get(k)
+    forcing = {k: g(k) for k in evpk.RAD_FORCING}
+    if not ocn2d:
+        forcing["ocn_albedo2D"] = None
+    a = dict(ntrcr=x["ntrcr"], tracers=x["tracers"])
+    a.update({k: x[k] for k in evpk.RAD_SCALARS})
+    a.update(kw)
+    return ctx.step_radiation({k: g(k) for k in evpk.RAD_STATE}, forcing, {k: g(k) for k in rv.WRITTEN}, **a)
+
+
+def call_prep(ctx, x, z, **kw):
+    tr = x["tracers"]
+    a = dict(nilyr=tr["nilyr"], nslyr=tr["nslyr"])
+    a.update(kw)
+    return ctx.prep_radiation(z, **a)
+
+
+def assert_equal(got, want):
+    for k in rv.WRITTEN:
+        if want.get(k) is None:
+            assert got.get(k) is None, k
+            continue
+        assert eq(got[k], want[k]), (k, int((got[k] != want[k]).sum()))
+
+
+def run_case(ctx, cfg, tcase, ncat=5, ocn2d=True, penl=True, **kw):
+    """one evpk_step_radiation against the restatement of the same case, every cell of every array; returns (x, y, want)"""
+    x, want, _, _ = restated(cfg, tcase, ncat, ocn2d, penl, **kw)
+    y = outputs(x, penl)
+    assert call(ctx, x, y, ocn2d=ocn2d, **kw) is None
+    assert_equal(y, want)
+    return x, y, want
+
+
+@pytest.mark.parametrize("cfg", list(rv.CONFIGS))
+@pytest.mark.parametrize("tcase", rv.TABLES)
+def test_equals_restatement_on_every_cell_and_prep_leaves_ghost_and_land_cells(contexts, cfg, tcase):
+    """both grids (the second block of each is ice-free), the plain table (k_shortwave_ccsm3<5, 4, 1>) and the deep one (7 + 2 layers,
+    the generic kernels): equal to the restatement on every cell, ghost cells included.  Then evpk_prep_radiation under the changed
+    shortwave, with a scale_factor of 5e-12 in some cells, sentinels in the ghost cells of scale_factor and fswfac and in the ghost and
+    land cells of the category arrays: equal to the restatement where the reference writes, the sentinels survive"""
+    ctx = contexts(cfg)
+    x, y, want = run_case(ctx, cfg, tcase)
+    listed = (x["aicen"] > rv.PUNY) & x["ocean"][:, None]
+    assert (x["aicen"][1] == 0.0).all() and y["fswsfcn"][listed].any() and not y["fswsfcn"][~listed].any()
+    phys = physical(x)
+    wz, _ = prep_restate(x, want)
+    z = prep_arrays(x, y)
+    for k in ("scale_factor", "fswfac"):
+        z[k][~phys] = SENTINEL
+    for k in rv.RADIATION:
+        put(z[k], ~x["ocean"], SENTINEL)
+    assert call_prep(ctx, x, z) is None
+    for k in ("scale_factor", "fswfac"):
+        assert eq(z[k][phys], wz[k][phys]), k
+        assert (z[k][~phys] == SENTINEL).all(), k
+    for k in rv.RADIATION:
+        assert eq(cells(z[k], x["ocean"]), cells(wz[k], x["ocean"])), k
+        assert (cells(z[k], ~x["ocean"]) == SENTINEL).all(), k
+    assert not eq(z["fswsfcn"], y["fswsfcn"]) and (z["scale_factor"][x["sf_tiny"]] == 1.0).all()
+
+
+@pytest.mark.parametrize("kw", [dict(ocn2d=False), dict(albedo_type="constant"), dict(ocn2d=False, albedo_type="constant"), dict(penl=False)],
+                         ids=["albocn", "constant", "constant_albocn", "no_fswpenln"])
+def test_argument_variants(contexts, kw):
+    """ocn_albedo2D NULL (the scalar albocn on every cell); albedo_type = 'constant'; fswpenln NULL with every other array identical"""
+    x, y, want = run_case(contexts(CFG), CFG, "plain", **kw)
+    base = restated(CFG, "plain")[1]
+    if kw.get("penl") is False:
+        for k in rv.WRITTEN:
+            if k != "fswpenln":
+                assert eq(y[k], base[k]), k
+    else:
+        assert not eq(y["alvdfn"], base["alvdfn"])
+    if kw.get("ocn2d") is False:
+        listed = (x["aicen"] > rv.PUNY) & x["ocean"][:, None]
+        assert (y["alvdrn"][~listed] == x["albocn"]).all()
+
+
+@pytest.mark.parametrize("ncat,tcase", [(3, "plain"), (1, "plain"), (3, "deep")])
+def test_generic_kernel_with_fewer_categories(contexts, ncat, tcase):
+    run_case(contexts(CFG), CFG, tcase, ncat)
+
+
+def test_prep_without_fswpenln(contexts):
+    ctx = contexts(CFG)
+    x, want, _, _ = restated(CFG, "plain")
+    wz, _ = prep_restate(x, want)
+    z = prep_arrays(x, want)
+    z["fswpenln"] = None
+    assert call_prep(ctx, x, z) is None
+    for k in PREP_WRITTEN:
+        if k != "fswpenln":
+            assert eq(z[k], wz[k]), k
+
+
+@pytest.mark.parametrize("tcase", rv.TABLES)
+def test_round_trip_is_the_identity(contexts, tcase):
+    """evpk_step_radiation, then evpk_prep_radiation with the same sw* and the aggregated albedos as alvdr_ai ..: scale_factor is exactly
+    1 wherever it was > puny and aice > 0, and every radiation array is bit for bit unchanged; with sw* doubled the factor is exactly 2
+    and every array doubles exactly"""
+    ctx = contexts(CFG)
+    x, want, _, _ = restated(CFG, tcase)
+    y = outputs(x)
+    assert call(ctx, x, y) is None
+    phys = physical(x)
+    acted = phys & (x["aice"] > 0.0) & (y["scale_factor"] > rv.PUNY)
+    assert acted.sum() > 20
+    z = prep_arrays(x, y, sw="sw", tiny=False)
+    assert call_prep(ctx, x, z) is None
+    assert (z["scale_factor"][phys] == 1.0).all() and (z["fswfac"][phys] == 1.0).all()
+    for k in rv.RADIATION:
+        assert eq(z[k], y[k]), k
+    xx = dict(x, **{q: 2.0 * x[q] for q in rv.BANDS})
+    z = prep_arrays(xx, y, sw="sw", tiny=False)
+    assert call_prep(ctx, x, z) is None
+    assert (z["scale_factor"][acted] == 2.0).all() and (z["scale_factor"][phys & ~acted] == 1.0).all()
+    lit = np.broadcast_to(acted[:, None], y["fswsfcn"].shape) & (x["aicen"] > rv.PUNY) & x["ocean"][:, None]
+    for k in rv.RADIATION:
+        m = lit if y[k].ndim == 4 else np.broadcast_to(lit[:, :, None], y[k].shape)
+        assert eq(z[k][m], 2.0 * y[k][m]) and eq(z[k][~m], y[k][~m]), k
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a).copy()).cuda()
+
+
+def test_device_tensors_and_pageable_arrays_agree(contexts):
+    ctx = contexts(CFG)
+    x, want, _, _ = restated(CFG, "plain")
+    y = outputs(x)
+    assert not evpk.host_is_mapped(y["fswsfcn"])
+    assert call(ctx, x, y) is None
+    dev = {k: _dev(x[k]) for k in rv.STATE + rv.FORCING + rv.WRITTEN}
+    assert call(ctx, x, dev) is None
+    torch.cuda.synchronize()
+    for k in rv.WRITTEN:
+        assert eq(dev[k].cpu().numpy(), y[k]), k
+    assert_equal(y, want)
+    z = prep_arrays(x, y)
+    assert call_prep(ctx, x, z) is None
+    dz = {k: _dev(v) for k, v in prep_arrays(x, y).items()}
+    assert call_prep(ctx, x, dz) is None
+    torch.cuda.synchronize()
+    for k in PREP_WRITTEN:
+        assert eq(dz[k].cpu().numpy(), z[k]), k
+
+
+def test_chain_on_device_tensors_into_step_therm1(contexts):
+    """evpk_step_radiation -> evpk_prep_radiation (under the changed shortwave, the aggregated albedos aliased as alvdr_ai ..) ->
+    evpk_step_therm1 on device tensors that never visit the host, against nprad -> nprad -> nptherm1s: the state, the 22 merged planes
+    and the radiation arrays"""
+    ctx = contexts(CFG)
+    x, w1, _, _ = restated(CFG, "plain")
+    wz, _ = prep_restate(x, w1, tiny=False)
+    w = therm1s_arrays(x)
+    carried = ["fswsfcn", "fswintn", "fswthrun", "Sswabsn", "Iswabsn"]
+    w.update({k: wz[k].copy() for k in carried})
+    infos, stop, _ = nptherm1s.step(iv.blocks_of(x["d"]), x["tmask"], nptherm1s.params(x), w)
+    assert stop is None
+    names64 = sv.WRITTEN + sv.IN2D + ["flw", "potT", "Qa", "rhoa", "fsnow", "sss", "fswthrun"]
+    dev = {k: _dev(x[k]) for k in set(names64 + rv.STATE + rv.FORCING + rv.WRITTEN + ["fswfac"] + [q[:2] + "2" + q[2:] for q in rv.BANDS])}
+    dev.update({k: _dev(x[k]) for k in evpk.THERM1_MASKS})
+    assert call(ctx, x, dev) is None
+    dz = {k: dev[k] for k in PREP_WRITTEN + ["aice", "aicen"]}
+    dz.update({q: dev[q[:2] + "2" + q[2:]] for q in rv.BANDS})
+    dz.update({k: dev[v] for k, v in AI.items()})
+    assert call_prep(ctx, x, dz) is None
+    assert call_therm1(ctx, x, dev) is None
+    torch.cuda.synchronize()
+    got = {k: v.cpu().numpy() for k, v in dev.items()}
+    m = x["ocean"]
+    for k in tv.STATE + sv.MERGED + ["fswsfcn", "fswintn", "Sswabsn", "Iswabsn"]:
+        assert eq(cells(got[k], m), cells(w[k], m)), (k, int((cells(got[k], m) != cells(w[k], m)).sum()))
+    for k in ("fswthrun", "fswpenln", "scale_factor", "fswfac"):
+        assert eq(cells(got[k], m), cells(wz[k], m)), k
+    assert not eq(got["fswabs"], x["fswabs"]) and not eq(got["vicen"], x["vicen"])            # (step_therm1 went on from there)
+
+
+def _refused(fn, ctx, x, y, match, **kw):
+    with pytest.raises(evpk.EvpkError, match=match):
+        fn(ctx, x, y, **kw)
+    return True
+
+
+def test_refusals_leave_the_arrays_untouched(contexts):
+    ctx = contexts(CFG)
+    x, want, _, _ = restated(CFG, "plain")
+    y = outputs(x)
+    tr = x["tracers"]
+    nb, ncat, ny, nx = x["aicen"].shape
+    R = lambda match, xx=x, yy=y, **kw: _refused(call, ctx, xx, yy, match, **kw)
+    R("shortwave = 'dEdd'", shortwave="dEdd")
+    R("calc_Tsfc", calc_Tsfc=False)
+    R("heat_capacity", heat_capacity=False)
+    R("nilyr = 9", tracers=dict(tr, nilyr=9))
+    R("nilyr = 0", tracers=dict(tr, nilyr=0))
+    R("nslyr = 9", tracers=dict(tr, nslyr=9))
+    R("nslyr = 0", tracers=dict(tr, nslyr=0))
+    R("ncat = 17 not in", xx=dict(x, aicen=np.zeros((nb, 17, ny, nx))))
+    R("ncat = 0 not in", xx=dict(x, aicen=np.zeros((nb, 0, ny, nx))))
+    R("lies beyond ntrcr", tracers=dict(tr, nt_Tsfc=x["ntrcr"] + 1))
+    R("lies beyond ntrcr", tracers=dict(tr, nt_Tsfc=0))
+    R("puny = 1e-12", puny=1.0e-12)
+    for k in rv.STATE + [q for q in rv.FORCING if q != "ocn_albedo2D"]:
+        R("a required argument is missing", xx=dict(x, **{k: None}))
+    for k in rv.WRITTEN:
+        if k != "fswpenln":
+            R("a required argument is missing", yy=dict(y, **{k: None}))
+    for k in rv.WRITTEN:
+        assert eq(y[k], x[k]), k
+    z = prep_arrays(x, want)
+    before = {k: z[k].copy() for k in PREP_WRITTEN}
+    P = lambda match, zz=z, **kw: _refused(call_prep, ctx, x, zz, match, **kw)
+    P("nilyr = 9", nilyr=9)
+    P("nslyr = 0", nslyr=0)
+    P("ncat = 17 not in", zz=dict(z, aicen=np.zeros((nb, 17, ny, nx))))
+    P("puny = 1e-12", puny=1.0e-12)
+    for k in z:
+        if k != "fswpenln":
+            P("a required argument is missing", zz=dict(z, **{k: None}))
+    for k in PREP_WRITTEN:
+        assert eq(z[k], before[k]), k
+
+
+def test_refusal_on_more_than_one_rank_before_connect():
+    x = restated(CFG, "plain")[0]
+    _, d, f = geometry(CFG, nprocs=2, rank=0)
+    ctx = evpk.Context(d, f, defer_connect=True)    # (the geometry says two ranks; nothing collective has happened)
+    try:
+        nb = d.nblocks
+        assert nb > 0
+        xx = {k: (np.ascontiguousarray(v[:nb]) if isinstance(v, np.ndarray) and v.ndim >= 3 else v) for k, v in x.items()}
+        y = outputs(xx)
+        with pytest.raises(evpk.EvpkError, match="nranks = 2"):
+            call(ctx, xx, y)
+        z = prep_arrays(xx, y)
+        with pytest.raises(evpk.EvpkError, match="nranks = 2"):
+            call_prep(ctx, xx, z)
+        for k in rv.WRITTEN:
+            assert eq(y[k], xx[k]), k
+    finally:
+        ctx.close()
+
+
+# ---- x-slab ranks: one process per rank on one GPU (the harness of tests/test_therm1s_gpu.py) ----
+def job_rad(rank, world, tag, tcase):
+    d1, d, f = geometry(CFG, world, rank)
+    at = {b.block_id: n for n, b in enumerate(d1.local_blocks)}
+    loc = [at[b.block_id] for b in d.local_blocks]
+    x = rv.rad_input(CFG, tcase)
+    f["tmask"] = np.ascontiguousarray(x["tmask"][loc])
+    cut = lambda a: np.ascontiguousarray(a[loc])
+    ctx = evpk.Context(d, f, device=0, unique_id=(b"EVPKIPC:" + f"{tag}_0".encode()).ljust(128, b"\0"))
+    try:
+        ctx.set_params(params(x))
+        names = rv.STATE + rv.FORCING + ["aice", "fswfac", "sf_tiny"] + [q[:2] + "2" + q[2:] for q in rv.BANDS]
+        xx = dict(x, **{k: cut(x[k]) for k in names})
+        y = {k: cut(x[k]) for k in rv.WRITTEN}
+        call(ctx, xx, y)
+        z = prep_arrays(xx, y)
+        call_prep(ctx, xx, z)
+    finally:
+        ctx.close()
+    return loc, y, {k: z[k] for k in PREP_WRITTEN}
+
+
+def _worker(rank, world, tag, job, args, q):
+    try:
+        sys.path.insert(0, ROOT)
+        os.environ["OMP_NUM_THREADS"] = "2"
+        q.put((rank, None, globals()[job](rank, world, tag, *args)))
+    except Exception:
+        q.put((rank, traceback.format_exc(), None))
+
+
+def _spawn(world, job, args=(), timeout=240):
+    import multiprocessing as mp
+    assert world <= 3                              # (+ the parent: at most 4 processes hold the GPU)
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    tag = "evpk_rad_" + uuid.uuid4().hex[:12]
+    procs = [ctx.Process(target=_worker, args=(r, world, tag, job, args, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = {}
+    try:
+        for _ in procs:
+            rank, err, out = q.get(timeout=timeout)
+            assert err is None, f"rank {rank}: {err}"
+            res[rank] = out
+    finally:
+        for p in procs:
+            p.join(timeout=1 if len(res) < world else 30)
+            if p.is_alive():
+                p.kill()
+        try:
+            os.unlink(f"/dev/shm/{tag}_0")
+        except OSError:
+            pass
+    return [res[r] for r in range(world)]
+
+
+def test_ranks_equal_the_restatement():
+    """three rank processes on one GPU, of which two own block columns and the third owns none: put together, the ranks' blocks equal the
+    restatement of both calls; the rank without a block column returns 0"""
+    tcase = "plain"
+    x, want, _, _ = restated(CFG, tcase)
+    wz, _ = prep_restate(x, want)
+    outs = _spawn(3, "job_rad", (tcase,))
+    assert [len(loc) > 0 for loc, _, _ in outs] == [True, True, False]
+    seen = sorted(n for loc, _, _ in outs for n in loc)
+    assert seen == list(range(x["aicen"].shape[0]))
+    for loc, y, z in outs[:2]:
+        assert_equal(y, {k: want[k][loc] for k in rv.WRITTEN})
+        for k in PREP_WRITTEN:
+            assert eq(z[k], wz[k][loc]), k
+    for k in rv.WRITTEN:                            # the idle rank's (empty) arrays are what it passed
+        assert outs[2][1][k].shape[0] == 0

@@ -1,0 +1,257 @@
+"""evpk_step_radiation and evpk_prep_radiation without a GPU: the entry points are declared, exported and bound (header, ctypes structures
+and Fortran types member by member), and the numpy restatement tests/nprad.py -- the checker of tests/test_rad_gpu.py -- takes every
+branch the inputs of tests/golden/radvec.py are drawn for and satisfies, recomputed from outside its own code, the energy budget of
+absorbed_solar, the bounds of the albedos and the sums of coupling_prep; step_radiation followed by prep_radiation under the same
+shortwave is the identity, which pins the order in which both build the net shortwave.
+
+**Parity with the reference is unpinned**: no reference-built record exists for these routines.
+
+The spread between the restatement on the ports of the device's math (tests/npfmath2.py, npridge.dev_exp) and on libm is printed per
+array and bounded by four times the spread measured here with libm, as
+tests/test_ridge_ref.py::test_spread_between_the_two_exps does; no column may take another branch.
+"""
+import ctypes as ct
+import os
+import re
+
+import numpy as np
+import pytest
+
+from cice5_amd import evpk
+from tests import nprad
+from tests.golden import itdvec as iv
+from tests.golden import radvec as rv
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+COUNTED = ["hs_pos", "hs_zero", "fh_capped", "fh_below", "fT_zero", "fT_neg", "ocn_max_taken", "ocn_max_not", "night", "lit"]
+PREP_COUNTED = ["aice_zero", "sf_tiny", "scaled"]
+EPS = 2.0 ** -52
+# the largest |ports - libm| measured here per array, relative to the array's largest magnitude, over both grids and both tables
+# (printed by test_spread_between_ports_and_libm); the test allows four times as much
+SPREAD_MEASURED = 3.3e-16
+AI = dict(alvdr_ai="alvdr", alvdf_ai="alvdf", alidr_ai="alidr", alidf_ai="alidf")          # the caller's aliases (CICE_RunMod.F90:564-567)
+
+
+def params(x, **kw):
+    p = {k: x[k] for k in nprad.SCALARS}
+    p["tr"] = x["tracers"]
+    p["albedo_type"] = "default"
+    p.update(kw)
+    return p
+
+
+def arrays(x, ocn2d=True, penl=True):
+    """copies of every array step_radiation writes, and the read-only ones as they are"""
+    y = {k: x[k].copy() for k in rv.WRITTEN}
+    y.update({k: x[k] for k in rv.STATE + rv.FORCING})
+    if not ocn2d:
+        y["ocn_albedo2D"] = None
+    if not penl:
+        y["fswpenln"] = None
+    return y
+
+
+def restate(x, M=nprad.PORTS, ocn2d=True, penl=True, **kw):
+    """(arrays, infos, sig) of the restatement of step_radiation on copies; kw: members of nprad's p (albedo_type)"""
+    y = arrays(x, ocn2d, penl)
+    infos, sig = nprad.step_radiation(iv.blocks_of(x["d"]), x["tmask"], params(x, **kw), y, M)
+    return y, infos, sig
+
+
+_cache = {}
+
+
+def restated(cfg, tcase, ncat=5, ocn2d=True, penl=True, **kw):
+    """the inputs and the restatement on the ports: computed once per case, shared, not modified"""
+    key = (cfg, tcase, ncat, ocn2d, penl) + tuple(sorted(kw.items()))
+    if key not in _cache:
+        x = rv.rad_input(cfg, tcase, ncat=ncat)
+        _cache[key] = (x,) + restate(x, ocn2d=ocn2d, penl=penl, **kw)
+    return _cache[key]
+
+
+def prep_arrays(x, y, sw="sw2", tiny=True):
+    """the arrays of one prep_radiation call behind step_radiation's result y: copies of what it rewrites; sw: "sw" the shortwave
+    step_radiation saw, "sw2" the changed one; tiny: scale_factor = 5e-12 on the cells of x["sf_tiny"]"""
+    z = {k: (y[k].copy() if y[k] is not None else None) for k in rv.RADIATION + ["scale_factor"]}
+    z["fswfac"] = x["fswfac"].copy()
+    z.update(aice=x["aice"], aicen=x["aicen"])
+    for q in rv.BANDS:
+        z[q] = x[q] if sw == "sw" else x[q[:2] + "2" + q[2:]]
+    z.update({k: y[v] for k, v in AI.items()})
+    if tiny:
+        z["scale_factor"][x["sf_tiny"]] = 5.0e-12
+    return z
+
+
+def prep_restate(x, y, **kw):
+    z = prep_arrays(x, y, **kw)
+    infos = nprad.prep_radiation(iv.blocks_of(x["d"]), x["tmask"], params(x), z)
+    return z, infos
+
+
+def physical(x):
+    phys = np.zeros(x["aice"].shape, dtype=bool)
+    for b, (ilo, ihi, jlo, jhi) in enumerate(iv.blocks_of(x["d"])):
+        phys[b, jlo - 1:jhi, ilo - 1:ihi] = True
+    return phys
+
+
+def _struct_names(hdr, name):
+    body = re.search(r"typedef struct \{([^}]*)\} %s;" % name, hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    return [w.strip().split()[-1].lstrip("*") for part in body.split(";") for w in part.split(",") if w.strip()]
+
+
+def test_header_declares_the_entry_points():
+    hdr = open(os.path.join(ROOT, "include", "evpk.h")).read()
+    assert re.search(r"^#define EVPK_HAS_STEP_RADIATION 1$", hdr, re.M)
+    assert re.search(r"^#define EVPK_VERSION 6$", hdr, re.M)
+    assert re.search(r"^int evpk_step_radiation\(evpk_ctx \*c, const evpk_rad_args \*a\);$", hdr, re.M)
+    assert re.search(r"^int evpk_prep_radiation\(evpk_ctx \*c, const evpk_prep_rad_args \*a\);$", hdr, re.M)
+    assert _struct_names(hdr, "evpk_rad_args") == [n for n, _ in evpk.RadArgs._fields_]            # the ctypes mirrors, member for member
+    assert _struct_names(hdr, "evpk_prep_rad_args") == [n for n, _ in evpk.PrepRadArgs._fields_]
+    assert dict(evpk.RadArgs._fields_)["t"] is evpk.ItdTracers
+    block = hdr[hdr.index("SURVEY S8 row f-12"):hdr.index("#define EVPK_HAS_STEP_RADIATION")]
+    assert "**Parity unpinned**" in block
+    for word in ("run_dEdd", "albpndn", "apeffn", "snowfracn", "albpnd", "apeff_ai", "tr_pond_topo", "frzmlt_init", "ocean_mixed_layer",
+                 "albcnt", "scale_fluxes", "sfcflux_to_ocn", "CICE_RunMod.F90:395", "CICE_RunMod.F90:332-338", "tmask", "ocn_albedo2D",
+                 "kappav = 1.4", "i0vis = 0.70", "dalb_mlt = -0.075", "warmice = 0.68"):
+        assert word in block, word
+
+
+def test_symbols_are_exported_and_bound():
+    L = ct.CDLL(evpk.LIB_PATH)
+    for name in ("evpk_step_radiation", "evpk_prep_radiation"):
+        assert name in evpk.EXPORTS and hasattr(L, name)
+    assert callable(evpk.Context.step_radiation) and callable(evpk.Context.prep_radiation)
+    assert evpk.RAD_STATE == rv.STATE and evpk.RAD_FORCING == rv.FORCING and evpk.RAD_OUT == rv.OUT3D == nprad.OUT3D
+    assert evpk.RAD_OUT_LAYERS == rv.OUT_LAYERS == nprad.OUT_LAYERS and evpk.RAD_OUT2D == rv.OUT2D == nprad.OUT2D
+    assert evpk.RAD_SCALARS == nprad.SCALARS == list(rv.SCALARS) and evpk.RAD_DEFAULTS == rv.SCALARS
+    assert evpk.PREP_RAD_INOUT == ["scale_factor"] + rv.RADIATION
+
+
+def _fortran_names(src, name):
+    body = src[src.index("type, bind(C) :: " + name):src.index("end type " + name)]
+    body = re.sub(r"!.*", "", body)
+    return [re.sub(r"\s*=.*", "", w).strip() for line in body.splitlines()[1:] if "::" in line for w in re.split(r",(?![^(]*\))", line.split("::")[1])]
+
+
+def test_fortran_interface():
+    src = open(os.path.join(ROOT, "fortran", "evpk_mod.F90")).read()
+    assert "bind(C, name='evpk_step_radiation')" in src and "bind(C, name='evpk_prep_radiation')" in src
+    assert _fortran_names(src, "evpk_rad_args") == [n for n, _ in evpk.RadArgs._fields_]
+    assert _fortran_names(src, "evpk_prep_rad_args") == [n for n, _ in evpk.PrepRadArgs._fields_]
+    assert "type (evpk_itd_tracers) :: t" in src[src.index("type, bind(C) :: evpk_rad_args"):src.index("end type evpk_rad_args")]
+
+
+@pytest.mark.parametrize("cfg", list(rv.CONFIGS))
+def test_inputs_take_every_branch(cfg):
+    """the counts of the restatement's info records, summed over the blocks and the two tracer tables of one grid: every item of the
+    input list of tests/golden/radvec.py, each non-zero, over more than 300 listed (cell, category) columns"""
+    tot = {k: 0 for k in COUNTED + PREP_COUNTED + ["listed"]}
+    for tcase in rv.TABLES:
+        x, y, infos, sig = restated(cfg, tcase)
+        listed = int(((x["aicen"] > rv.PUNY) & x["ocean"][:, None]).sum())
+        assert sum(i["listed"] for i in infos) == listed == len(sig) > 300
+        assert (x["aicen"][1] == 0.0).all() and infos[1]["listed"] == 0, "an ice-free block"
+        assert (np.diff(x["ocn_albedo2D"], axis=1) != 0.0).all(), "ocn_albedo2D varies with the row"
+        thin = x["thin_warm"] & (x["aicen"] > rv.PUNY) & x["ocean"][:, None]
+        assert thin.any() and all(sig[tuple(k)][3] for k in np.argwhere(thin)), "thin, warm, bare ice takes the max against the ocean albedo"
+        _, pinfos = prep_restate(x, y)
+        for i in infos + pinfos:
+            for k in i:
+                if k in tot:
+                    tot[k] += i[k]
+    print(cfg, tot)
+    for k in COUNTED + PREP_COUNTED:
+        assert tot[k] > 0, k
+    _, _, infos, _ = restated(cfg, "plain", albedo_type="constant")
+    assert all(sum(i[k] for i in infos) > 0 for k in ("warm_const", "cold_const", "hs_pos", "hs_zero"))
+
+
+@pytest.mark.parametrize("cfg", list(rv.CONFIGS))
+@pytest.mark.parametrize("tcase", rv.TABLES)
+@pytest.mark.parametrize("albedo_type", ["default", "constant"])
+def test_budget_bounds_and_sums_from_the_returned_arrays(cfg, tcase, albedo_type):
+    """from outside the restatement's own code, on its returned arrays.  Tolerances: the budget is a sum of four products of magnitude at
+    most the incoming shortwave S, rebuilt through some twenty roundings of relative size 2^-52 each, hence 64 * 2^-52 * S; the layer sum
+    telescopes to fswpen (1 - tranbot) through nilyr + 2 roundings on terms no larger than fswintn + fswthrun, hence 32 * 2^-52 of that"""
+    x, y, infos, sig = restated(cfg, tcase, albedo_type=albedo_type)
+    ncat = x["aicen"].shape[1]
+    listed = (x["aicen"] > rv.PUNY) & x["ocean"][:, None]
+    S = x["swvdr"] + x["swvdf"] + x["swidr"] + x["swidf"]
+    absorbed = (x["swvdr"][:, None] * (1.0 - y["alvdrn"]) + x["swvdf"][:, None] * (1.0 - y["alvdfn"]) + x["swidr"][:, None] * (1.0 - y["alidrn"])
+                + x["swidf"][:, None] * (1.0 - y["alidfn"]))
+    total = y["fswsfcn"] + y["fswintn"] + y["fswthrun"]
+    assert (np.abs(total - absorbed)[listed] <= (64.0 * EPS * S[:, None] * np.ones_like(total))[listed]).all()
+    assert total[listed].any()
+    layers = y["Iswabsn"].sum(axis=2)
+    assert (np.abs(layers - y["fswintn"]) <= 32.0 * EPS * (np.abs(y["fswintn"]) + np.abs(y["fswthrun"]))).all()
+    assert not y["Sswabsn"].any()
+    assert (y["fswintn"][listed] >= 0.0).all() and (y["fswthrun"][listed] >= 0.0).all() and (y["fswsfcn"][listed] >= 0.0).all()
+    ocn = x["ocn_albedo2D"][:, None]
+    top = max(x["albsnowv"], x["albsnowi"], x["albicev"], x["albicei"], nprad.COLDSNOW)
+    for q in ("alvdrn", "alidrn", "alvdfn", "alidfn"):
+        assert (y[q] >= ocn).all() and (y[q] <= top).all(), q
+        assert (y[q][~listed] == np.broadcast_to(ocn, y[q].shape)[~listed]).all(), q
+    for q in ("albicen", "albsnon", "fswsfcn", "fswintn", "fswthrun"):
+        assert not y[q][~listed].any(), q
+    for q in ("Iswabsn", "fswpenln"):
+        assert not y[q][np.broadcast_to(~listed[:, :, None], y[q].shape)].any(), q
+    assert np.array_equal(y["fswpenln"][:, :, -1], y["fswthrun"])
+    assert (y["coszen"] == 0.5).all()
+    for m, q in (("alvdr", "alvdrn"), ("alidr", "alidrn"), ("alvdf", "alvdfn"), ("alidf", "alidfn"), ("albice", "albicen"), ("albsno", "albsnon")):
+        want = np.zeros(x["aice"].shape)
+        for n in range(ncat):
+            want = want + y[q][:, n] * x["aicen"][:, n]
+        assert np.array_equal(want, y[m]), m
+    night = S == 0.0
+    assert night[x["ocean"]].any() and (~night)[x["ocean"]].any()
+    assert not y["scale_factor"][night].any()
+    for q in ("fswsfcn", "fswintn", "fswthrun"):
+        assert not y[q][np.broadcast_to(night[:, None], y[q].shape)].any(), q
+
+
+@pytest.mark.parametrize("cfg", list(rv.CONFIGS))
+@pytest.mark.parametrize("tcase", rv.TABLES)
+def test_round_trip_is_the_identity(cfg, tcase):
+    """step_radiation, then prep_radiation with the same sw* and the aggregated albedos: scale_factor is exactly 1 wherever it was > puny
+    and aice > 0, and every radiation array is bit for bit unchanged -- both lines build netsw in one order, and this pins that order.
+    With sw* doubled the factor is exactly 2 and every array doubles exactly"""
+    x, y, _, _ = restated(cfg, tcase)
+    phys = physical(x)
+    acted = phys & (x["aice"] > 0.0) & (y["scale_factor"] > rv.PUNY)
+    assert acted.sum() > 20
+    z, infos = prep_restate(x, y, sw="sw", tiny=False)
+    assert sum(i["scaled"] for i in infos) == acted.sum()
+    assert (z["scale_factor"][phys] == 1.0).all() and (z["fswfac"][phys] == 1.0).all()
+    assert np.array_equal(z["scale_factor"][~phys], y["scale_factor"][~phys]) and np.array_equal(z["fswfac"][~phys], x["fswfac"][~phys])
+    for q in rv.RADIATION:
+        assert np.array_equal(z[q], y[q]), q
+    xx = dict(x, **{q: 2.0 * x[q] for q in rv.BANDS})
+    z, _ = prep_restate(xx, y, sw="sw", tiny=False)
+    assert (z["scale_factor"][acted] == 2.0).all() and (z["scale_factor"][phys & ~acted] == 1.0).all()
+    lit = np.broadcast_to(acted[:, None], y["fswsfcn"].shape) & (x["aicen"] > rv.PUNY) & x["ocean"][:, None]
+    for q in rv.RADIATION:
+        m = lit if y[q].ndim == 4 else np.broadcast_to(lit[:, :, None], y[q].shape)
+        assert np.array_equal(z[q][m], 2.0 * y[q][m]) and np.array_equal(z[q][~m], y[q][~m]), q
+    assert y["fswsfcn"][lit].any()
+
+
+def test_spread_between_ports_and_libm():
+    """the restatement on the ports against the restatement on math.exp / math.atan: the device's fixed algorithms are within 1 - 2 ulp of
+    glibc, and the call amplifies that no further than this; no column takes another branch"""
+    worst = 0.0
+    for cfg in rv.CONFIGS:
+        for tcase in rv.TABLES:
+            x, y, infos, sig = restated(cfg, tcase)
+            z, _, sig2 = restate(x, nprad.LIBM)
+            assert sig == sig2, "a column on another branch: move that input off the threshold"
+            for k in rv.WRITTEN:
+                scale = float(np.abs(y[k]).max())
+                spread = float(np.abs(y[k] - z[k]).max()) / scale if scale else 0.0
+                print(f"  {cfg} {tcase} {k:14s} {spread:.3e}")
+                worst = max(worst, spread)
+    print("largest relative spread", worst)
+    assert worst <= 4.0 * SPREAD_MEASURED
