@@ -438,7 +438,7 @@ int evpk_aggregate(evpk_ctx *c, double dt, int32_t bound, int32_t ncat, int32_t 
  * is left with donor = 0 but daice > 0 -- only a negative vicen under aicen > puny can do that, through the second "entire category"
  * rule -- moves nothing (the reference indexes category 0 there).
  * Parity: PINNED to reference-built output.  The call equals, bit for bit on the physical ocean cells, the records of the reference's
- * own compiled linear_itd -- fit_line and the boundary integrals included (tests/golden/ref_litd_*.npz, oracle/ref/therm2.mk;
+ * own compiled linear_itd -- fit_line and the boundary integrals included (tests/golden/ref_litd_*.npz, oracle/ref/Makefile, target therm2;
  * tests/test_therm2_ref_gpu.py), and so does the numpy restatement written from the Fortran (tests/nplitd.py, tests/test_therm2_ref.py).
  * The reference leaves hin_max(ncat) = 999.9 in its module for whatever runs after it (ice_therm_itd.F90:208; recorded with every
  * fixture); this call takes that value inside and leaves the caller's hin_max alone -- no routine after it reads hin_max(ncat).
@@ -553,7 +553,7 @@ int evpk_step_dynamics(evpk_ctx *c, const evpk_dyn_args *a, int32_t stop[5] /* o
  * (ice_therm_vertical.F90:575-591) -- salinz must be horizontally uniform for parity.  (c) add_new_ice_bgc, aerosols and bgc tracers
  * are refused.
  * Parity: PINNED to reference-built output.  add_new_ice, lateral_melt, reduce_area and the mushy liquidus equal, bit for bit on the
- * physical ocean cells, the records of the reference's own compiled routines (tests/golden/ref_therm2_*.npz, oracle/ref/therm2.mk),
+ * physical ocean cells, the records of the reference's own compiled routines (tests/golden/ref_therm2_*.npz, oracle/ref/Makefile, target therm2),
  * each on its own and chained, and evpk_step_therm2 equals the record after cleanup_itd (tests/test_therm2_ref_gpu.py); the numpy
  * restatement written from the Fortran (tests/nptherm2.py) equals the records stage by stage (tests/test_therm2_ref.py).  The liquidus
  * parameters derived in the module's expression order are the values the Fortran compiler folds: no difference was found.  The

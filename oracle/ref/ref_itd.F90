@@ -1,6 +1,6 @@
 !=======================================================================
 ! ref_itd -- test infrastructure (ours, not reference code): a driver for the reference's own cleanup_itd, aggregate (ice_itd) and
-! bound_state (ice_state), compiled unmodified by oracle/ref/itd.mk.  It is written from the interfaces of those routines and from
+! bound_state (ice_state), compiled unmodified by oracle/ref/Makefile (target itd).  It is written from the interfaces of those routines and from
 ! their calls in step_ridge (ice_step_mod.F90:1325-1341) and step_dynamics (:1152-1189): the domain is set up as in ref_harness.F90
 ! (init_domain_blocks, init_domain_distribution -> halo_info), the tracer indices / flags of ice_state, hin_max of ice_itd,
 ! heat_capacity of ice_therm_shared and Tocnfrz are set from the input, cleanup_itd is called block by block with the block's

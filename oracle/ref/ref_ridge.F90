@@ -1,6 +1,6 @@
 !=======================================================================
 ! ref_ridge -- test infrastructure (ours, not reference code): a driver for the reference's own ridge_ice (ice_mechred), compiled
-! unmodified by oracle/ref/ridge.mk.  It is written from ridge_ice's interface and step_ridge's call (ice_step_mod.F90:1272-1305): it
+! unmodified by oracle/ref/Makefile (target ridge).  It is written from ridge_ice's interface and step_ridge's call (ice_step_mod.F90:1272-1305): it
 ! sets the namelist switches of ice_mechred, hin_max of ice_itd and the tracer indices / flags of ice_state that ridge_shift and
 ! compute_tracers read, builds step_ridge's cell list (physical cells with tmask) and calls ridge_ice block by block with every
 ! optional argument.  tests/golden/make_ref_ridge.py turns its dumps into the fixtures tests/golden/ref_ridge_*.npz.

@@ -1,6 +1,6 @@
 !=======================================================================
 ! ref_therm2 -- test infrastructure (ours, not reference code): a driver for the reference's own linear_itd, add_new_ice, lateral_melt
-! (ice_therm_itd, compiled unmodified and whole by oracle/ref/therm2.mk, with fit_line, update_vertical_tracers and the mushy liquidus
+! (ice_therm_itd, compiled unmodified and whole by oracle/ref/Makefile (target therm2), with fit_line, update_vertical_tracers and the mushy liquidus
 ! of ice_therm_mushy) and aggregate_area, reduce_area, cleanup_itd (ice_itd).  It is written from the interfaces of those routines and
 ! from their calls in step_therm2 (ice_step_mod.F90:792-993): the domain is set up as in ref_itd.F90 (init_domain_blocks,
 ! init_domain_distribution), and per case the tracer indices / flags of ice_state (nt_sice, nt_FY and tr_FY among them), hin_max, hi_min

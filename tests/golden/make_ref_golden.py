@@ -8,56 +8,21 @@ refvec.py:     python tests/golden/make_ref_golden.py
 from __future__ import annotations
 
 import os
-import struct
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-from tests.golden import refvec as rv  # noqa: E402
+from tests.golden import refrun, refvec as rv  # noqa: E402
+from tests.golden.refrun import Writer  # noqa: E402
 
-REFDIR = os.path.join(ROOT, "oracle", "ref")
 NTRCR_BOUND = 3
 
 
 def build(cfg):
-    nx, ny, bx, by, mxb = rv.CONFIGS[cfg]
-    exe = os.path.join(ROOT, "oracle", "_ref", cfg, "ref_harness")
-    subprocess.check_call(["make", "-C", REFDIR, f"CFG={cfg}", f"NX={nx}", f"NY={ny}", f"BX={bx}", f"BY={by}", f"MXB={mxb}",
-                           f"NCAT={rv.NCAT}"], stdout=subprocess.DEVNULL)
-    return exe
-
-
-class Writer:
-    def __init__(self):
-        self.parts = []
-
-    def i4(self, *v):
-        self.parts.append(np.asarray(v, dtype=np.int32).tobytes())
-
-    def r8(self, *v):
-        self.parts.append(np.asarray(v, dtype=np.float64).tobytes())
-
-    def arr(self, a):
-        self.parts.append(np.ascontiguousarray(a).tobytes())
-
-    def raw(self, b):
-        self.parts.append(b)
-
-
-class Reader:
-    def __init__(self, buf):
-        self.b, self.o = buf, 0
-
-    def take(self, dtype, shape):
-        n = int(np.prod(shape)) if shape else 1
-        a = np.frombuffer(self.b, dtype=dtype, count=n, offset=self.o).reshape(shape).copy()
-        self.o += a.nbytes
-        return a
+    return refrun.build("ref_harness", cfg, rv.CONFIGS[cfg], rv.NCAT)
 
 
 def run_case(exe, cfg, ew, ns, land, with_strength):
@@ -128,19 +93,10 @@ def run_case(exe, cfg, ew, ns, land, with_strength):
     plan.append(("global_minval", np.float64, ()))
     w.i4(0)
 
-    with tempfile.TemporaryDirectory() as td:
-        with open(os.path.join(td, "in.bin"), "wb") as f:
-            f.write(b"".join(w.parts))
-        with open(os.path.join(td, "cice_in.nml"), "w") as f:
-            f.write("&domain_nml\n  nprocs = 1\n  processor_shape = 'slenderX1'\n  distribution_type = 'cartesian'\n"
-                    "  distribution_wght = 'latitude'\n"
-                    f"  ew_boundary_type = '{ew}'\n  ns_boundary_type = '{ns}'\n"
-                    "  maskhalo_dyn = .false.\n  maskhalo_remap = .false.\n  maskhalo_bound = .false.\n/\n")
-        p = subprocess.run([exe, "in.bin", "out.bin"], cwd=td, capture_output=True, text=True)
-        if p.returncode != 0 or not os.path.exists(os.path.join(td, "out.bin")):
-            return None, (p.stdout[-600:] + p.stderr[-600:])
-        buf = open(os.path.join(td, "out.bin"), "rb").read()
-    r = Reader(buf)
+    try:
+        r, _ = refrun.run(exe, w.payload(), refrun.domain_nml(ew, ns))
+    except AssertionError as e:
+        return None, str(e)
     out = {}
     hdr = r.take(np.int32, (7,))
     assert tuple(hdr[:5]) == (nx, ny, nxb, nyb, mxb) and hdr[5] == rv.NCAT and hdr[6] == rv.MAX_NTRCR, hdr
@@ -166,12 +122,12 @@ def run_case(exe, cfg, ew, ns, land, with_strength):
         if key.startswith("bound/"):
             a = np.ascontiguousarray(a[:nblocks])
         out[key] = a
-    assert r.o == len(buf), (r.o, len(buf))
-    return out, p.stdout[-300:]
+    r.done()
+    return out, ""
 
 
-def main():
-    for ci, cfg in enumerate(rv.CONFIGS):
+def main(outdir=HERE):
+    for cfg in rv.CONFIGS:
         exe = build(cfg)
         allout = {}
         nbt = ((rv.CONFIGS[cfg][0] - 1) // rv.CONFIGS[cfg][2] + 1) * ((rv.CONFIGS[cfg][1] - 1) // rv.CONFIGS[cfg][3] + 1)
@@ -190,14 +146,14 @@ def main():
             for k, v in out.items():
                 allout[f"{case}/{k}"] = v
             print(f"{cfg} {case}: {len(out)} arrays")
-        path = os.path.join(HERE, f"ref_{cfg}.npz")
+        path = os.path.join(outdir, f"ref_{cfg}.npz")
         np.savez_compressed(path, **allout)
         print(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
-    from tests.golden import make_ref_kernels          # the slice fixtures ref_dyn_*.npz (evp_prep1 .. stress)
-    make_ref_kernels.main()
-    from tests.golden import make_ref_remap            # the remap slice fixtures ref_remap_*.npz (make_masks .. update_fields)
-    make_ref_remap.main()
 
 
 if __name__ == "__main__":
     main()
+    from tests.golden import make_ref_kernels          # the slice fixtures ref_dyn_*.npz (evp_prep1 .. stress)
+    make_ref_kernels.main()
+    from tests.golden import make_ref_remap            # the remap slice fixtures ref_remap_*.npz (make_masks .. update_fields)
+    make_ref_remap.main()

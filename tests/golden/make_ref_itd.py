@@ -1,5 +1,5 @@
 """Makes tests/golden/ref_itd_<cfg>.<case>.npz from the reference's own cleanup_itd, bound_state and aggregate: oracle/_ref/<cfg>/ref_itd
-(oracle/ref/itd.mk + oracle/ref/ref_itd.F90, built by __graft_entry__.build() where the reference is present).  Inputs come from itdvec;
+(oracle/ref/Makefile, target itd + oracle/ref/ref_itd.F90, built by __graft_entry__.build() where the reference is present).  Inputs come from itdvec;
 only the reference's OUTPUTS are stored:
   after cleanup_itd alone, on the physical ocean cells in (block, j, i) order:
     aicen / vicen / vsnon (L, ncat)  trcrn (L, ncat, ntrcr)  aice0, aice, fpond, fresh, fsalt, fhocn (L,)  first_ice (L, ncat)
@@ -16,9 +16,7 @@ and ref_itd_stops.npz with the stop records.  The generator asserts what the fix
 from __future__ import annotations
 
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -27,93 +25,62 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from tests.golden import itdvec as iv          # noqa: E402
+from tests.golden import itdvec as iv, refrun          # noqa: E402
+from tests.golden.refrun import Writer, on_cells, padded, same          # noqa: E402,F401
 
 CELL2 = ["aice0", "aice"] + iv.FLUX
-IDX = ("nt_Tsfc", "nt_qice", "nt_qsno", "nt_alvl", "nt_vlvl", "nt_apnd", "nt_hpnd", "nt_fbri", "nt_iage", "tr_pond_cesm", "tr_pond_lvl",
-       "tr_pond_topo", "tr_brine")
+IDX = tuple(k for k in refrun.IDX if k not in ("nt_sice", "nt_FY"))          # what ref_itd.F90 reads
 
 
 def run_reference(x):
     """the driver on one input; returns (after cleanup, after the chain or None), dicts of full block arrays"""
     cfg, d = x["cfg"], x["d"]
-    exe = os.path.join(ROOT, "oracle", "_ref", cfg, "ref_itd")
     _, _, _, _, mxb = iv.CONFIGS[cfg]
     nb, ncat, ntrcr, ny, nx = d.nblocks, x["ncat"], x["ntrcr"], d.ny_block, d.nx_block
     ew, ns, _ = iv.BOUNDS[x["bcase"]]
     kmt, ulat = iv.kmt_ulat(cfg, x["bcase"])
     tr = x["tracers"]
-    i32 = lambda *v: np.array(v, dtype=np.int32).tobytes()
-    f64 = lambda *v: np.array(v, dtype=np.float64).tobytes()
-
-    def padded(a, shape_tail):
-        out = np.zeros((mxb,) + shape_tail, dtype=a.dtype)
-        out[:nb] = a
-        return out.tobytes()
     t20 = np.zeros((mxb, ncat, iv.MAX_NTRCR, ny, nx))
     t20[:nb, :, :ntrcr] = x["trcrn"]
-    buf = [kmt.astype(np.float64).tobytes(), ulat.astype(np.float64).tobytes(), i32(1), i32(ntrcr), i32(*[tr.get(k, 0) for k in IDX]),
-           f64(x["dt"], x["k"]["Tocnfrz"]), x["hin_max"].astype(np.float64).tobytes(), x["trcr_depend"].tobytes(), x["tmask"].tobytes()]
-    buf += [padded(x[k], (ncat, ny, nx)) for k in ("aicen", "vicen", "vsnon")]
-    buf.append(t20.tobytes())
-    w = np.zeros((9, mxb, ny, nx))
-    for q, k in enumerate(CELL2 + iv.TEND):
-        w[q, :nb] = x[k]
-    buf += [w.tobytes(), padded(x["first_ice"], (ncat, ny, nx)), i32(0)]
-    with tempfile.TemporaryDirectory() as tmp:
-        with open(os.path.join(tmp, "in.bin"), "wb") as f:
-            f.write(b"".join(buf))
-        with open(os.path.join(tmp, "cice_in.nml"), "w") as f:
-            f.write("&domain_nml\n  nprocs = 1\n  processor_shape = 'slenderX1'\n  distribution_type = 'cartesian'\n"
-                    "  distribution_wght = 'latitude'\n"
-                    f"  ew_boundary_type = '{ew}'\n  ns_boundary_type = '{ns}'\n"
-                    "  maskhalo_dyn = .false.\n  maskhalo_remap = .false.\n  maskhalo_bound = .false.\n/\n")
-        p = subprocess.run([exe, "in.bin", "out.bin"], cwd=tmp, capture_output=True, text=True)
-        assert p.returncode == 0, p.stdout[-600:] + p.stderr[-600:]
-        raw = open(os.path.join(tmp, "out.bin"), "rb").read()
-    pos = 0
-
-    def take(dtype, shape):
-        nonlocal pos
-        a = np.frombuffer(raw, dtype=dtype, count=int(np.prod(shape)), offset=pos).reshape(shape).copy()
-        pos += a.nbytes
-        return a
-    hdr = take(np.int32, (6,))
+    w = Writer()
+    w.arr(kmt.astype(np.float64)); w.arr(ulat.astype(np.float64)); w.i4(1); w.i4(ntrcr); w.i4(*[tr.get(k, 0) for k in IDX])
+    w.r8(x["dt"], x["k"]["Tocnfrz"]); w.arr(x["hin_max"].astype(np.float64)); w.arr(x["trcr_depend"]); w.arr(x["tmask"])
+    for k in ("aicen", "vicen", "vsnon"):
+        w.arr(padded(x[k], mxb))
+    w.arr(t20)
+    for k in CELL2 + iv.TEND:
+        w.arr(padded(x[k], mxb))
+    w.arr(padded(x["first_ice"], mxb)); w.i4(0)
+    r, _ = refrun.run(refrun.exe("ref_itd", cfg), w.payload(), refrun.domain_nml(ew, ns))
+    hdr = r.take(np.int32, (6,))
     assert tuple(hdr) == (nx, ny, ncat, iv.MAX_NTRCR, mxb, nb), hdr
-    blk = take(np.int32, (nb, 4))
+    blk = r.take(np.int32, (nb, 4))
     assert [tuple(r) for r in blk] == iv.blocks_of(d)
-    st = take(np.int32, (nb, 3))
+    st = r.take(np.int32, (nb, 3))
     one = dict(l_stop=st[:, 0].copy(), istop=st[:, 1].copy(), jstop=st[:, 2].copy())
     for k in ("aicen", "vicen", "vsnon"):
-        one[k] = take(np.float64, (mxb, ncat, ny, nx))[:nb]
-    one["trcrn"] = np.ascontiguousarray(take(np.float64, (mxb, ncat, iv.MAX_NTRCR, ny, nx))[:nb, :, :ntrcr])
-    w = take(np.float64, (6, mxb, ny, nx))
+        one[k] = r.take(np.float64, (mxb, ncat, ny, nx))[:nb]
+    one["trcrn"] = np.ascontiguousarray(r.take(np.float64, (mxb, ncat, iv.MAX_NTRCR, ny, nx))[:nb, :, :ntrcr])
+    w = r.take(np.float64, (6, mxb, ny, nx))
     for q, k in enumerate(CELL2):
         one[k] = w[q, :nb].copy()
-    one["first_ice"] = take(np.int32, (mxb, ncat, ny, nx))[:nb]
-    chain = int(take(np.int32, (1,))[0])
+    one["first_ice"] = r.take(np.int32, (mxb, ncat, ny, nx))[:nb]
+    chain = int(r.take(np.int32, (1,))[0])
     two = None
     if chain:
         two = {}
         for k in ("aicen", "vicen", "vsnon"):
-            two[k] = take(np.float64, (mxb, ncat, ny, nx))[:nb]
-        two["trcrn"] = np.ascontiguousarray(take(np.float64, (mxb, ncat, iv.MAX_NTRCR, ny, nx))[:nb, :, :ntrcr])
-        w = take(np.float64, (4, mxb, ny, nx))
+            two[k] = r.take(np.float64, (mxb, ncat, ny, nx))[:nb]
+        two["trcrn"] = np.ascontiguousarray(r.take(np.float64, (mxb, ncat, iv.MAX_NTRCR, ny, nx))[:nb, :, :ntrcr])
+        w = r.take(np.float64, (4, mxb, ny, nx))
         for q, k in enumerate(("aice", "vice", "vsno", "aice0")):
             two[k] = w[q, :nb].copy()
-        two["trcr"] = np.ascontiguousarray(take(np.float64, (mxb, iv.MAX_NTRCR, ny, nx))[:nb, :ntrcr])
-        w = take(np.float64, (3, mxb, ny, nx))
+        two["trcr"] = np.ascontiguousarray(r.take(np.float64, (mxb, iv.MAX_NTRCR, ny, nx))[:nb, :ntrcr])
+        w = r.take(np.float64, (3, mxb, ny, nx))
         for q, k in enumerate(iv.TEND):
             two[k] = w[q, :nb].copy()
-    assert pos == len(raw), (pos, len(raw))
+    r.done()
     return one, two
-
-
-def on_cells(a, m):
-    """values of a block array on the cells of mask m (nb, ny, nx), (block, j, i) order, the category / tracer axes last"""
-    if a.ndim == 3:
-        return a[m]
-    return np.moveaxis(a, (0, -2, -1), (0, 1, 2))[m]
 
 
 def restate(x, chain=True, fluxes=True):
@@ -220,11 +187,7 @@ COVER = ["up", "down", "cascade", "edge_up_stays", "edge_down_moves", "block_nos
          "zap1-", "zap2", "zapT_cold", "zapT_warm", "thin_kept"]
 
 
-def same(a, b):
-    return a.shape == b.shape and bool(((a == b) | (np.isnan(a) & np.isnan(b))).all()) if a.dtype.kind == "f" else np.array_equal(a, b)
-
-
-def main():
+def main(outdir=HERE):
     seen = {k: 0 for k in COVER}
     for cfg, recs in iv.RECORDS.items():
         for tcase, bcase in recs:
@@ -241,7 +204,7 @@ def main():
             bad = [k for k in rec if not same(rec[k], got[k])]
             print(f"{cfg}.{tcase}_{bcase}: restatement vs reference differs in {bad or 'nothing'}")
             coverage(x, rec, infos, seen)
-            path = os.path.join(HERE, f"ref_itd_{cfg}.{iv.record_name(tcase, bcase)}.npz")
+            path = os.path.join(outdir, f"ref_itd_{cfg}.{iv.record_name(tcase, bcase)}.npz")
             np.savez_compressed(path, **rec)
             print(f"   {os.path.getsize(path) / 1024:.0f} KiB")
     print(seen)
@@ -256,7 +219,7 @@ def main():
         print("stop", name, "reference: blocks", np.nonzero(one["l_stop"])[0] + 1, "first", (b + 1, one["istop"][b], one["jstop"][b]), "restatement", st)
         assert (b + 1, int(one["istop"][b]), int(one["jstop"][b])) == sp["expect"], name
         stops[name] = np.stack([one["l_stop"], one["istop"], one["jstop"]]).astype(np.int32)
-    np.savez_compressed(os.path.join(HERE, "ref_itd_stops.npz"), **stops)
+    np.savez_compressed(os.path.join(outdir, "ref_itd_stops.npz"), **stops)
 
 
 if __name__ == "__main__":

@@ -15,9 +15,7 @@ from __future__ import annotations
 
 import ctypes as ct
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -26,8 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 from cice5_amd import constants as C  # noqa: E402
 from oracle import orc  # noqa: E402
-from tests.golden import refvec as rv  # noqa: E402
-from tests.golden.make_ref_golden import REFDIR, Reader, Writer  # noqa: E402
+from tests.golden import refrun, refvec as rv  # noqa: E402
+from tests.golden.refrun import Writer  # noqa: E402
 
 SN = rv.STRESS_NAMES
 # the planes ref_kernels.F90 reads / writes, in its order
@@ -49,29 +47,17 @@ CHAIN_OUT = ["fm", "strtltx", "strtlty", "strocnx", "strocny", "strintx", "strin
 
 
 def build(cfg):
-    nx, ny, bx, by, mxb = rv.KERNEL_CONFIGS[cfg]
-    subprocess.check_call(["make", "-C", REFDIR, "kernels", f"CFG={cfg}", f"NX={nx}", f"NY={ny}", f"BX={bx}", f"BY={by}", f"MXB={mxb}",
-                           f"NCAT={rv.NCAT}"], stdout=subprocess.DEVNULL)
-    return os.path.join(ROOT, "oracle", "_ref", cfg, "ref_kernels")
+    return refrun.build("ref_kernels", cfg, rv.KERNEL_CONFIGS[cfg], rv.NCAT)
 
 
-def run(exe, cfg, ew, ns, land, w):
+def run(exe, cfg, ew, ns, land, w, ncat=None):
+    """-> (Reader behind the header, block bounds); ref_remap's header carries its ncat as a seventh integer"""
     nx, ny, bx, by, mxb = rv.KERNEL_CONFIGS[cfg]
     kmt, ulat = rv.kmt_ulat(nx, ny, bx, by, ew, ns, land)
-    with tempfile.TemporaryDirectory() as td:
-        with open(os.path.join(td, "in.bin"), "wb") as f:
-            f.write(kmt.tobytes() + ulat.tobytes() + b"".join(w.parts) + np.int32(0).tobytes())
-        with open(os.path.join(td, "cice_in.nml"), "w") as f:
-            f.write("&domain_nml\n  nprocs = 1\n  processor_shape = 'slenderX1'\n  distribution_type = 'cartesian'\n"
-                    f"  distribution_wght = 'latitude'\n  ew_boundary_type = '{ew}'\n  ns_boundary_type = '{ns}'\n"
-                    "  maskhalo_dyn = .false.\n  maskhalo_remap = .false.\n  maskhalo_bound = .false.\n/\n")
-        p = subprocess.run([exe, "in.bin", "out.bin"], cwd=td, capture_output=True, text=True)
-        assert p.returncode == 0, p.stdout[-800:] + p.stderr[-800:]
-        r = Reader(open(os.path.join(td, "out.bin"), "rb").read())
-    hdr = r.take(np.int32, (6,))
-    assert tuple(hdr[:5]) == (nx, ny, bx + 2, by + 2, mxb), hdr
-    bounds = r.take(np.int32, (int(hdr[5]), 4))
-    return r, bounds
+    r, _ = refrun.run(exe, kmt.tobytes() + ulat.tobytes() + w.payload() + np.int32(0).tobytes(), refrun.domain_nml(ew, ns))
+    hdr = r.take(np.int32, (6 if ncat is None else 7,))
+    assert tuple(hdr[:5]) == (nx, ny, bx + 2, by + 2, mxb) and (ncat is None or hdr[6] == ncat), hdr
+    return r, r.take(np.int32, (int(hdr[5]), 4))
 
 
 def put_params(w, p, tilt):
@@ -120,7 +106,7 @@ def single_records(exe, cfg):
             plan += [(f"{pre}/principal_stress/{k}", np.float64, shp) for k in ("sig1", "sig2")]
     r, _ = run(exe, cfg, "cyclic", "open", "none", w)
     out = {k: r.take(dt, s) for k, dt, s in plan}
-    assert r.o == len(r.b)
+    r.done()
     return out
 
 
@@ -195,7 +181,7 @@ def chain_records(exe, cfg, case):
         for k, v in o.items():
             if not k.startswith("_"):
                 out[f"ndte{ndte}/{k}"] = v
-    assert r.o == len(r.b)
+    r.done()
     return d, f, out
 
 
@@ -206,18 +192,18 @@ def save(path, out):
     assert kib < 1024, "fixture over 1 MiB: split it"
 
 
-def main():
+def main(outdir=HERE):
     from tests import test_ref_pins as P
     for cfg in rv.KERNEL_CONFIGS:
         exe = build(cfg)
         out = single_records(exe, cfg)
         P.assert_block_coverage(cfg, out)
         for var in rv.BLOCK_VARIANTS:                # one file per variant: dense random planes do not compress
-            save(os.path.join(HERE, f"ref_dyn_{cfg}.{var}.npz"), {k: v for k, v in out.items() if k.split("/")[1] == var})
+            save(os.path.join(outdir, f"ref_dyn_{cfg}.{var}.npz"), {k: v for k, v in out.items() if k.split("/")[1] == var})
         for case in rv.DYN_CASES:
             d, f, out = chain_records(exe, cfg, case)
             P.assert_chain_coverage(cfg, case, d, f, out)
-            save(os.path.join(HERE, f"ref_dyn_{cfg}.{case}.npz"), out)
+            save(os.path.join(outdir, f"ref_dyn_{cfg}.{case}.npz"), out)
 
 
 if __name__ == "__main__":

@@ -18,17 +18,15 @@ Runs in the build container only; called by make_ref_golden.py, or alone:   pyth
 from __future__ import annotations
 
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-from tests.golden import refvec as rv  # noqa: E402
-from tests.golden.make_ref_golden import Reader, Writer  # noqa: E402
+from tests.golden import refrun, refvec as rv  # noqa: E402
+from tests.golden.refrun import Writer  # noqa: E402
 from tests.golden import make_ref_kernels as mk  # noqa: E402
 
 NG, NV = 6, 4
@@ -57,7 +55,7 @@ def block_records(exe):
             for k in rv.REMAP_BLOCK_GRID:
                 w.arr(q[k])
             plan.append((f"{rec}/{var}", nt))
-    r, _ = run(exe, cfg, "cyclic", "open", "none", w)
+    r, _ = mk.run(exe, cfg, "cyclic", "open", "none", w, ncat=rv.REMAP_NCAT)
     out = {}
     for pre, nt in plan:
         T = lambda *s: r.take(np.float64, s)
@@ -88,27 +86,8 @@ def block_records(exe):
             o["update_fields/mm"] = T(ncp, *shp)
             o["update_fields/tm"] = T(ncp - 1, nt, *shp)
         out.update({f"{pre}/{k}": v for k, v in o.items()})
-    assert r.o == len(r.b)
+    r.done()
     return out
-
-
-def run(exe, cfg, ew, ns, land, w):
-    """as make_ref_kernels.run; ref_remap's header carries ncat as a seventh integer"""
-    nx, ny, bx, by, mxb = rv.KERNEL_CONFIGS[cfg]
-    kmt, ulat = rv.kmt_ulat(nx, ny, bx, by, ew, ns, land)
-    with tempfile.TemporaryDirectory() as td:
-        with open(os.path.join(td, "in.bin"), "wb") as f:
-            f.write(kmt.tobytes() + ulat.tobytes() + b"".join(w.parts) + np.int32(0).tobytes())
-        with open(os.path.join(td, "cice_in.nml"), "w") as f:
-            f.write("&domain_nml\n  nprocs = 1\n  processor_shape = 'slenderX1'\n  distribution_type = 'cartesian'\n"
-                    f"  distribution_wght = 'latitude'\n  ew_boundary_type = '{ew}'\n  ns_boundary_type = '{ns}'\n"
-                    "  maskhalo_dyn = .false.\n  maskhalo_remap = .false.\n  maskhalo_bound = .false.\n/\n")
-        p = subprocess.run([exe, "in.bin", "out.bin"], cwd=td, capture_output=True, text=True)
-        assert p.returncode == 0, p.stdout[-800:] + p.stderr[-800:]
-        r = Reader(open(os.path.join(td, "out.bin"), "rb").read())
-    hdr = r.take(np.int32, (7,))
-    assert tuple(hdr[:5]) == (nx, ny, bx + 2, by + 2, mxb) and hdr[6] == rv.REMAP_NCAT, hdr
-    return r, r.take(np.int32, (int(hdr[5]), 4))
 
 
 def signatures(d, icng, indx, flux, tri, xy):
@@ -166,7 +145,7 @@ def chain(exe, cfg, case, combos, courant=None, stop=None):
             w.arr(mm[n]); w.arr(tm[n])
             for k in rv.REMAP_GRID:
                 w.arr(f[k][n])
-    r, bounds = run(exe, cfg, ew, ns, land, w)
+    r, bounds = mk.run(exe, cfg, ew, ns, land, w, ncat=rv.REMAP_NCAT)
     assert [tuple(x) for x in bounds] == [(b.ilo, b.ihi, b.jlo, b.jhi) for b in d.local_blocks]
     out = {}
     for order, midpt in combos:
@@ -186,7 +165,7 @@ def chain(exe, cfg, case, combos, courant=None, stop=None):
             xy.append(r.take(np.float64, (2, 2, NG, NV) + shp))
         out[f"{pre}/mm"], out[f"{pre}/tm"] = om, ot
         out[f"{pre}/sig"], out[f"{pre}/pat"] = signatures(d, icng, indx, flux, tri, xy)
-    assert r.o == len(r.b)
+    r.done()
     return out
 
 
@@ -200,26 +179,26 @@ def find_courant(exes):
         print(f"courant {c}: {len(bad)} stops", bad[:4])
 
 
-def main():
+def main(outdir=HERE):
     from tests import test_ref_pins as P
     exes = {}
     for cfg in rv.KERNEL_CONFIGS:
         mk.build(cfg)
-        exes[cfg] = os.path.join(ROOT, "oracle", "_ref", cfg, "ref_remap")
+        exes[cfg] = refrun.exe("ref_remap", cfg)
     if "--courant" in sys.argv:
         return find_courant(exes)
     out = block_records(exes[rv.REMAP_BLOCK_CFG])
     for var in rv.REMAP_BLOCK_VARIANTS:
-        mk.save(os.path.join(HERE, f"ref_remap_blk.{var}.npz"), {k: v for k, v in out.items() if k.split("/")[1] == var})
+        mk.save(os.path.join(outdir, f"ref_remap_blk.{var}.npz"), {k: v for k, v in out.items() if k.split("/")[1] == var})
     for cfg, exe in exes.items():
         per_case = {}
         for case, (_, _, combos) in rv.REMAP_CASES.items():
             per_case[case] = chain(exe, cfg, case, combos)
-            mk.save(os.path.join(HERE, f"ref_remap_{cfg}.{case}.npz"), per_case[case])
+            mk.save(os.path.join(outdir, f"ref_remap_{cfg}.{case}.npz"), per_case[case])
         stops = {}
         for name, (_, order, midpt) in rv.REMAP_STOPS.items():
             stops[name] = chain(exe, cfg, "cyclic_open", [(order, midpt)], stop=name)[f"o{order}m{midpt}/stop"]
-        mk.save(os.path.join(HERE, f"ref_remap_{cfg}.stops.npz"), stops)
+        mk.save(os.path.join(outdir, f"ref_remap_{cfg}.stops.npz"), stops)
         P.assert_remap_coverage(cfg, per_case, stops)
 
 

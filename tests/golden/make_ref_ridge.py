@@ -1,4 +1,4 @@
-"""Makes tests/golden/ref_ridge_<cfg>.<case>.npz from the reference's own ridge_ice: oracle/_ref/<cfg>/ref_ridge (oracle/ref/ridge.mk +
+"""Makes tests/golden/ref_ridge_<cfg>.<case>.npz from the reference's own ridge_ice: oracle/_ref/<cfg>/ref_ridge (oracle/ref/Makefile, target ridge +
 oracle/ref/ref_ridge.F90, built by __graft_entry__.build() where the reference is present).  Inputs come from ridgevec; only the
 reference's OUTPUTS are stored, on the listed cells (physical cells with tmask) in (block, j, i) order:
     aice0 (L,)  aicen / vicen / vsnon (L, ncat)  trcrn (L, ncat, ntrcr)  the 2-D diagnostics (L,)  the per-category ones (L, ncat)
@@ -11,9 +11,7 @@ and ref_ridge_stops.npz with the stop records.  The generator asserts what the f
 from __future__ import annotations
 
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -22,61 +20,44 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from tests.golden import ridgevec as rv          # noqa: E402
+from tests.golden import refrun, ridgevec as rv          # noqa: E402
+from tests.golden.refrun import on_cells as on_listed          # noqa: E402,F401
 
 
 def run_reference(cfg, x, sw):
     """one ridge_ice call per block by the reference build of `cfg`; returns dict of full block arrays + per-block scalars"""
-    exe = os.path.join(ROOT, "oracle", "_ref", cfg, "ref_ridge")
     d = x["d"]
     nb, ncat, ntrcr = d.nblocks, x["ncat"], x["ntrcr"]
     kp, kr = sw
     tr = x["tracers"]
-    i32 = lambda *v: np.array(v, dtype=np.int32).tobytes()
-    f64 = lambda *v: np.array(v, dtype=np.float64).tobytes()
-    buf = [i32(1), i32(nb, ntrcr, kp, kr, x["ndtd"]), f64(x["dt"], x["mu_rdg"]), x["hin_max"].astype(np.float64).tobytes(),
-           x["trcr_depend"].tobytes(),
-           i32(*[tr.get(k, 0) for k in ("nt_qsno", "nt_alvl", "nt_vlvl", "nt_apnd", "nt_hpnd", "nt_fbri", "tr_pond_cesm", "tr_pond_lvl",
-                                        "tr_pond_topo")])]
+    w = refrun.Writer()
+    w.i4(1); w.i4(nb, ntrcr, kp, kr, x["ndtd"]); w.r8(x["dt"], x["mu_rdg"]); w.arr(x["hin_max"].astype(np.float64))
+    w.arr(x["trcr_depend"])
+    w.i4(*[tr.get(k, 0) for k in ("nt_qsno", "nt_alvl", "nt_vlvl", "nt_apnd", "nt_hpnd", "nt_fbri", "tr_pond_cesm", "tr_pond_lvl", "tr_pond_topo")])
     for b, (ilo, ihi, jlo, jhi) in enumerate(rv.blocks_of(d)):
-        buf += [i32(ilo, ihi, jlo, jhi), x["tmask"][b].tobytes(), x["rdg_conv"][b].tobytes(), x["rdg_shear"][b].tobytes(),
-                x["aice0"][b].tobytes(), x["aicen"][b].tobytes(), x["vicen"][b].tobytes(), x["vsnon"][b].tobytes(), x["trcrn"][b].tobytes()]
-        buf += [x[k][b].tobytes() for k in rv.DIAG_2D]
-        buf += [x[k][b].tobytes() for k in rv.DIAG_3D]
-    buf.append(i32(0))
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(b"".join(buf))
-        subprocess.check_call([exe, fin, fout], cwd=tmp)
-        raw = open(fout, "rb").read()
-        text = open(fout + ".diag").read().splitlines()
-    pos = 0
-
-    def take(dtype, shape):
-        nonlocal pos
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        a = np.frombuffer(raw, dtype=dtype, count=int(np.prod(shape)), offset=pos).reshape(shape).copy()
-        pos += n
-        return a
-    nxb, nyb, nc = take(np.int32, (3,))
+        w.i4(ilo, ihi, jlo, jhi)
+        for k in ["tmask", "rdg_conv", "rdg_shear", "aice0", "aicen", "vicen", "vsnon", "trcrn"] + rv.DIAG_2D + rv.DIAG_3D:
+            w.arr(x[k][b])
+    w.i4(0)
+    r, text = refrun.run(refrun.exe("ref_ridge", cfg), w.payload())
+    nxb, nyb, nc = r.take(np.int32, (3,))
     assert (nxb, nyb, nc) == (d.nx_block, d.ny_block, ncat), (nxb, nyb, nc)
     out = {k: np.zeros_like(x[k]) for k in rv.STATE + rv.DIAG_2D + rv.DIAG_3D}
     sc = np.zeros((nb, 4), dtype=np.int32)
     for b in range(nb):
-        sc[b] = take(np.int32, (4,))
-        out["aice0"][b] = take(np.float64, (nyb, nxb))
+        sc[b] = r.take(np.int32, (4,))
+        out["aice0"][b] = r.take(np.float64, (nyb, nxb))
         for k in ("aicen", "vicen", "vsnon"):
-            out[k][b] = take(np.float64, (ncat, nyb, nxb))
-        out["trcrn"][b] = take(np.float64, (ncat, ntrcr, nyb, nxb))
+            out[k][b] = r.take(np.float64, (ncat, nyb, nxb))
+        out["trcrn"][b] = r.take(np.float64, (ncat, ntrcr, nyb, nxb))
         for k in rv.DIAG_2D:
-            out[k][b] = take(np.float64, (nyb, nxb))
+            out[k][b] = r.take(np.float64, (nyb, nxb))
         for k in rv.DIAG_3D:
-            out[k][b] = take(np.float64, (ncat, nyb, nxb))
-    assert pos == len(raw)
+            out[k][b] = r.take(np.float64, (ncat, nyb, nxb))
+    r.done()
     repeats = np.zeros(nb, dtype=np.int32)
     cur = -1
-    for line in text:
+    for line in text.splitlines():
         w = line.split()
         if w[:1] == ["BLOCK"]:
             cur = int(w[1]) - 1
@@ -84,13 +65,6 @@ def run_reference(cfg, x, sw):
             repeats[cur] += 1
     out.update(l_stop=sc[:, 0].copy(), istop=sc[:, 1].copy(), jstop=sc[:, 2].copy(), icells=sc[:, 3].copy(), repeats=repeats)
     return out
-
-
-def on_listed(a, m):
-    """values of a block array on the listed cells, (block, j, i) order, the category / tracer axes last"""
-    if a.ndim == 3:
-        return a[m]
-    return np.moveaxis(a, (0, -2, -1), (0, 1, 2))[m]
 
 
 def restate(x, sw, exp=None, per_cell_iteration=False):
@@ -105,7 +79,7 @@ def restate(x, sw, exp=None, per_cell_iteration=False):
     return y, res, stop
 
 
-def main():
+def main(outdir=HERE):
     seen = dict(repeat=0, norepeat=0, conv_in_repeat=0, tmpfac0=0, tmpfacn=0, clamp=0, raft1=0, raft0=0)
     for cfg, recs in rv.RECORDS.items():
         for tcase, swn in recs:
@@ -142,7 +116,7 @@ def main():
             print(f"{cfg}.{tcase}_{swn}: restatement (libm exp) vs reference: max rel diff {worst:.3e}; repeats per block {ref['repeats'].tolist()}")
             rec = {k: on_listed(ref[k], m) for k in rv.STATE + rv.DIAG_2D + rv.DIAG_3D}
             rec.update({k: ref[k] for k in ("l_stop", "istop", "jstop", "icells", "repeats")})
-            np.savez_compressed(os.path.join(HERE, f"ref_ridge_{cfg}.{rv.record_name(tcase, swn)}.npz"), **rec)
+            np.savez_compressed(os.path.join(outdir, f"ref_ridge_{cfg}.{rv.record_name(tcase, swn)}.npz"), **rec)
     print(seen)
     # what the fixtures must contain (ISSUE: block-wide iteration, both reductions, the round-off clamp, both values of mraftn)
     assert seen["repeat"] >= 1 and seen["norepeat"] >= 1, seen
@@ -158,7 +132,7 @@ def main():
         assert st == (rv.STOPS[name]["reason"], 1, int(ref["istop"][0]), int(ref["jstop"][0])), (name, st, ref["istop"], ref["jstop"])
         stops[name] = np.array([ref["l_stop"][0], ref["istop"][0], ref["jstop"][0]], dtype=np.int32)
         print("stop", name, stops[name])
-    np.savez_compressed(os.path.join(HERE, "ref_ridge_stops.npz"), **stops)
+    np.savez_compressed(os.path.join(outdir, "ref_ridge_stops.npz"), **stops)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """Makes tests/golden/ref_litd_<cfg>.<case>.npz and ref_therm2_<cfg>.<case>.npz from the reference's own linear_itd, add_new_ice,
-lateral_melt, reduce_area, aggregate_area and cleanup_itd: oracle/_ref/<build>/ref_therm2 (oracle/ref/therm2.mk +
+lateral_melt, reduce_area, aggregate_area and cleanup_itd: oracle/_ref/<build>/ref_therm2 (oracle/ref/Makefile, target therm2 +
 oracle/ref/ref_therm2.F90, built by __graft_entry__.build() where the reference is present).  Inputs come from litdvec.litd_input,
 therm2vec.therm2_input and therm2vec.stop_input; only the reference's OUTPUTS are stored, on the physical ocean cells in (block, j, i)
 order, the category / tracer axes last:
@@ -32,9 +32,7 @@ from __future__ import annotations
 
 import hashlib
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -46,11 +44,11 @@ if ROOT not in sys.path:
 from tests.golden import itdvec as iv          # noqa: E402
 from tests.golden import litdvec as lv         # noqa: E402
 from tests.golden import therm2vec as tv       # noqa: E402
+from tests.golden import refrun                # noqa: E402
+from tests.golden.refrun import IDX, Writer, bits, on_cells, padded, same          # noqa: E402,F401
 
 BCASE = "cyclic_open"
 REF_CP_OCN = 3989.24495292815
-IDX = ("nt_Tsfc", "nt_qice", "nt_qsno", "nt_sice", "nt_alvl", "nt_vlvl", "nt_apnd", "nt_hpnd", "nt_fbri", "nt_iage", "nt_FY", "tr_pond_cesm",
-       "tr_pond_lvl", "tr_pond_topo", "tr_brine")
 W_OUT = ["aice0", "aice", "frazil", "frz_onset", "meltl", "fpond", "fresh", "fsalt", "fhocn"]
 W_IN = W_OUT + ["frain", "frzmlt", "Tf", "sss", "rside"]
 L_OUT = iv.STATE + ["aice", "aice0", "fpond"]
@@ -74,13 +72,13 @@ def build_of(cfg, ncat):
     return cfg if ncat == 5 else f"{cfg}_ncat{ncat}"
 
 
-def l_path(cfg, tcase, ncat):
-    return os.path.join(HERE, f"ref_litd_{cfg}.{tcase}{'' if ncat == 5 else f'_ncat{ncat}'}.npz")
+def l_path(cfg, tcase, ncat, outdir=HERE):
+    return os.path.join(outdir, f"ref_litd_{cfg}.{tcase}{'' if ncat == 5 else f'_ncat{ncat}'}.npz")
 
 
-def t_path(cfg, tcase, ncat, kitd, ktherm, ocnf):
+def t_path(cfg, tcase, ncat, kitd, ktherm, ocnf, outdir=HERE):
     tag = f"{tcase}_k{ktherm}" + ("_ocnf" if ocnf else "") + ("" if kitd == 1 or ncat == 1 else "_kitd0") + ("" if ncat == 5 else f"_ncat{ncat}")
-    return os.path.join(HERE, f"ref_therm2_{cfg}.{tag}.npz")
+    return os.path.join(outdir, f"ref_therm2_{cfg}.{tag}.npz")
 
 
 def t_input(cfg, tcase, ncat=5, stop=False):
@@ -93,93 +91,53 @@ def run_reference(x, mode, kitd=1, ktherm=1, ocnf=False):
     """the driver on one input: (list of per-stage dicts of full block arrays, st (nb, 3, nstage), hin_top)"""
     cfg, d = x["cfg"], x["d"]
     ncat, ntrcr = x["ncat"], x["ntrcr"]
-    exe = os.path.join(ROOT, "oracle", "_ref", build_of(cfg, ncat), "ref_therm2")
     _, _, _, _, mxb = lv.CONFIGS[cfg]
     nb, ny, nx = d.nblocks, d.ny_block, d.nx_block
     ew, ns, _ = iv.BOUNDS[BCASE]
     kmt, ulat = iv.refvec.kmt_ulat(*lv.CONFIGS[cfg][:4], ew, ns, iv.BOUNDS[BCASE][2])
     tr = x["tracers"]
-    i32 = lambda *v: np.array(v, dtype=np.int32).tobytes()
-    f64 = lambda *v: np.array(v, dtype=np.float64).tobytes()
-
-    def padded(a, shape_tail):
-        out = np.zeros((mxb,) + shape_tail, dtype=a.dtype)
-        out[:nb] = a
-        return out.tobytes()
     t20 = np.zeros((mxb, ncat, iv.MAX_NTRCR, ny, nx))
     t20[:nb, :, :ntrcr] = x["trcrn"]
-    buf = [kmt.astype(np.float64).tobytes(), ulat.astype(np.float64).tobytes(), i32(mode), i32(ntrcr), i32(*[tr.get(k, 0) for k in IDX]),
-           i32(kitd, ktherm, int(ocnf)),
-           f64(x["dt"], x["k"]["Tocnfrz"], x["hi_min"], x.get("yday", 0.0), x.get("phi_init", 0.75), x.get("dSin0_frazil", 3.0)),
-           x["hin_max"].astype(np.float64).tobytes(), x["trcr_depend"].astype(np.int32).tobytes(), x["tmask"].astype(np.int32).tobytes()]
-    buf += [padded(x[k], (ncat, ny, nx)) for k in ("aicen_init", "vicen_init", "aicen", "vicen", "vsnon")]
-    buf.append(t20.tobytes())
-    w = np.zeros((len(W_IN), mxb, ny, nx))
-    for q, k in enumerate(W_IN):
-        if x.get(k) is not None:
-            w[q, :nb] = x[k]
+    w = Writer()
+    w.arr(kmt.astype(np.float64)); w.arr(ulat.astype(np.float64)); w.i4(mode); w.i4(ntrcr); w.i4(*[tr.get(k, 0) for k in IDX])
+    w.i4(kitd, ktherm, int(ocnf))
+    w.r8(x["dt"], x["k"]["Tocnfrz"], x["hi_min"], x.get("yday", 0.0), x.get("phi_init", 0.75), x.get("dSin0_frazil", 3.0))
+    w.arr(x["hin_max"].astype(np.float64)); w.arr(x["trcr_depend"].astype(np.int32)); w.arr(x["tmask"].astype(np.int32))
+    for k in ("aicen_init", "vicen_init", "aicen", "vicen", "vsnon"):
+        w.arr(padded(x[k], mxb))
+    w.arr(t20)
+    for k in W_IN:
+        w.arr(padded(x[k], mxb) if x.get(k) is not None else np.zeros((mxb, ny, nx)))
     sal = x.get("salinz")
-    buf += [w.tobytes(), padded(sal if sal is not None else np.zeros((nb, iv.NILYR + 1, ny, nx)), (iv.NILYR + 1, ny, nx)),
-            padded(x["first_ice"].astype(np.int32), (ncat, ny, nx)), i32(0)]
-    with tempfile.TemporaryDirectory() as tmp:
-        with open(os.path.join(tmp, "in.bin"), "wb") as f:
-            f.write(b"".join(buf))
-        with open(os.path.join(tmp, "cice_in.nml"), "w") as f:
-            f.write("&domain_nml\n  nprocs = 1\n  processor_shape = 'slenderX1'\n  distribution_type = 'cartesian'\n"
-                    "  distribution_wght = 'latitude'\n"
-                    f"  ew_boundary_type = '{ew}'\n  ns_boundary_type = '{ns}'\n"
-                    "  maskhalo_dyn = .false.\n  maskhalo_remap = .false.\n  maskhalo_bound = .false.\n/\n")
-        p = subprocess.run([exe, "in.bin", "out.bin"], cwd=tmp, capture_output=True, text=True)
-        assert p.returncode == 0, p.stdout[-600:] + p.stderr[-600:]
-        raw = open(os.path.join(tmp, "out.bin"), "rb").read()
-    pos = 0
-
-    def take(dtype, shape):
-        nonlocal pos
-        a = np.frombuffer(raw, dtype=dtype, count=int(np.prod(shape)), offset=pos).reshape(shape).copy()
-        pos += a.nbytes
-        return a
-    hdr = take(np.int32, (8,))
+    w.arr(padded(sal if sal is not None else np.zeros((nb, iv.NILYR + 1, ny, nx)), mxb))
+    w.arr(padded(x["first_ice"].astype(np.int32), mxb)); w.i4(0)
+    r, _ = refrun.run(refrun.exe("ref_therm2", build_of(cfg, ncat)), w.payload(), refrun.domain_nml(ew, ns))
+    hdr = r.take(np.int32, (8,))
     assert tuple(hdr) == (nx, ny, ncat, iv.MAX_NTRCR, mxb, nb, iv.NILYR, 0), hdr            # (the last: pop_icediag = .false.)
-    blk = take(np.int32, (nb, 4))
+    blk = r.take(np.int32, (nb, 4))
     assert [tuple(r) for r in blk] == iv.blocks_of(d)
     k = x["k"]
-    const = take(np.float64, (10,))
+    const = r.take(np.float64, (10,))
     want = [k["rhoi"], k["rhos"], x.get("rhow", 1026.0), k["Lfresh"], k["cp_ice"], x.get("cp_ocn", REF_CP_OCN), k["ice_ref_salinity"], k["puny"],
             x.get("hfrazilmin", 0.05), k["hs_min"]]
     assert list(const) == want, (list(const), want)                                          # the reference's compile-time constants
-    nstage = int(take(np.int32, (1,))[0])
+    nstage = int(r.take(np.int32, (1,))[0])
     assert nstage == (1 if mode == 1 else 4)
-    st = np.moveaxis(take(np.int32, (nstage, nb, 3)), 0, -1)                                 # (nb, 3, nstage)
-    hin_top = float(take(np.float64, (1,))[0])
+    st = np.moveaxis(r.take(np.int32, (nstage, nb, 3)), 0, -1)                                 # (nb, 3, nstage)
+    hin_top = float(r.take(np.float64, (1,))[0])
     out = []
     for s in range(nstage):
         one = {}
         for q in ("aicen", "vicen", "vsnon"):
-            one[q] = take(np.float64, (mxb, ncat, ny, nx))[:nb]
-        one["trcrn"] = np.ascontiguousarray(take(np.float64, (mxb, ncat, iv.MAX_NTRCR, ny, nx))[:nb, :, :ntrcr])
-        w = take(np.float64, (len(W_OUT), mxb, ny, nx))
+            one[q] = r.take(np.float64, (mxb, ncat, ny, nx))[:nb]
+        one["trcrn"] = np.ascontiguousarray(r.take(np.float64, (mxb, ncat, iv.MAX_NTRCR, ny, nx))[:nb, :, :ntrcr])
+        w = r.take(np.float64, (len(W_OUT), mxb, ny, nx))
         for q, name in enumerate(W_OUT):
             one[name] = w[q, :nb].copy()
-        one["first_ice"] = take(np.int32, (mxb, ncat, ny, nx))[:nb]
+        one["first_ice"] = r.take(np.int32, (mxb, ncat, ny, nx))[:nb]
         out.append(one)
-    assert pos == len(raw), (pos, len(raw))
+    r.done()
     return out, st, hin_top
-
-
-def on_cells(a, m):
-    """values of a block array on the cells of mask m (nb, ny, nx), (block, j, i) order, the category / tracer axes last"""
-    if a.ndim == 3:
-        return a[m]
-    return np.moveaxis(a, (0, -2, -1), (0, 1, 2))[m]
-
-
-def same(a, b):
-    return a.shape == b.shape and bool(((a == b) | (np.isnan(a) & np.isnan(b))).all()) if a.dtype.kind == "f" else np.array_equal(a, b)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64) if a.dtype == np.float64 else np.ascontiguousarray(a)
 
 
 def check_departures(x, stages, keys2d):
@@ -306,7 +264,7 @@ def coverage(seen_l, seen_t):
     return missing
 
 
-def main():
+def main(outdir=HERE):
     from tests import nplitd, nptherm2
     seen_l = {k: 0 for k in nplitd.INFO_KEYS}
     for cfg, tcase, ncat in L_RECORDS:
@@ -323,7 +281,7 @@ def main():
         for i in infos:
             for k in seen_l:
                 seen_l[k] += i[k]
-        path = l_path(cfg, tcase, ncat)
+        path = l_path(cfg, tcase, ncat, outdir)
         np.savez_compressed(path, **rec)
         print(f"   {os.path.getsize(path) / 1024:.0f} KiB")
     print(seen_l)
@@ -342,7 +300,7 @@ def main():
         for i in infos:
             for k in seen_t[ktherm]:
                 seen_t[ktherm][k] += i[k]
-        path = t_path(cfg, tcase, ncat, kitd, ktherm, ocnf)
+        path = t_path(cfg, tcase, ncat, kitd, ktherm, ocnf, outdir)
         np.savez_compressed(path, **rec)
         print(f"   {os.path.getsize(path) / 1024:.0f} KiB")
     print(seen_t)
@@ -355,7 +313,7 @@ def main():
     print("stop: reference blocks", blocks + 1, "stages", [STAGES[s] for s in np.nonzero(st[b, 0])[0]], "cell", st[b, 1:, 3])
     assert not st[:, 0, :3].any() and st[b, 0, 3] == 1
     assert (b + 1, int(st[b, 1, 3]), int(st[b, 2, 3])) == x["stop_expect"][1:]
-    np.savez_compressed(os.path.join(HERE, "ref_therm2_stop.npz"), stop=st.astype(np.int32))
+    np.savez_compressed(os.path.join(outdir, "ref_therm2_stop.npz"), stop=st.astype(np.int32))
 
 
 if __name__ == "__main__":

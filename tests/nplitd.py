@@ -4,7 +4,7 @@ loop and operation order, with p333 = c1 / c3 and p666 = c2 / c3 as ice_constant
 tests/npitd.py's, which tests/test_itd_ref.py holds bit for bit to the reference's own output (one boundary per call there; here all
 ncat - 1 boundaries go into one call).  fit_line, the boundary integrals and the whole call are PINNED to reference-built output:
 tests/test_therm2_ref.py holds this file bit for bit to the records of the reference's own compiled linear_itd
-(tests/golden/ref_litd_*.npz, made by tests/golden/make_ref_therm2.py from oracle/ref/therm2.mk).
+(tests/golden/ref_litd_*.npz, made by tests/golden/make_ref_therm2.py from oracle/ref/Makefile, target therm2).
 
 The l_conservation_check blocks (compile-time .false.) are left out.  Stated departures, shared with evpk_linear_itd (include/evpk.h):
 the cell list takes physical cells with tmask and aice > puny; a boundary left with donor = 0 and daice > 0 (a negative vicen under

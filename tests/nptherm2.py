@@ -6,7 +6,7 @@ the layer loop where the Fortran has it) and its operation order per cell.  line
 
 PINNED to reference-built output: add_new_ice, update_vertical_tracers, the mushy liquidus, lateral_melt, reduce_area and the chain of
 step_therm2 equal the records of the reference's own compiled routines bit for bit, stage by stage (tests/golden/ref_therm2_*.npz, made
-by tests/golden/make_ref_therm2.py from oracle/ref/therm2.mk; tests/test_therm2_ref.py).  What stays unpinned: step_therm2's call order
+by tests/golden/make_ref_therm2.py from oracle/ref/Makefile, target therm2; tests/test_therm2_ref.py).  What stays unpinned: step_therm2's call order
 (the driver oracle/ref/ref_therm2.F90 restates it), a horizontally non-uniform salinz (the departure below), aerosols / bgc, and
 l_conservation_check = .true.
 
