@@ -37,6 +37,7 @@
 #include "evpk_therm1.hip"
 #include "evpk_therm1s.hip"
 #include "evpk_rad.hip"
+#include "evpk_dedd.hip"
 #include "evpk_eap.hip"
 
 using namespace evpk;
@@ -4682,6 +4683,90 @@ extern "C" int evpk_prep_radiation(evpk_ctx *c, const evpk_prep_rad_args *a) {
         hipLaunchKernelGGL((k_prep_radiation<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
     HIPCHK(c, hipGetLastError());
     return stage_out(c, arr);
+}
+
+// ---- step_radiation on its Delta-Eddington branch (source/ice_step_mod.F90:1408-1451: run_dEdd, source/ice_shortwave.F90:1251-1577) with
+// the albedo lines of coupling_prep: one launch (kernel in evpk_dedd.hip) ----
+extern "C" int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a) {
+    if (!c) return 1;
+    RANKS_ENTRY(c, "evpk_step_radiation_dedd");
+    const char *who = "evpk_step_radiation_dedd";
+    if (!a) FAIL(c, "%s: a required argument is missing", who);
+    const evpk_itd_tracers &t = a->t;
+    const bool cesm = a->tr_pond_cesm || t.tr_pond_cesm;
+    if (a->calc_Tsfc != 1) FAIL(c, "%s: calc_Tsfc = .false. is not supported", who);
+    if (a->heat_capacity != 1) FAIL(c, "%s: heat_capacity = .false. (zero-layer) is not supported", who);
+    if (a->tr_aero) FAIL(c, "%s: aerosol tracers (tr_aero) are not supported", who);
+    if (a->tr_pond_lvl || t.tr_pond_lvl) FAIL(c, "%s: tr_pond_lvl (dhsn, ffracn) is not supported", who);
+    if (a->tr_pond_topo || t.tr_pond_topo) FAIL(c, "%s: tr_pond_topo is not supported", who);
+    if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->swvdr || !a->swvdf || !a->swidr || !a->swidf || !a->coszen || !a->alvdrn ||
+        !a->alidrn || !a->alvdfn || !a->alidfn || !a->albicen || !a->albsnon || !a->fswsfcn || !a->fswintn || !a->fswthrun || !a->Sswabsn ||
+        !a->Iswabsn || !a->alvdr || !a->alidr || !a->alvdf || !a->alidf || !a->albice || !a->albsno || !a->scale_factor || !a->albpndn ||
+        !a->apeffn || !a->snowfracn || !a->albpnd || !a->apeff_ai)
+        FAIL(c, "%s: a required argument is missing", who);
+    if (t.nilyr < 1 || t.nslyr < 1 || t.nilyr > DEDD_MAXL || t.nslyr > DEDD_MAXL)
+        FAIL(c, "%s: nilyr = %d, nslyr = %d not in 1..%d", who, t.nilyr, t.nslyr, DEDD_MAXL);
+    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, a->ncat, MAXCAT);
+    if (a->ntrcr < 1 || a->ntrcr_dim < a->ntrcr || t.nt_Tsfc < 1 || t.nt_Tsfc > a->ntrcr)
+        FAIL(c, "%s: nt_Tsfc = %d lies beyond ntrcr = %d (ntrcr_dim = %d)", who, t.nt_Tsfc, a->ntrcr, a->ntrcr_dim);
+    if (cesm && (t.nt_apnd < 1 || t.nt_hpnd < 1 || t.nt_apnd > a->ntrcr || t.nt_hpnd > a->ntrcr))
+        FAIL(c, "%s: tr_pond_cesm without nt_apnd / nt_hpnd in 1..ntrcr = %d", who, a->ntrcr);
+    if (a->puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->puny);
+    if (!(a->dT_mlt > 0.0)) FAIL(c, "%s: dT_mlt = %g", who, a->dT_mlt);
+    if (!c->nblocks) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    DeddArgs A{};
+    A.ncat = a->ncat; A.ntrcr_dim = a->ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nilyr = t.nilyr; A.nslyr = t.nslyr; A.nt_Tsfc = t.nt_Tsfc;
+    A.nt_apnd = t.nt_apnd; A.nt_hpnd = t.nt_hpnd; A.tr_pond_cesm = cesm ? 1 : 0;
+    A.puny = a->puny; A.rhos = c->p.rhos; A.R_snw = a->R_snw; A.dT_mlt = a->dT_mlt; A.rsnw_mlt = a->rsnw_mlt; A.kalg = a->kalg; A.hs0 = a->hs0;
+    A.pndaspect = a->pndaspect; A.awtvdr = a->awtvdr; A.awtidr = a->awtidr; A.awtvdf = a->awtvdf; A.awtidf = a->awtidf;
+    dedd_iops(a->R_ice, a->R_pnd, A.iop);
+    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
+    std::vector<HostArr> arr = {            // (every output is written on every cell: none is copied up; coszen is in / out)
+        {a->aicen, n3, &A.aicen, false}, {a->vicen, n3, &A.vicen, false}, {a->vsnon, n3, &A.vsnon, false}, {a->trcrn, n3 * a->ntrcr_dim, &A.trcrn, false},
+        {a->swvdr, N, &A.swvdr, false}, {a->swvdf, N, &A.swvdf, false}, {a->swidr, N, &A.swidr, false}, {a->swidf, N, &A.swidf, false},
+        {a->coszen, N, &A.coszen, true},
+        {a->alvdrn, n3, &A.alvdrn, true, false}, {a->alidrn, n3, &A.alidrn, true, false}, {a->alvdfn, n3, &A.alvdfn, true, false},
+        {a->alidfn, n3, &A.alidfn, true, false}, {a->albicen, n3, &A.albicen, true, false}, {a->albsnon, n3, &A.albsnon, true, false},
+        {a->albpndn, n3, &A.albpndn, true, false}, {a->apeffn, n3, &A.apeffn, true, false}, {a->snowfracn, n3, &A.snowfracn, true, false},
+        {a->fswsfcn, n3, &A.fswsfcn, true, false}, {a->fswintn, n3, &A.fswintn, true, false}, {a->fswthrun, n3, &A.fswthrun, true, false},
+        {a->Sswabsn, n3 * t.nslyr, &A.Sswabsn, true, false}, {a->Iswabsn, n3 * t.nilyr, &A.Iswabsn, true, false},
+        {a->fswpenln, n3 * (t.nilyr + 1), &A.fswpenln, true, false},
+        {a->alvdr, N, &A.alvdr, true, false}, {a->alidr, N, &A.alidr, true, false}, {a->alvdf, N, &A.alvdf, true, false},
+        {a->alidf, N, &A.alidf, true, false}, {a->albice, N, &A.albice, true, false}, {a->albsno, N, &A.albsno, true, false},
+        {a->albpnd, N, &A.albpnd, true, false}, {a->apeff_ai, N, &A.apeff_ai, true, false}, {a->scale_factor, N, &A.scale_factor, true, false}};
+    if (stage_in(c, arr, true)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
+    const dim3 b(64), g = block_grid(c);
+    if (a->ncat == 5 && t.nilyr == 4 && t.nslyr == 1)
+        hipLaunchKernelGGL((k_shortwave_dedd<5, 4, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    else
+        hipLaunchKernelGGL((k_shortwave_dedd<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    HIPCHK(c, hipGetLastError());
+    return stage_out(c, arr);
+}
+
+// the tables of evpk_dedd_tables.h by name (no context, no device): out[0 .. n), n the table's length; 1 for an unknown name or another n
+extern "C" int evpk_dedd_table(const char *name, double *out, int32_t n) {
+    using namespace dedd;
+    if (!name || !out) return 1;
+    struct Tab { const char *name; const double *p; int n; };
+    const Tab tabs[] = {{"rsnw_tab", rsnw_tab, NMBRAD}, {"Qs_tab", &Qs_tab[0][0], NSPINT * NMBRAD}, {"ws_tab", &ws_tab[0][0], NSPINT * NMBRAD},
+                        {"gs_tab", &gs_tab[0][0], NSPINT * NMBRAD},
+                        {"ki_ssl_mn", ki_ssl_mn, NSPINT}, {"wi_ssl_mn", wi_ssl_mn, NSPINT}, {"gi_ssl_mn", gi_ssl_mn, NSPINT},
+                        {"ki_dl_mn", ki_dl_mn, NSPINT}, {"wi_dl_mn", wi_dl_mn, NSPINT}, {"gi_dl_mn", gi_dl_mn, NSPINT},
+                        {"ki_int_mn", ki_int_mn, NSPINT}, {"wi_int_mn", wi_int_mn, NSPINT}, {"gi_int_mn", gi_int_mn, NSPINT},
+                        {"ki_p_ssl_mn", ki_p_ssl_mn, NSPINT}, {"wi_p_ssl_mn", wi_p_ssl_mn, NSPINT}, {"gi_p_ssl_mn", gi_p_ssl_mn, NSPINT},
+                        {"ki_p_int_mn", ki_p_int_mn, NSPINT}, {"wi_p_int_mn", wi_p_int_mn, NSPINT}, {"gi_p_int_mn", gi_p_int_mn, NSPINT},
+                        {"kw", kw, NSPINT}, {"ww", ww, NSPINT}, {"gw", gw, NSPINT}, {"gauspt", gauspt, NGMAX}, {"gauswt", gauswt, NGMAX},
+                        {"scalars", scalars, NSCALARS}};
+    for (const Tab &t : tabs)
+        if (!strcmp(name, t.name)) {
+            if (n != t.n) return 1;
+            for (int q = 0; q < n; q++) out[q] = t.p[q];
+            return 0;
+        }
+    return 1;
 }
 
 extern "C" int evpk_calibrate(evpk_ctx *c, int32_t nrep) {

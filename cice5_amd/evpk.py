@@ -99,7 +99,7 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
            "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics", "evpk_linear_itd",
            "evpk_new_ice_lateral_melt", "evpk_step_therm2", "evpk_thermo_vertical", "evpk_step_therm1", "evpk_step_radiation",
-           "evpk_prep_radiation"]
+           "evpk_prep_radiation", "evpk_step_radiation_dedd", "evpk_dedd_table"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -234,6 +234,40 @@ class PrepRadArgs(ct.Structure):
                 [(n, c_f64p) for n in PREP_RAD_IN + PREP_RAD_INOUT] + [("fswfac", c_f64p)])
 
 
+DEDD_FLAGS = ["calc_Tsfc", "heat_capacity", "tr_pond_cesm", "tr_pond_lvl", "tr_pond_topo", "tr_aero"]
+DEDD_SCALARS = ["R_ice", "R_pnd", "R_snw", "dT_mlt", "rsnw_mlt", "kalg", "hs0", "pndaspect", "awtvdr", "awtidr", "awtvdf", "awtidf"]
+DEDD_STATE = ["aicen", "vicen", "vsnon", "trcrn"]
+DEDD_FORCING = ["swvdr", "swvdf", "swidr", "swidf"]
+DEDD_OUT = RAD_OUT + ["albpndn", "apeffn", "snowfracn"]                              # (nb, ncat, ny, nx)
+DEDD_OUT_LAYERS = RAD_OUT_LAYERS
+DEDD_OUT2D = [n for n in RAD_OUT2D if n != "coszen"] + ["albpnd", "apeff_ai"]        # coszen is in / out
+# the reference's namelist defaults (source/ice_init.F90:289-304: R_ice, R_pnd, R_snw, dT_mlt, rsnw_mlt, kalg, hs0, pndaspect; :318-321 awt*)
+DEDD_DEFAULTS = dict(R_ice=0.0, R_pnd=0.0, R_snw=1.5, dT_mlt=1.5, rsnw_mlt=1500.0, kalg=0.60, hs0=0.03, pndaspect=0.8,
+                     awtvdr=0.00318, awtidr=0.00182, awtvdf=0.63282, awtidf=0.36218)
+DEDD_TABLES = dict(rsnw_tab=32, Qs_tab=96, ws_tab=96, gs_tab=96, ki_ssl_mn=3, wi_ssl_mn=3, gi_ssl_mn=3, ki_dl_mn=3, wi_dl_mn=3, gi_dl_mn=3,
+                   ki_int_mn=3, wi_int_mn=3, gi_int_mn=3, ki_p_ssl_mn=3, wi_p_ssl_mn=3, gi_p_ssl_mn=3, ki_p_int_mn=3, wi_p_int_mn=3,
+                   gi_p_int_mn=3, kw=3, ww=3, gw=3, gauspt=8, gauswt=8, scalars=28)
+DEDD_SCALAR_NAMES = ["hi_ssl", "hs_ssl", "hpmin", "hp0", "hs_min", "Timelt", "rsnw_fresh", "rsnw_nonmelt", "rsnw_sig", "dT_pnd", "pnd_fac",
+                     "cp67", "cp78", "cp01", "rhoi", "fr_max", "fr_min", "fp_ice", "fm_ice", "fp_pnd", "fm_pnd", "trmin", "refindx", "cp063",
+                     "cp455", "exp_min", "ssl_div", "alg_depth"]
+
+
+class DeddArgs(ct.Structure):
+    """evpk_dedd_args (include/evpk.h), member for member"""
+    _fields_ = ([(n, ct.c_int32) for n in DEDD_FLAGS] + [("ncat", ct.c_int32), ("ntrcr", ct.c_int32), ("ntrcr_dim", ct.c_int32),
+                                                        ("t", ItdTracers), ("puny", ct.c_double)] +
+                [(n, ct.c_double) for n in DEDD_SCALARS] + [(n, c_f64p) for n in DEDD_STATE + DEDD_FORCING + ["coszen"] + RAD_OUT + RAD_OUT_LAYERS] +
+                [(n, c_f64p) for n in RAD_OUT2D if n != "coszen"] + [(n, c_f64p) for n in ("albpndn", "apeffn", "snowfracn", "albpnd", "apeff_ai")])
+
+
+def dedd_table(name: str) -> np.ndarray:
+    """evpk_dedd_table: one table of csrc/evpk_dedd_tables.h as the library holds it (the snow tables [band][radius], flattened)"""
+    out = np.zeros(DEDD_TABLES[name])
+    if lib().evpk_dedd_table(name.encode(), _p64(out), out.size):
+        raise EvpkError(f"evpk_dedd_table: no table {name!r} of {out.size} numbers")
+    return out
+
+
 def remap_tracer_tables(trcr_depend):
     """tracer_type, depend, has_dependents of transport_remap as init_transport builds them from trcr_depend
     (ice_transport_driver.F90:90-118): hice and hsno first (type 1, no parent); a tracer of the area is type 1, one that hangs on a
@@ -321,6 +355,8 @@ def lib():
         L.evpk_step_therm1.argtypes = [ctxp, ct.POINTER(Therm1Args), c_i32p]
         L.evpk_step_radiation.argtypes = [ctxp, ct.POINTER(RadArgs)]
         L.evpk_prep_radiation.argtypes = [ctxp, ct.POINTER(PrepRadArgs)]
+        L.evpk_step_radiation_dedd.argtypes = [ctxp, ct.POINTER(DeddArgs)]
+        L.evpk_dedd_table.argtypes = [ct.c_char_p, c_f64p, ct.c_int32]
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -881,6 +917,34 @@ class Context:
             for n in names:
                 setattr(a, n, _p64(src.get(n)))
         self._chk(self._L.evpk_step_radiation(self._ctx, ct.byref(a)), "evpk_step_radiation")
+
+    def step_radiation_dedd(self, state, forcing, coszen, out, ntrcr: int, tracers, calc_Tsfc=True, heat_capacity=True, tr_aero=False,
+                            puny=1.0e-11, **scalars):
+        """evpk_step_radiation_dedd: step_radiation on its Delta-Eddington branch (run_dEdd) and the albedo lines of coupling_prep in one
+        launch.  state: dict of DEDD_STATE -- aicen / vicen / vsnon (nb, ncat, ny, nx), trcrn (nb, ncat, ntrcr_dim, ny, nx), read only;
+        forcing: dict of DEDD_FORCING (nb, ny, nx); coszen (nb, ny, nx): what compute_coszen made, in / out -- max(puny, coszen) is stored
+        on the listed, lit cells; out: dict of DEDD_OUT (nb, ncat, ny, nx), DEDD_OUT_LAYERS (Sswabsn (nb, ncat, nslyr, ny, nx), Iswabsn
+        (nb, ncat, nilyr, ny, nx), fswpenln (nb, ncat, nilyr + 1, ny, nx), which may be absent) and DEDD_OUT2D (nb, ny, nx), all written
+        on every cell.  tracers: dict with nt_Tsfc, nilyr, nslyr and, with tr_pond_cesm, nt_apnd, nt_hpnd; scalars: any of DEDD_SCALARS
+        (the rest take DEDD_DEFAULTS, the reference's namelist defaults).  Raises on a refusal, which leaves every array untouched."""
+        a = DeddArgs()
+        a.calc_Tsfc, a.heat_capacity, a.tr_aero = int(bool(calc_Tsfc)), int(bool(heat_capacity)), int(bool(tr_aero))
+        a.tr_pond_cesm, a.tr_pond_lvl, a.tr_pond_topo = (int(bool(tracers.get(k, 0))) for k in ("tr_pond_cesm", "tr_pond_lvl", "tr_pond_topo"))
+        aicen, trcrn = state.get("aicen"), state.get("trcrn")
+        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
+        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
+        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        a.puny = float(puny)
+        unknown = set(scalars) - set(DEDD_SCALARS)
+        if unknown:
+            raise TypeError(f"step_radiation_dedd: unknown arguments {sorted(unknown)}")
+        for n in DEDD_SCALARS:
+            setattr(a, n, float(scalars.get(n, DEDD_DEFAULTS[n])))
+        for names, src in ((DEDD_STATE, state), (DEDD_FORCING, forcing), (DEDD_OUT + DEDD_OUT_LAYERS + DEDD_OUT2D, out)):
+            for n in names:
+                setattr(a, n, _p64(src.get(n)))
+        a.coszen = _p64(coszen)
+        self._chk(self._L.evpk_step_radiation_dedd(self._ctx, ct.byref(a)), "evpk_step_radiation_dedd")
 
     def prep_radiation(self, arrays, nilyr: int, nslyr: int, puny=1.0e-11):
         """evpk_prep_radiation: prep_radiation in one launch (an AusCOM host does not call it).  arrays: dict of PREP_RAD_IN (aice and the

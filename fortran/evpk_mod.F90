@@ -234,6 +234,28 @@
          type (c_ptr) :: fswfac = c_null_ptr
       end type evpk_prep_rad_args
 
+      ! evpk_dedd_args (include/evpk.h): the arguments of evpk_step_radiation_dedd, member for member.  fswpenln may stay c_null_ptr; of t
+      ! nt_Tsfc, nt_apnd, nt_hpnd, nilyr, nslyr are read; the scalars default to the namelist defaults of source/ice_init.F90:289-304, :318-321
+      type, bind(C) :: evpk_dedd_args
+         integer (c_int32_t) :: calc_Tsfc = 1, heat_capacity = 1, tr_pond_cesm = 0, tr_pond_lvl = 0, tr_pond_topo = 0, tr_aero = 0
+         integer (c_int32_t) :: ncat, ntrcr, ntrcr_dim
+         type (evpk_itd_tracers) :: t
+         real (c_double) :: puny
+         real (c_double) :: R_ice = 0.0_c_double, R_pnd = 0.0_c_double, R_snw = 1.5_c_double, dT_mlt = 1.5_c_double
+         real (c_double) :: rsnw_mlt = 1500.0_c_double, kalg = 0.60_c_double, hs0 = 0.03_c_double, pndaspect = 0.8_c_double
+         real (c_double) :: awtvdr = 0.00318_c_double, awtidr = 0.00182_c_double, awtvdf = 0.63282_c_double, awtidf = 0.36218_c_double
+         type (c_ptr) :: aicen = c_null_ptr, vicen = c_null_ptr, vsnon = c_null_ptr, trcrn = c_null_ptr
+         type (c_ptr) :: swvdr = c_null_ptr, swvdf = c_null_ptr, swidr = c_null_ptr, swidf = c_null_ptr
+         type (c_ptr) :: coszen = c_null_ptr
+         type (c_ptr) :: alvdrn = c_null_ptr, alidrn = c_null_ptr, alvdfn = c_null_ptr, alidfn = c_null_ptr, albicen = c_null_ptr
+         type (c_ptr) :: albsnon = c_null_ptr, fswsfcn = c_null_ptr, fswintn = c_null_ptr, fswthrun = c_null_ptr
+         type (c_ptr) :: Sswabsn = c_null_ptr, Iswabsn = c_null_ptr, fswpenln = c_null_ptr
+         type (c_ptr) :: alvdr = c_null_ptr, alidr = c_null_ptr, alvdf = c_null_ptr, alidf = c_null_ptr
+         type (c_ptr) :: albice = c_null_ptr, albsno = c_null_ptr, scale_factor = c_null_ptr
+         type (c_ptr) :: albpndn = c_null_ptr, apeffn = c_null_ptr, snowfracn = c_null_ptr
+         type (c_ptr) :: albpnd = c_null_ptr, apeff_ai = c_null_ptr
+      end type evpk_dedd_args
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -249,7 +271,8 @@
                 evpk_therm2_args, evpk_new_ice_lateral_melt, evpk_step_therm2, &
                 evpk_thermo_args, evpk_thermo_vertical, EVPK_THERMO_STOP, &
                 evpk_therm1_args, evpk_step_therm1, &
-                evpk_rad_args, evpk_prep_rad_args, evpk_step_radiation, evpk_prep_radiation
+                evpk_rad_args, evpk_prep_rad_args, evpk_step_radiation, evpk_prep_radiation, &
+                evpk_dedd_args, evpk_step_radiation_dedd
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
@@ -495,6 +518,13 @@
             import :: c_int, c_ptr, evpk_prep_rad_args
             type (c_ptr), value :: ctx
             type (evpk_prep_rad_args), intent(in) :: a
+         end function
+         ! step_radiation on its Delta-Eddington branch (ice_step_mod.F90:1408-1451, run_dEdd) with the albedo lines of coupling_prep in
+         ! one launch; coszen is in / out: the caller runs compute_coszen first
+         integer (c_int) function evpk_step_radiation_dedd (ctx, a) bind(C, name='evpk_step_radiation_dedd')
+            import :: c_int, c_ptr, evpk_dedd_args
+            type (c_ptr), value :: ctx
+            type (evpk_dedd_args), intent(in) :: a
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then
          ! mm(nx_block,ny_block,0:ncat,max_blocks), tm(nx_block,ny_block,ntrace,ncat,max_blocks) advanced in place

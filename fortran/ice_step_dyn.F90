@@ -28,7 +28,7 @@
 
       implicit none
       private
-      public :: evpk_step_dynamics_core, evpk_step_radiation_core
+      public :: evpk_step_dynamics_core, evpk_step_radiation_core, evpk_step_radiation_dedd_core
 
       contains
 
@@ -239,6 +239,100 @@
       alvdr_ai = alvdr;  alidr_ai = alidr;  alvdf_ai = alvdf;  alidf_ai = alidf      ! CICE_RunMod.F90:564-567
 
       end subroutine evpk_step_radiation_core
+
+!=======================================================================
+
+! step_radiation with shortwave = 'dEdd' for every block, and the albedo lines of coupling_prep, in one library call.
+!
+! As evpk_step_radiation_core, for a host whose ice_in selects the Delta-Eddington scheme: the loop `call step_radiation (dt, iblk)`
+! and, in coupling_prep, the albedo aggregation (:503-548 without the albcnt lines), the four _ai copies (:564-567) and the
+! scale_factor line (:582-586) become
+!     use ice_step_dyn, only: evpk_step_radiation_dedd_core
+!     call evpk_step_radiation_dedd_core
+! The cosine of the zenith angle stays on the host: compute_coszen (shr_orb_decl, the libm sin and cos of ice_orbital.F90:130-132) runs
+! here over the tmask cells of every block, as run_dEdd does at :1385-1402, and the library stores max(puny, coszen) back on the listed,
+! lit cells.  This routine only marshals arguments; what the call computes is evpk_step_radiation_dedd (include/evpk.h), which refuses
+! tr_pond_lvl, tr_pond_topo, tr_aero, calc_Tsfc = .false. and the zero-layer model with its message.
+
+      subroutine evpk_step_radiation_dedd_core
+
+      use ice_blocks, only: nx_block, ny_block
+      use ice_calendar, only: dt
+      use ice_constants, only: puny, awtvdr, awtidr, awtvdf, awtidf
+      use ice_domain, only: nblocks
+      use ice_domain_size, only: ncat, nilyr, nslyr, max_ntrcr
+      use ice_dyn_evp, only: evpk_context
+      use ice_exit, only: abort_ice
+      use ice_flux, only: swvdr, swvdf, swidr, swidf, coszen, alvdr, alidr, alvdf, alidf, albice, albsno, albpnd, apeff_ai, &
+          scale_factor, alvdr_ai, alidr_ai, alvdf_ai, alidf_ai
+      use ice_grid, only: tmask, tlat, tlon
+      use ice_meltpond_cesm, only: hs0
+      use ice_meltpond_lvl, only: pndaspect
+      use ice_orbital, only: compute_coszen
+      use ice_shortwave, only: R_ice, R_pnd, R_snw, dT_mlt, rsnw_mlt, kalg, &
+          alvdrn, alidrn, alvdfn, alidfn, albicen, albsnon, albpndn, apeffn, snowfracn, fswsfcn, fswintn, fswthrun, fswpenln, &
+          Sswabsn, Iswabsn
+      use ice_state, only: aicen, vicen, vsnon, trcrn, ntrcr, nt_Tsfc, nt_apnd, nt_hpnd, tr_pond_cesm, tr_pond_lvl, tr_pond_topo, tr_aero
+      use ice_therm_shared, only: heat_capacity, calc_Tsfc
+
+      type (evpk_dedd_args) :: a
+      type (c_ptr) :: ctx
+      integer (c_int) :: rc
+      integer (kind=int_kind) :: iblk, i, j, icells
+      integer (kind=int_kind), dimension (nx_block*ny_block) :: indxi, indxj
+
+      ctx = evpk_context ()
+      if (.not. c_associated(ctx)) call abort_ice('step_radiation: no context on the device: evp has not run yet')
+
+      do iblk = 1, nblocks                                   ! ice_shortwave.F90:1385-1402
+         icells = 0
+         do j = 1, ny_block
+         do i = 1, nx_block
+            if (tmask(i,j,iblk)) then
+               icells = icells + 1
+               indxi(icells) = i
+               indxj(icells) = j
+            endif
+         enddo
+         enddo
+         call compute_coszen (nx_block, ny_block, icells, indxi, indxj, tlat(:,:,iblk), tlon(:,:,iblk), coszen(:,:,iblk), dt)
+      enddo
+
+      a%calc_Tsfc = merge(1_c_int32_t, 0_c_int32_t, calc_Tsfc)
+      a%heat_capacity = merge(1_c_int32_t, 0_c_int32_t, heat_capacity)
+      a%tr_pond_cesm = merge(1_c_int32_t, 0_c_int32_t, tr_pond_cesm)
+      a%tr_pond_lvl = merge(1_c_int32_t, 0_c_int32_t, tr_pond_lvl)
+      a%tr_pond_topo = merge(1_c_int32_t, 0_c_int32_t, tr_pond_topo)
+      a%tr_aero = merge(1_c_int32_t, 0_c_int32_t, tr_aero)
+      a%ncat = int(ncat, c_int32_t)
+      a%ntrcr = int(ntrcr, c_int32_t)
+      a%ntrcr_dim = int(max_ntrcr, c_int32_t)
+      a%t%nt_Tsfc = int(nt_Tsfc, c_int32_t);  a%t%nilyr = int(nilyr, c_int32_t);  a%t%nslyr = int(nslyr, c_int32_t)
+      if (tr_pond_cesm) then
+         a%t%nt_apnd = int(nt_apnd, c_int32_t);  a%t%nt_hpnd = int(nt_hpnd, c_int32_t)
+      endif
+      a%puny = puny
+      a%R_ice = R_ice;  a%R_pnd = R_pnd;  a%R_snw = R_snw;  a%dT_mlt = dT_mlt;  a%rsnw_mlt = rsnw_mlt;  a%kalg = kalg
+      a%hs0 = hs0;  a%pndaspect = pndaspect
+      a%awtvdr = awtvdr;  a%awtidr = awtidr;  a%awtvdf = awtvdf;  a%awtidf = awtidf
+
+      a%aicen = loc_r8(aicen);  a%vicen = loc_r8(vicen);  a%vsnon = loc_r8(vsnon);  a%trcrn = loc_r8(trcrn)
+      a%swvdr = loc_r8(swvdr);  a%swvdf = loc_r8(swvdf);  a%swidr = loc_r8(swidr);  a%swidf = loc_r8(swidf)
+      a%coszen = loc_r8(coszen)
+      a%alvdrn = loc_r8(alvdrn);  a%alidrn = loc_r8(alidrn);  a%alvdfn = loc_r8(alvdfn);  a%alidfn = loc_r8(alidfn)
+      a%albicen = loc_r8(albicen);  a%albsnon = loc_r8(albsnon)
+      a%fswsfcn = loc_r8(fswsfcn);  a%fswintn = loc_r8(fswintn);  a%fswthrun = loc_r8(fswthrun)
+      a%Sswabsn = loc_r8(Sswabsn);  a%Iswabsn = loc_r8(Iswabsn);  a%fswpenln = loc_r8(fswpenln)
+      a%alvdr = loc_r8(alvdr);  a%alidr = loc_r8(alidr);  a%alvdf = loc_r8(alvdf);  a%alidf = loc_r8(alidf)
+      a%albice = loc_r8(albice);  a%albsno = loc_r8(albsno);  a%scale_factor = loc_r8(scale_factor)
+      a%albpndn = loc_r8(albpndn);  a%apeffn = loc_r8(apeffn);  a%snowfracn = loc_r8(snowfracn)
+      a%albpnd = loc_r8(albpnd);  a%apeff_ai = loc_r8(apeff_ai)
+
+      rc = evpk_step_radiation_dedd (ctx, a)
+      if (rc /= 0) call abort_ice('step_radiation: evpk_step_radiation_dedd: '//trim(evpk_error_string(ctx)))
+      alvdr_ai = alvdr;  alidr_ai = alidr;  alvdf_ai = alvdf;  alidf_ai = alidf      ! CICE_RunMod.F90:564-567
+
+      end subroutine evpk_step_radiation_dedd_core
 
 !=======================================================================
 

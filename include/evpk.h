@@ -832,6 +832,99 @@ typedef struct {
 int evpk_step_radiation(evpk_ctx *c, const evpk_rad_args *a);
 int evpk_prep_radiation(evpk_ctx *c, const evpk_prep_rad_args *a);
 
+/* The Delta-Eddington shortwave (kernel in csrc/evpk_dedd.hip, tables in csrc/evpk_dedd_tables.h): the scheme every ice_in of the
+ * reference's own grids selects (shortwave = 'dEdd', reference/input_templates/{gx1,gx3,tp1,col}/ice_in).  evpk_step_radiation keeps
+ * refusing shortwave_dEdd = 1; a Delta-Eddington host calls this instead.
+ *
+ * evpk_step_radiation_dedd: step_radiation (source/ice_step_mod.F90:1408-1451) on its calc_Tsfc / dEdd branch -- run_dEdd
+ * (source/ice_shortwave.F90:1251-1577) with shortwave_dEdd_set_snow (:3782-3883), shortwave_dEdd_set_pond (:3893-3958), shortwave_dEdd
+ * (:1607-2024), compute_dEdd (:2034-3261) and solution_dEdd (:3270-3772) -- and the albedo lines of coupling_prep that follow it at once
+ * (drivers/auscom/CICE_RunMod.F90:503-548, :564-567, :582-586), in ONE launch (k_shortwave_dedd) for every category of every block: one
+ * thread per cell that walks the categories in order.
+ *   initialisation     on EVERY cell of the block arrays, ghost cells included (ice_step_mod.F90:1408-1423, ice_shortwave.F90:1428-1429,
+ *                      :1744-1773): ZERO -- not the ocean albedo, which run_dEdd never writes -- in alvdrn, alidrn, alvdfn, alidfn,
+ *                      albicen, albsnon, albpndn, apeffn, snowfracn, fswsfcn, fswintn, fswthrun, every layer of Sswabsn and Iswabsn and
+ *                      every layer of fswpenln.  (The reference copies its whole work planes into apeffn and snowfracn, :1547, :1552;
+ *                      set_snow and set_pond zero those planes first, :3838, :3936-3941, so a cell that is not listed holds zero)
+ *   coszen             an IN / OUT 2-D plane: the caller passes what compute_coszen made (source/ice_orbital.F90:63-139; 0 where tmask is
+ *                      false); shr_orb_decl and the libm sin / cos of ice_orbital.F90:130-132 stay on the host.  On a listed cell with
+ *                      netsw > puny the kernel stores max(puny, coszen) back (:1814, :1869, :1922); everywhere else the plane keeps the
+ *                      caller's value
+ *   cell list          per category (:1406-1415): physical cells with aicen > puny AND tmask -- the stated departure of
+ *                      evpk_thermo_vertical and of k_shortwave_ccsm3, kept so that every column kernel lists the same cells
+ *   set_snow           (:3857-3880) hs = vsnon / aicen; fs = 1 under hs >= hs_min, min(hs / hs0, 1) under hs0 > puny; fT =
+ *                      -min((Timelt - Tsfc) / dT_mlt - 1, 0) with the NAMELIST dT_mlt of the module (:134), not compute_albedos'
+ *                      shadowing local; rsnw_nm = min(max(rsnw_nonmelt - R_snw rsnw_sig, rsnw_fresh), rsnw_mlt); rsnw = rsnw_nm +
+ *                      (rsnw_mlt - rsnw_nm) fT, clamped likewise; rhosnw = rhos
+ *   ponds              tr_pond_cesm (:1432-1448): fpn = trcrn(nt_apnd), hpn = trcrn(nt_hpnd); under hs >= hs_min and hs0 > puny asnow =
+ *                      min(hs / hs0, 1), fpn = (1 - asnow) fpn, hpn = pndaspect fpn; apeffn = fpn.  No pond tracer (:1540-1550):
+ *                      set_pond's 0.3 fT (1 - fs) (fT on dT_pnd = 1) feeds apeffn only, fpn = hpn = 0 go into the radiation.
+ *                      tr_pond_lvl and tr_pond_topo are refused, as evpk_step_therm1 refuses them
+ *   shortwave_dEdd     (:1762-1765) fnidr = swidr / (swidr + swidf) under swidr + swidf > puny, else 0; (:1812) netsw = swvdr + swidr +
+ *                      swvdf + swidf in that order; hi = vicen / aicen; fi = (1 - fs) - fp (:1817); three passes -- bare ice under fi > 0
+ *                      (with hs = 0, :1835), snow under fs > 0, pond under fp > puny -- each adds avdrl f and its like into the four
+ *                      category albedos and the four-term awt* sum into albicen, albsnon, albpndn, left to right (:1848-1855, :1900-1907,
+ *                      :1954-1961)
+ *   compute_dEdd       band weights wghtns (:2602-2605); frsnw (:2612); the layer thicknesses dzk with both surface scattering layers
+ *                      (:2618-2647); the R_ice / R_pnd adjustment of the ice and pond optical properties, both signs of each
+ *                      (:2655-2721; uniform per call: computed on the host in this order); snow optical properties by linear
+ *                      interpolation in the 32-radius table with both table ends (:2758-2785); pond layers (:2837-2841); the ice layers
+ *                      with the kalg term in the lowest layer of band 1 (:2855-2886); ice under ponds and the pond-depth transition hpmin
+ *                      <= hp <= hp0 (:2940-2986); albodr / albodf (:2992-2994); the interface fluxes dfdir / dfdif with their < puny -> 0
+ *                      clamps (:3045-3051); the visible and near-infrared accumulations into fsfc, fint, fthru, Sabs, Iabs and fthrul
+ *                      (-> fswpenln) with the km / kp indexing of the snow case (:3058-3186); the sums times the surface fraction
+ *                      (:3197-3231)
+ *   solution_dEdd      the statement functions alpha, agamm, n, u, el, taus, omgs, asys evaluated exactly as written (:3500-3508); mu0 =
+ *                      max(coszen, 0.01) (:3535); the refracted mu0n (:3541); the trntdr > trmin cut-off (:3577); extins and trnlay under
+ *                      max(exp_min, .) (:3597, :3607); the eight-point Gaussian recomputation of rdif / tdif with swt summed in the loop
+ *                      (:3619-3639); the Fresnel layer at kfrsnl (:3649-3702); the downward (:3730-3738) and upward (:3754-3769) sweeps
+ *   aggregation        every cell, categories in order (CICE_RunMod.F90:523-548): alvdf, alidf, alvdr, alidr and apeff_ai always; albice,
+ *                      albsno, albpnd only under coszen > puny -- here the test decides, on the cell's coszen after the store above;
+ *                      scale_factor as in :582-586.  alvdr_ai .. alidf_ai are plain copies (:564-567): the caller aliases them
+ * Arithmetic: the Fortran's operation order, -ffp-contract=off; x**2 is x*x; min / max are a comparison and a select; sqrt is the IEEE one;
+ * exp is dev_exp.  exp_min = exp(-argmax) with argmax = 10 a parameter (:1376, :1383), folded by the compiler with correct rounding: the
+ * literal 4.5399929762484854e-05 = 0x3F07CD79B5647C9B, the double nearest to e^-10 (exact arithmetic: 2.6e-21 away; its neighbours 4.1e-21
+ * and 9.4e-21).
+ * Compiled in (csrc/evpk_dedd_tables.h names the lines): rsnw_tab, Qs_tab, ws_tab, gs_tab; the mean ice and pond optical properties; kw,
+ * ww, gw; gauspt, gauswt; hi_ssl = 0.05, hs_ssl = 0.04, hpmin = 0.005, hp0 = 0.2, hs_min = 1e-4, rhoi = 917 (compute_dEdd's own), trmin =
+ * 0.001, refindx = 1.31.  rhos is that of evpk_set_params.  evpk_dedd_table(name, out, n) reads any of them back.
+ * **Parity unpinned**: nothing under oracle/ builds these routines; the call is held bit for bit to a numpy restatement written from the
+ * Fortran (tests/npdedd.py) with its own copy of the tables.
+ * Members (one struct of borrowed pointers; arrays (nx_block, ny_block[, ncat], nblocks) unless given):
+ *   calc_Tsfc, heat_capacity (only 1, 1 are accepted), tr_pond_cesm, tr_pond_lvl, tr_pond_topo, tr_aero (a pond flag set here or in t counts)
+ *   ncat, ntrcr, ntrcr_dim, t (nt_Tsfc, nt_apnd, nt_hpnd, nilyr, nslyr are read) as in evpk_thermo_args; puny (must be 1e-11)
+ *   R_ice, R_pnd, R_snw, dT_mlt, rsnw_mlt, kalg, hs0, pndaspect, awtvdr, awtidr, awtvdf, awtidf      the namelist's (ice_init.F90:289-304)
+ *   aicen, vicen, vsnon, trcrn, swvdr, swvdf, swidr, swidf   in
+ *   coszen                                                   in / out, 2-D
+ *   alvdrn, alidrn, alvdfn, alidfn, albicen, albsnon, fswsfcn, fswintn, fswthrun, albpndn, apeffn, snowfracn      out, per category, every cell
+ *   Sswabsn (.., nslyr, ncat, ..), Iswabsn (.., nilyr, ncat, ..), fswpenln (.., nilyr+1, ncat, ..; may be NULL)    out, every cell
+ *   alvdr, alidr, alvdf, alidf, albice, albsno, scale_factor, albpnd, apeff_ai        out, 2-D, every cell
+ * Nothing the call overwrites is copied up.
+ * Returns 0; or 1 with evpk_last_error, before any copy, touching nothing: calc_Tsfc = .false.; heat_capacity = .false.; tr_aero;
+ * tr_pond_lvl; tr_pond_topo; tr_pond_cesm without nt_apnd / nt_hpnd; nilyr or nslyr outside 1..8; ncat outside 1..16; a tracer index
+ * beyond ntrcr; puny != 1e-11; dT_mlt <= 0; a missing pointer (fswpenln may be NULL); a context of several ranks (nranks > 1) on which
+ * evpk_connect has not run.  x-slab ranks: the call is not collective -- a rank without a block column returns 0.
+ * Out of scope: level-ice and topographic ponds (dhsn, ffracn, :1450-1539); aerosols (aero_mp, :1775-1798 and the tr_aero blocks of
+ * compute_dEdd); the zero-layer tail (:3240-3259); compute_coszen; albcnt; the rest of coupling_prep. */
+#define EVPK_HAS_STEP_RADIATION_DEDD 1
+typedef struct {
+    int32_t calc_Tsfc, heat_capacity, tr_pond_cesm, tr_pond_lvl, tr_pond_topo, tr_aero;
+    int32_t ncat, ntrcr, ntrcr_dim;
+    evpk_itd_tracers t;
+    double puny;
+    double R_ice, R_pnd, R_snw, dT_mlt, rsnw_mlt, kalg, hs0, pndaspect, awtvdr, awtidr, awtvdf, awtidf;
+    const double *aicen, *vicen, *vsnon, *trcrn;                              /* in */
+    const double *swvdr, *swvdf, *swidr, *swidf;                              /* in */
+    double *coszen;                                                           /* in / out */
+    double *alvdrn, *alidrn, *alvdfn, *alidfn, *albicen, *albsnon, *fswsfcn, *fswintn, *fswthrun;     /* out, per category, every cell */
+    double *Sswabsn, *Iswabsn, *fswpenln;                                     /* out; fswpenln may be NULL */
+    double *alvdr, *alidr, *alvdf, *alidf, *albice, *albsno, *scale_factor;  /* out, 2-D, every cell */
+    double *albpndn, *apeffn, *snowfracn;                                     /* out, per category, every cell */
+    double *albpnd, *apeff_ai;                                                /* out, 2-D, every cell */
+} evpk_dedd_args;
+int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a);
+int evpk_dedd_table(const char *name, double *out, int32_t n);
+
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared
  * (:79-80), stress_eap (:1052-1467) with update_stress_rdg (:1474-1658) takes the place of stress, stepa (:1664-1787, with
