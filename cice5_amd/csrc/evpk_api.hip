@@ -4495,21 +4495,29 @@ extern "C" int evpk_thermo_vertical(evpk_ctx *c, const evpk_thermo_args *a, int3
     return EVPK_THERMO_STOP;
 }
 
+// what the two level-ice pond entry points refuse beyond their parents
+static int pond_lvl_check(evpk_ctx *c, const char *who, const evpk_itd_tracers &t, int ntrcr, const evpk_pond_lvl_args *p) {
+    const int nts[4] = {t.nt_alvl, t.nt_apnd, t.nt_hpnd, p->nt_ipnd};
+    for (int nt : nts)
+        if (nt < 1 || nt > ntrcr) FAIL(c, "%s: tr_pond_lvl without nt_alvl / nt_apnd / nt_hpnd / nt_ipnd in 1..ntrcr = %d", who, ntrcr);
+    if (p->frzpnd < 0 || p->frzpnd > 1) FAIL(c, "%s: frzpnd = %d not 0 ('cesm') or 1 ('hlid')", who, p->frzpnd);
+    if (!p->dhsn || !p->ffracn) FAIL(c, "%s: tr_pond_lvl needs dhsn and ffracn", who);
+    return 0;
+}
+
 // ---- step_therm1 (source/ice_step_mod.F90:154-733) in one call: k_therm1_open, k_thermo_vertical, k_therm1_merge (evpk_therm1s.hip) on
 // state staged once ----
-extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t stop[5]) {
-    if (!c) return 1;
-    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
-    RANKS_ENTRY(c, "evpk_step_therm1");
-    if (!a || !stop) FAIL(c, "evpk_step_therm1: a required argument is missing");
-    const char *who = "evpk_step_therm1";
+// p: the level-ice pond arguments of evpk_step_therm1_lvl, or null for evpk_step_therm1
+static int therm1_run(evpk_ctx *c, const char *who, const evpk_therm1_args *a, const evpk_pond_lvl_args *p, int32_t stop[5]) {
     const evpk_thermo_args &v = a->tv;
     const evpk_itd_tracers &t = v.t;
     if (a->formdrag) FAIL(c, "%s: formdrag (neutral_drag_coeffs) is not supported", who);
     if (a->highfreq) FAIL(c, "%s: highfreq coupling is not supported", who);
     if (a->atmbndy_constant) FAIL(c, "%s: atmbndy = 'constant' (atmo_boundary_const) is not supported", who);
     if (a->fbot_xfer_Cdn_ocn) FAIL(c, "%s: fbot_xfer_type = 'Cdn_ocn' is not supported", who);
-    if (t.tr_pond_lvl) FAIL(c, "%s: tr_pond_lvl (compute_ponds_lvl) is not supported", who);
+    if (!p && t.tr_pond_lvl) FAIL(c, "%s: tr_pond_lvl (compute_ponds_lvl) is not supported", who);
+    if (p && !t.tr_pond_lvl) FAIL(c, "%s: tr_pond_lvl is not set", who);
+    if (p && t.tr_pond_cesm) FAIL(c, "%s: tr_pond_cesm is set beside tr_pond_lvl", who);
     if (t.tr_pond_topo) FAIL(c, "%s: tr_pond_topo (compute_ponds_topo) is not supported", who);
     if (a->tr_aero) FAIL(c, "%s: aerosol tracers (tr_aero, update_aerosol) are not supported", who);
     if (thermo_check(c, who, &v, false)) return 1;
@@ -4527,6 +4535,12 @@ extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t 
         FAIL(c, "%s: tr_pond_cesm without nt_apnd / nt_hpnd in 1..ntrcr = %d", who, v.ntrcr);
     if (t.tr_pond_cesm && !a->frain) FAIL(c, "%s: tr_pond_cesm needs frain", who);
     if (t.tr_pond_cesm && !(a->pndaspect > 0.0)) FAIL(c, "%s: pndaspect = %g", who, a->pndaspect);
+    if (p) {
+        if (pond_lvl_check(c, who, t, v.ntrcr, p)) return 1;
+        if (!p->Tair) FAIL(c, "%s: tr_pond_lvl needs Tair", who);
+        if (!a->frain) FAIL(c, "%s: tr_pond_lvl needs frain", who);
+        if (!(a->pndaspect > 0.0)) FAIL(c, "%s: pndaspect = %g", who, a->pndaspect);
+    }
     if (!c->nblocks) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * v.ncat;
@@ -4548,12 +4562,17 @@ extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t 
         {const_cast<double *>(v.fbot), N, &d_fbot, true, false}, {const_cast<double *>(v.Tbot), N, &d_Tbot, true, false},
         {a->aice, N, &A.aice, false}, {a->frzmlt, N, &A.frzmlt, false}, {a->sst, N, &A.sst, false}, {a->Tf, N, &A.Tf, false},
         {a->strocnxT, N, &A.strocnxT, false}, {a->strocnyT, N, &A.strocnyT, false}, {a->uatm, N, &A.uatm, false}, {a->vatm, N, &A.vatm, false},
-        {a->wind, N, &A.wind, false}, {a->zlvl, N, &A.zlvl, false}, {t.tr_pond_cesm ? a->frain : nullptr, N, &A.frain, false},
+        {a->wind, N, &A.wind, false}, {a->zlvl, N, &A.zlvl, false}, {t.tr_pond_cesm || p ? a->frain : nullptr, N, &A.frain, false},
         {a->fswthrun, n3, &A.fswthrun, false}, {a->tr_FY ? a->lmask_n : nullptr, N, &A.lmask_n, false}, {a->tr_FY ? a->lmask_s : nullptr, N, &A.lmask_s, false},
         {a->Cdn_atm, N, &A.Cdn_atm, true}, {a->rside, N, &A.rside, true, false}, {a->aice_init, N, &A.aice_init, true, false},
         {a->aicen_init, n3, &A.aicen_init, true, false}, {a->vicen_init, n3, &A.vicen_init, true, false}};
     for (int q = 0; q < 8; q++) arr.push_back({h_opt[q], n3, &d_opt[q], true, false});
     for (int q = 0; q < T1S_NMERGE; q++) arr.push_back({merged[q], N, &A.m[q], true});
+    if (p) {                                  // (ffracn is written on every cell: not copied up)
+        arr.push_back({p->dhsn, n3, &A.dhsn, false});
+        arr.push_back({p->ffracn, n3, &A.ffracn, true, false});
+        arr.push_back({p->Tair, N, &A.Tair, false});
+    }
     if (stage_in(c, arr, true)) return 1;
     HIPCHK(c, grow(c, c->th1_pool, c->th1_pool_n, 8 * n3 + 2 * N));        // one pool, grown once
     for (int q = 0; q < 8; q++) if (!d_opt[q]) d_opt[q] = c->th1_pool + (size_t)q * n3;
@@ -4573,6 +4592,10 @@ extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t 
     A.nt_qice = t.nt_qice; A.nt_qsno = t.nt_qsno; A.nt_apnd = t.nt_apnd; A.nt_hpnd = t.nt_hpnd; A.nt_iage = a->nt_iage; A.nt_FY = a->nt_FY;
     A.tr_iage = a->tr_iage ? 1 : 0; A.tr_FY = a->tr_FY ? 1 : 0; A.tr_pond_cesm = t.tr_pond_cesm ? 1 : 0; A.calc_strair = a->calc_strair ? 1 : 0;
     A.natmiter = a->natmiter;
+    if (p) {
+        A.nt_alvl = t.nt_alvl; A.nt_ipnd = p->nt_ipnd; A.nt_sice = v.nt_sice; A.frzpnd = p->frzpnd; A.dpscale = p->dpscale;
+        A.Lfresh = v.k.Lfresh; A.cp_ice = v.k.cp_ice;
+    }
     A.dt = v.dt; A.yday = v.yday; A.puny = v.k.puny; A.rhoi = c->p.rhoi; A.rhos = c->p.rhos; A.rhow = c->p.rhow; A.chio = a->chio;
     A.ustar_min = a->ustar_min; A.hi_min = a->hi_min; A.pndaspect = a->pndaspect; A.rfracmin = a->rfracmin; A.rfracmax = a->rfracmax;
     const dim3 b(64), g = block_grid(c);
@@ -4586,15 +4609,36 @@ extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t 
     if (rc == 1) return 1;
     const std::string keep = c->err;
     if (rc == 0) {                            // (no merge after a stop)
-        if (v.ncat == 5)
-            hipLaunchKernelGGL(k_therm1_merge<5>, g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+        if (v.ncat == 5 && p)
+            hipLaunchKernelGGL((k_therm1_merge<5, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+        else if (p)
+            hipLaunchKernelGGL((k_therm1_merge<0, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+        else if (v.ncat == 5)
+            hipLaunchKernelGGL((k_therm1_merge<5, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
         else
-            hipLaunchKernelGGL(k_therm1_merge<0>, g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+            hipLaunchKernelGGL((k_therm1_merge<0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
         HIPCHK(c, hipGetLastError());
     }
     if (stage_out(c, arr)) return 1;
     if (rc) c->err = keep;
     return rc;
+}
+
+extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t stop[5]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
+    RANKS_ENTRY(c, "evpk_step_therm1");
+    if (!a || !stop) FAIL(c, "evpk_step_therm1: a required argument is missing");
+    return therm1_run(c, "evpk_step_therm1", a, nullptr, stop);
+}
+
+// step_therm1 under tr_pond_lvl: compute_ponds_lvl (source/ice_meltpond_lvl.F90:79-404) in the place of compute_ponds_cesm
+extern "C" int evpk_step_therm1_lvl(evpk_ctx *c, const evpk_therm1_args *a, const evpk_pond_lvl_args *p, int32_t stop[5]) {
+    if (!c) return 1;
+    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
+    RANKS_ENTRY(c, "evpk_step_therm1_lvl");
+    if (!a || !p || !stop) FAIL(c, "evpk_step_therm1_lvl: a required argument is missing");
+    return therm1_run(c, "evpk_step_therm1_lvl", a, p, stop);
 }
 
 // ---- step_radiation (source/ice_step_mod.F90:1364-1524, ccsm3) with the albedo lines of coupling_prep, and prep_radiation (:33-145):
@@ -4687,17 +4731,16 @@ extern "C" int evpk_prep_radiation(evpk_ctx *c, const evpk_prep_rad_args *a) {
 
 // ---- step_radiation on its Delta-Eddington branch (source/ice_step_mod.F90:1408-1451: run_dEdd, source/ice_shortwave.F90:1251-1577) with
 // the albedo lines of coupling_prep: one launch (kernel in evpk_dedd.hip) ----
-extern "C" int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a) {
-    if (!c) return 1;
-    RANKS_ENTRY(c, "evpk_step_radiation_dedd");
-    const char *who = "evpk_step_radiation_dedd";
-    if (!a) FAIL(c, "%s: a required argument is missing", who);
+// p: the level-ice pond arguments of evpk_step_radiation_dedd_lvl, or null for evpk_step_radiation_dedd
+static int dedd_run(evpk_ctx *c, const char *who, const evpk_dedd_args *a, const evpk_pond_lvl_args *p) {
     const evpk_itd_tracers &t = a->t;
     const bool cesm = a->tr_pond_cesm || t.tr_pond_cesm;
     if (a->calc_Tsfc != 1) FAIL(c, "%s: calc_Tsfc = .false. is not supported", who);
     if (a->heat_capacity != 1) FAIL(c, "%s: heat_capacity = .false. (zero-layer) is not supported", who);
     if (a->tr_aero) FAIL(c, "%s: aerosol tracers (tr_aero) are not supported", who);
-    if (a->tr_pond_lvl || t.tr_pond_lvl) FAIL(c, "%s: tr_pond_lvl (dhsn, ffracn) is not supported", who);
+    if (!p && (a->tr_pond_lvl || t.tr_pond_lvl)) FAIL(c, "%s: tr_pond_lvl (dhsn, ffracn) is not supported", who);
+    if (p && !(a->tr_pond_lvl || t.tr_pond_lvl)) FAIL(c, "%s: tr_pond_lvl is not set", who);
+    if (p && cesm) FAIL(c, "%s: tr_pond_cesm is set beside tr_pond_lvl", who);
     if (a->tr_pond_topo || t.tr_pond_topo) FAIL(c, "%s: tr_pond_topo is not supported", who);
     if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->swvdr || !a->swvdf || !a->swidr || !a->swidf || !a->coszen || !a->alvdrn ||
         !a->alidrn || !a->alvdfn || !a->alidfn || !a->albicen || !a->albsnon || !a->fswsfcn || !a->fswintn || !a->fswthrun || !a->Sswabsn ||
@@ -4713,6 +4756,11 @@ extern "C" int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a) {
         FAIL(c, "%s: tr_pond_cesm without nt_apnd / nt_hpnd in 1..ntrcr = %d", who, a->ntrcr);
     if (a->puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->puny);
     if (!(a->dT_mlt > 0.0)) FAIL(c, "%s: dT_mlt = %g", who, a->dT_mlt);
+    if (p) {
+        if (pond_lvl_check(c, who, t, a->ntrcr, p)) return 1;
+        if (!p->fsnow) FAIL(c, "%s: tr_pond_lvl needs fsnow", who);
+        if (!(p->dt > 0.0)) FAIL(c, "%s: dt = %g", who, p->dt);
+    }
     if (!c->nblocks) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     DeddArgs A{};
@@ -4721,6 +4769,7 @@ extern "C" int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a) {
     A.puny = a->puny; A.rhos = c->p.rhos; A.R_snw = a->R_snw; A.dT_mlt = a->dT_mlt; A.rsnw_mlt = a->rsnw_mlt; A.kalg = a->kalg; A.hs0 = a->hs0;
     A.pndaspect = a->pndaspect; A.awtvdr = a->awtvdr; A.awtidr = a->awtidr; A.awtvdf = a->awtvdf; A.awtidf = a->awtidf;
     dedd_iops(a->R_ice, a->R_pnd, A.iop);
+    if (p) { A.nt_alvl = t.nt_alvl; A.nt_ipnd = p->nt_ipnd; A.linitonly = p->linitonly ? 1 : 0; A.hs1 = p->hs1; A.dt = p->dt; }
     const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
     std::vector<HostArr> arr = {            // (every output is written on every cell: none is copied up; coszen is in / out)
         {a->aicen, n3, &A.aicen, false}, {a->vicen, n3, &A.vicen, false}, {a->vsnon, n3, &A.vsnon, false}, {a->trcrn, n3 * a->ntrcr_dim, &A.trcrn, false},
@@ -4735,15 +4784,40 @@ extern "C" int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a) {
         {a->alvdr, N, &A.alvdr, true, false}, {a->alidr, N, &A.alidr, true, false}, {a->alvdf, N, &A.alvdf, true, false},
         {a->alidf, N, &A.alidf, true, false}, {a->albice, N, &A.albice, true, false}, {a->albsno, N, &A.albsno, true, false},
         {a->albpnd, N, &A.albpnd, true, false}, {a->apeff_ai, N, &A.apeff_ai, true, false}, {a->scale_factor, N, &A.scale_factor, true, false}};
+    if (p) {                                  // (dhsn is in / out on the listed cells)
+        arr.push_back({p->dhsn, n3, &A.dhsn, true});
+        arr.push_back({p->ffracn, n3, &A.ffracn, false});
+        arr.push_back({p->fsnow, N, &A.fsnow, false});
+    }
     if (stage_in(c, arr, true)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
     const dim3 b(64), g = block_grid(c);
-    if (a->ncat == 5 && t.nilyr == 4 && t.nslyr == 1)
-        hipLaunchKernelGGL((k_shortwave_dedd<5, 4, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    const bool fixed = a->ncat == 5 && t.nilyr == 4 && t.nslyr == 1;
+    if (fixed && p)
+        hipLaunchKernelGGL((k_shortwave_dedd<5, 4, 1, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    else if (p)
+        hipLaunchKernelGGL((k_shortwave_dedd<0, 0, 0, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+    else if (fixed)
+        hipLaunchKernelGGL((k_shortwave_dedd<5, 4, 1, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
     else
-        hipLaunchKernelGGL((k_shortwave_dedd<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
+        hipLaunchKernelGGL((k_shortwave_dedd<0, 0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
     HIPCHK(c, hipGetLastError());
     return stage_out(c, arr);
+}
+
+extern "C" int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a) {
+    if (!c) return 1;
+    RANKS_ENTRY(c, "evpk_step_radiation_dedd");
+    if (!a) FAIL(c, "evpk_step_radiation_dedd: a required argument is missing");
+    return dedd_run(c, "evpk_step_radiation_dedd", a, nullptr);
+}
+
+// step_radiation (dEdd) under tr_pond_lvl: the level-ice block of run_dEdd (source/ice_shortwave.F90:1450-1514) sets the ponds
+extern "C" int evpk_step_radiation_dedd_lvl(evpk_ctx *c, const evpk_dedd_args *a, const evpk_pond_lvl_args *p) {
+    if (!c) return 1;
+    RANKS_ENTRY(c, "evpk_step_radiation_dedd_lvl");
+    if (!a || !p) FAIL(c, "evpk_step_radiation_dedd_lvl: a required argument is missing");
+    return dedd_run(c, "evpk_step_radiation_dedd_lvl", a, p);
 }
 
 // the tables of evpk_dedd_tables.h by name (no context, no device): out[0 .. n), n the table's length; 1 for an unknown name or another n

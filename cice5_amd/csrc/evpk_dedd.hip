@@ -18,6 +18,9 @@
 // interpolations once per (category, band): every snow layer of a column has the same grain radius (:3873-3880, :2756).
 // The adjusted ice and pond optical properties (ki_ssl .. gi_p_int, :2655-2721) are uniform per call: evpk_step_radiation_dedd computes
 // them on the host in the Fortran's order (dedd_iops) and passes them by value.
+// The LVL instantiations (evpk_step_radiation_dedd_lvl) run the tr_pond_lvl block of run_dEdd (:1450-1514) in the place of the tr_pond_cesm
+// lines: dhsn is read and written on the listed cells, ffracn and fsnow are read, and the snow depth the radiation sees is the infiltrated
+// one.  The pond scheme is a template parameter so that the instantiations without it keep their registers (no scratch in <5, 4, 1, 0>).
 // Operation order: the Fortran's, -ffp-contract=off; x**2 is x*x; min / max are a comparison and a select; sqrt is the IEEE one; exp is
 // dev_exp; the statement functions of solution_dEdd (:3500-3508) are evaluated exactly as written.
 #pragma once
@@ -69,6 +72,11 @@ struct DeddArgs {
     int ncat, ntrcr_dim, nxb, nyb, nilyr, nslyr, nt_Tsfc, nt_apnd, nt_hpnd, tr_pond_cesm;
     double puny, rhos, R_snw, dT_mlt, rsnw_mlt, kalg, hs0, pndaspect, awtvdr, awtidr, awtvdf, awtidf;
     DeddIop iop;
+    // tr_pond_lvl (the LVL instantiations only; behind the members above so that theirs keep their places)
+    double *dhsn;                                                       // (nb, ncat, ny, nx), in / out on the listed cells
+    const double *ffracn, *fsnow;                                       // (nb, ncat, ny, nx), (nb, ny, nx)
+    int nt_alvl, nt_ipnd, linitonly;
+    double hs1, dt;
 };
 
 // the statement functions of solution_dEdd (:3500-3508), as written
@@ -79,7 +87,9 @@ __device__ __forceinline__ double dedd_agamm(double w, double uu, double gg, dou
     return (0.5 * w) * ((1.0 + (((3.0 * gg) * (1.0 - w)) * uu) * uu) / (1.0 - ((e * e) * uu) * uu));
 }
 
-template <int NC, int NL, int NS>
+// LVL = 1: the tr_pond_lvl block of run_dEdd (:1450-1514) sets the ponds, and the snow depth and fraction the radiation sees; LVL = 0 is
+// the kernel as it was (tr_pond_cesm or no pond tracer, chosen at run time).
+template <int NC, int NL, int NS, int LVL>
 __global__ void __launch_bounds__(64) k_shortwave_dedd(Slab s, const BlockDesc *bd, DeddArgs A) {
     using namespace dedd;
     __shared__ double lds[DEDD_LDS];
@@ -156,7 +166,7 @@ __global__ void __launch_bounds__(64) k_shortwave_dedd(Slab s, const BlockDesc *
             const double vsnon = A.vsnon[bc];
             const double Tsfc = A.trcrn[(lo * A.ntrcr_dim + (A.nt_Tsfc - 1)) * nn + o];
             // shortwave_dEdd_set_snow (:3857-3880)
-            const double hs = vsnon / aicen;
+            double hs = vsnon / aicen;
             double fs = c0;
             if (hs >= hs_min) {
                 fs = c1;
@@ -175,7 +185,43 @@ __global__ void __launch_bounds__(64) k_shortwave_dedd(Slab s, const BlockDesc *
             }
             // ponds (:1432-1448 or :1540-1550)
             double fp, hp;
-            if (A.tr_pond_cesm) {
+            if constexpr (LVL) {                                                         // :1450-1514
+                const double *t = A.trcrn + lo * A.ntrcr_dim * nn + o;
+                const double alvl = t[(size_t)(A.nt_alvl - 1) * nn], apnd = t[(size_t)(A.nt_apnd - 1) * nn];
+                const double ipn = (alvl * apnd) * t[(size_t)(A.nt_ipnd - 1) * nn];     // the lid thickness averaged over the ice
+                double dhs = A.dhsn[bc];
+                const double snowfall = A.fsnow[ci] * A.dt;
+                if (!A.linitonly && ipn > puny && dhs < puny && snowfall > hs_min) dhs = hs - snowfall;
+                const double spn = hs - dhs;                                             // snow depth on the pond ice
+                if (!A.linitonly && ipn * spn < puny) dhs = c0;
+                A.dhsn[bc] = dhs;
+                fp = apnd * alvl;
+                hp = t[(size_t)(A.nt_hpnd - 1) * nn];
+                fp = (c1 - A.ffracn[bc]) * fp;
+                if (dhs > puny && spn >= puny && A.hs1 > puny) {                         // taper with the snow on the pond ice
+                    const double asnow = litd_min(spn / A.hs1, c1);
+                    fp = (c1 - asnow) * fp;
+                }
+                double hpi = hp;                                                         // infiltrate the snow
+                if (hpi > puny) {
+                    const double rhofresh = th1s::rhofresh;
+                    const double rp = (rhofresh * hpi) / (rhofresh * hpi + A.rhos * hs);
+                    if (rp < 0.15) {
+                        fp = c0;
+                        hp = c0;
+                    } else {
+                        const double hmx = (hs * (rhofresh - A.rhos)) / rhofresh;
+                        const double tmp = litd_max(c0, copysign(c1, hpi - hmx));
+                        hpi = (rhofresh * hpi + (A.rhos * hs) * tmp) / (rhofresh - A.rhos * (c1 - tmp));
+                        hs = hs - (hpi * fp) * (c1 - tmp);
+                        hp = hpi * tmp;
+                        fp = fp * tmp;
+                    }
+                }
+                if (hp < hpmin) fp = c0;
+                fs = litd_min(fs, c1 - fp);
+                apeff = fp;
+            } else if (A.tr_pond_cesm) {
                 fp = A.trcrn[(lo * A.ntrcr_dim + (A.nt_apnd - 1)) * nn + o];
                 hp = A.trcrn[(lo * A.ntrcr_dim + (A.nt_hpnd - 1)) * nn + o];
                 if (hs >= hs_min && A.hs0 > puny) {
@@ -475,7 +521,9 @@ __global__ void __launch_bounds__(64) k_shortwave_dedd(Slab s, const BlockDesc *
     A.albice[ci] = albice; A.albsno[ci] = albsno; A.albpnd[ci] = albpnd; A.apeff_ai[ci] = apeff_ai;
     A.scale_factor[ci] = ((swvdr * (c1 - alvdr) + swvdf * (c1 - alvdf)) + swidr * (c1 - alidr)) + swidf * (c1 - alidf);     // :582-586
 }
-template __global__ void __launch_bounds__(64) k_shortwave_dedd<0, 0, 0>(Slab, const BlockDesc *, DeddArgs);
-template __global__ void __launch_bounds__(64) k_shortwave_dedd<5, 4, 1>(Slab, const BlockDesc *, DeddArgs);
+template __global__ void __launch_bounds__(64) k_shortwave_dedd<0, 0, 0, 0>(Slab, const BlockDesc *, DeddArgs);
+template __global__ void __launch_bounds__(64) k_shortwave_dedd<5, 4, 1, 0>(Slab, const BlockDesc *, DeddArgs);
+template __global__ void __launch_bounds__(64) k_shortwave_dedd<0, 0, 0, 1>(Slab, const BlockDesc *, DeddArgs);
+template __global__ void __launch_bounds__(64) k_shortwave_dedd<5, 4, 1, 1>(Slab, const BlockDesc *, DeddArgs);
 
 }  // namespace evpk

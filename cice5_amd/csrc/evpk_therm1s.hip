@@ -10,6 +10,8 @@
 //   k_therm1_merge   per category in order: fswabsn (:565-571), compute_ponds_cesm (source/ice_meltpond_cesm.F90:61-197) on its own list
 //                    (aicen > puny AFTER the vertical thermodynamics), merge_fluxes (source/ice_flux.F90:681-831) weighted with aicen_init
 //                    over the list of entry.  One thread per cell: the category order gives the sums the reference's bits.
+//                    Its LVL instantiations (evpk_step_therm1_lvl) run compute_ponds_lvl (source/ice_meltpond_lvl.F90:79-404) in the place
+//                    of compute_ponds_cesm, on that routine's own list: physical cells with aicen alvl > puny**2, and tmask.
 // The eight per-category results of atmo_boundary_layer (shcoef, lhcoef, strairxn, strairyn, Cdn_atm_ratio_n, Trefn, Qrefn, Urefn) are locals
 // of step_therm1; here they are per-category planes, ZERO wherever the cell is not listed.  (The Fortran's block-wide `icells > 0` test only
 // decides whether locals nobody reads -- merge_fluxes and thermo_vertical run over the same list -- hold zeros or the previous category's
@@ -56,6 +58,11 @@ struct Therm1sArgs {
     int ncat, ntrcr_dim, nxb, nyb, nilyr, nslyr, nt_Tsfc, nt_qice, nt_qsno, nt_apnd, nt_hpnd, nt_iage, nt_FY, tr_iage, tr_FY, tr_pond_cesm,
         calc_strair, natmiter;
     double dt, yday, puny, rhoi, rhos, rhow, chio, ustar_min, hi_min, pndaspect, rfracmin, rfracmax;
+    // tr_pond_lvl (the LVL instantiations of k_therm1_merge only; behind the members above so that theirs keep their places)
+    const double *dhsn, *Tair;                                          // (nb, ncat, ny, nx), (nb, ny, nx)
+    double *ffracn;                                                     // (nb, ncat, ny, nx), written on every cell
+    int nt_alvl, nt_ipnd, nt_sice, frzpnd;                              // frzpnd: 0 'cesm', 1 'hlid'
+    double dpscale, Lfresh, cp_ice;
 };
 
 // the unstable parts of the stability functions (ice_atmo.F90:208-212)
@@ -208,13 +215,123 @@ __global__ void __launch_bounds__(64) k_therm1_open(Slab s, const BlockDesc *bd,
 template __global__ void __launch_bounds__(64) k_therm1_open<0>(Slab, const BlockDesc *, Therm1sArgs);
 template __global__ void __launch_bounds__(64) k_therm1_open<5>(Slab, const BlockDesc *, Therm1sArgs);
 
-template <int NC>
+// compute_ponds_lvl (source/ice_meltpond_lvl.F90:79-345) with brine_permeability (:351-404) and calculate_Tin_from_qin under l_brine
+// (source/ice_therm_shared.F90:62-90) on one physical ocean cell and category, on the state thermo_vertical left; t: the category's tracer
+// planes at this cell.  ffracn is written by the caller's zero and, under 'hlid', here.  ktherm is 1 (evpk_thermo_vertical refuses
+// anything else), so the drainage runs whenever hpondn > 0 and dpscale > puny; the nilyr enthalpy and salinity planes are read only then.
+__device__ __forceinline__ void t1s_ponds_lvl(const Therm1sArgs &A, double *t, size_t nn, size_t bc, size_t ci, double aicen) {
+    using namespace th1s;
+    const double c0 = 0.0, c1 = 1.0, c2 = 2.0, c4 = 4.0, c10 = 10.0, p5 = 0.5, puny = A.puny;
+    const double viscosity_dyn = 1.79e-3;                                                // drivers/cice/ice_constants.F90:42
+    double *apnd = t + (size_t)(A.nt_apnd - 1) * nn, *hpnd = t + (size_t)(A.nt_hpnd - 1) * nn, *ipnd = t + (size_t)(A.nt_ipnd - 1) * nn;
+    const double alvl = t[(size_t)(A.nt_alvl - 1) * nn];
+    if (!(aicen * alvl > puny * puny)) return;                                           // :187-196
+    const double hpnd0 = *hpnd, apnd0 = *apnd;
+    double volpn = ((hpnd0 * aicen) * alvl) * apnd0;                                     // :177-178
+    const double hi = A.vicen[bc] / aicen, hs = A.vsnon[bc] / aicen;
+    double apondn, hpondn, hlid = c0;
+    if (hi < A.hi_min) {                                                                 // :206-215
+        apondn = c0; hpondn = c0; volpn = c0; hlid = c0;
+    } else {
+        apondn = apnd0 * alvl;
+        const double rfrac = A.rfracmin + (A.rfracmax - A.rfracmin) * aicen;             // ice_step_mod.F90:624
+        double dvn = ((rfrac / rhofresh) * ((A.melttn[bc] * A.rhoi + A.meltsn[bc] * A.rhos) + A.frain[ci] * A.dt)) * aicen;       // :228-230
+        if (A.frzpnd == 0) {                                                             // 'cesm' (:233-236)
+            const double Tp = Timelt - Td;
+            const double dTs = litd_max(Tp - t[(size_t)(A.nt_Tsfc - 1) * nn], c0);
+            dvn = dvn - volpn * (c1 - dev_exp((rexp * dTs) / Tp));
+        } else {                                                                         // 'hlid' (:238-267)
+            hlid = *ipnd;
+            double dhlid;
+            if (dvn == c0) {
+                const double Ts = A.Tair[ci] - th1::Tffresh;
+                if (Ts < c0) {
+                    const double bdt = ((((-c2) * Ts) * th1::kice) * A.dt) / (A.rhoi * A.Lfresh);
+                    dhlid = p5 * sqrt(bdt);
+                    if (hlid > dhlid) dhlid = (p5 * bdt) / hlid;
+                    dhlid = litd_min(dhlid, (hpnd0 * rhofresh) / A.rhoi);
+                    hlid = hlid + dhlid;
+                } else {
+                    dhlid = c0;
+                }
+            } else {
+                const double fsurfn = A.fsurfn[bc];
+                dhlid = litd_max((fsurfn * A.dt) / (A.rhoi * A.Lfresh), c0);
+                dhlid = -litd_min(dhlid, hlid);
+                hlid = litd_max(hlid + dhlid, c0);
+                if (hs - A.dhsn[bc] < puny) {
+                    double ffrac = c1;
+                    if (fsurfn > puny) ffrac = litd_min((((-dhlid) * A.rhoi) * A.Lfresh) / (A.dt * fsurfn), c1);
+                    A.ffracn[bc] = ffrac;
+                }
+            }
+            const double alid = apondn * aicen;
+            dvn = dvn - ((dhlid * alid) * A.rhoi) / rhofresh;
+        }
+        volpn = volpn + dvn;
+        if (volpn <= c0) { volpn = c0; apondn = c0; }                                    // :274-277
+        if (apondn * aicen > puny) {                                                     // existing ponds (:279-284)
+            apondn = litd_max(c0, litd_min(alvl, apondn + (0.5 * dvn) / ((A.pndaspect * apondn) * aicen)));
+            hpondn = c0;
+            if (apondn > puny) hpondn = volpn / (apondn * aicen);
+        } else if (alvl * aicen > c10 * puny) {                                          // new ponds (:286-288)
+            apondn = litd_min(sqrt(volpn / (A.pndaspect * aicen)), alvl);
+            hpondn = A.pndaspect * apondn;
+        } else {                                                                         // melt water runs off deformed ice (:290-293)
+            apondn = c0; hpondn = c0;
+        }
+        apondn = litd_max(apondn, c0);
+        hpondn = litd_min(hpondn, ((A.rhow - A.rhoi) * hi - A.rhos * hs) / rhofresh);    // :297
+        apondn = apondn * aicen;
+        volpn = hpondn * apondn;
+        if (volpn <= c0) { volpn = c0; apondn = c0; hpondn = c0; hlid = c0; }            // :303-308
+        if (hpondn > c0 && A.dpscale > puny) {                                           // :316-331 (ktherm = 1)
+            const double draft = (A.rhos * hs + A.rhoi * hi) / A.rhow + hpondn;
+            double deltah = (hpondn + hi) - draft;
+            const double pressure_head = (gravit * A.rhow) * litd_max(deltah, c0);
+            double phimin = c0;
+            _Pragma("unroll 1")
+            for (int k = 0; k < A.nilyr; k++) {                                          // brine_permeability (:384-402)
+                const double qin = t[(size_t)(A.nt_qice - 1 + k) * nn], salin = t[(size_t)(A.nt_sice - 1 + k) * nn];
+                const double Tmlt = (-salin) * th1::depressT;
+                const double aa1 = A.cp_ice;                                             // ice_therm_shared.F90:80-84
+                const double bb1 = (((th1::cp_ocn - A.cp_ice) * Tmlt) - qin / A.rhoi) - A.Lfresh;
+                const double cc1 = A.Lfresh * Tmlt;
+                const double Tin = litd_min((-bb1 - sqrt(bb1 * bb1 - (c4 * aa1) * cc1)) / (c2 * aa1), Tmlt);
+                const double Sbr = c1 / (1.0e-3 - th1::depressT / Tin);
+                double phi = salin / Sbr;
+                if (phi < 0.05) phi = c0;
+                if (k == 0 || phi < phimin) phimin = phi;
+            }
+            const double perm = 3.0e-8 * ((phimin * phimin) * phimin);
+            const double drain = (((perm * pressure_head) * A.dt) / (viscosity_dyn * hi)) * A.dpscale;
+            deltah = litd_min(drain, hpondn);
+            const double dvd = (-deltah) * apondn;
+            volpn = volpn + dvd;
+            apondn = litd_max(c0, litd_min(apondn + (0.5 * dvd) / (A.pndaspect * apondn), alvl * aicen));
+            hpondn = c0;
+            if (apondn > puny) hpondn = volpn / apondn;
+        }
+    }
+    *hpnd = hpondn;                                                                      // :339-341
+    *apnd = apondn / (aicen * alvl);
+    if (A.frzpnd == 1) *ipnd = hlid;
+}
+
+// LVL = 1: tr_pond_lvl -- compute_ponds_lvl at the reference's call site (ice_step_mod.F90:623-642) in place of compute_ponds_cesm, and
+// ffracn = 0 on every cell of the block arrays (ice_meltpond_lvl.F90:175-181).  LVL = 0 is the kernel as it was.
+template <int NC, int LVL>
 __global__ void __launch_bounds__(64) k_therm1_merge(Slab s, const BlockDesc *bd, Therm1sArgs A) {
     using namespace th1s;
     const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
     const int j = blockIdx.y + 1;
     const int b = blockIdx.z;
     if (i > A.nxb) return;
+    if constexpr (LVL) {
+        const int nc = NC ? NC : A.ncat;
+        const size_t pn = (size_t)A.nyb * A.nxb, po = (size_t)(j - 1) * A.nxb + (i - 1);
+        for (int n = 0; n < nc; n++) A.ffracn[((size_t)b * nc + n) * pn + po] = 0.0;
+    }
     if (!itd_ocean(s, bd[b], i, j)) return;
     const int ncat = NC ? NC : A.ncat;
     const double c0 = 0.0, c1 = 1.0, puny = A.puny;
@@ -225,7 +342,9 @@ __global__ void __launch_bounds__(64) k_therm1_merge(Slab s, const BlockDesc *bd
     for (int n = 1; n <= ncat; n++) {
         const size_t lo = (size_t)b * ncat + (n - 1), bc = lo * nn + o;
         const double aicen = A.aicen[bc];
-        if (A.tr_pond_cesm && aicen > puny) {                                            // ice_meltpond_cesm.F90:124-193
+        if constexpr (LVL) {
+            t1s_ponds_lvl(A, A.trcrn + lo * A.ntrcr_dim * nn + o, nn, bc, ci, aicen);
+        } else if (A.tr_pond_cesm && aicen > puny) {                                     // ice_meltpond_cesm.F90:124-193
             double *t = A.trcrn + lo * A.ntrcr_dim * nn + o;
             double *apnd = t + (size_t)(A.nt_apnd - 1) * nn, *hpnd = t + (size_t)(A.nt_hpnd - 1) * nn;
             const double rfrac = A.rfracmin + (A.rfracmax - A.rfracmin) * aicen;         // ice_step_mod.F90:610
@@ -284,7 +403,9 @@ __global__ void __launch_bounds__(64) k_therm1_merge(Slab s, const BlockDesc *bd
         for (int q = 0; q < T1S_NMERGE; q++) A.m[q][ci] = m[q];
     }
 }
-template __global__ void __launch_bounds__(64) k_therm1_merge<0>(Slab, const BlockDesc *, Therm1sArgs);
-template __global__ void __launch_bounds__(64) k_therm1_merge<5>(Slab, const BlockDesc *, Therm1sArgs);
+template __global__ void __launch_bounds__(64) k_therm1_merge<0, 0>(Slab, const BlockDesc *, Therm1sArgs);
+template __global__ void __launch_bounds__(64) k_therm1_merge<5, 0>(Slab, const BlockDesc *, Therm1sArgs);
+template __global__ void __launch_bounds__(64) k_therm1_merge<0, 1>(Slab, const BlockDesc *, Therm1sArgs);
+template __global__ void __launch_bounds__(64) k_therm1_merge<5, 1>(Slab, const BlockDesc *, Therm1sArgs);
 
 }  // namespace evpk

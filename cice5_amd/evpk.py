@@ -99,7 +99,7 @@ EXPORTS = ["evpk_get_unique_id", "evpk_create", "evpk_set_params", "evpk_run", "
            "evpk_transport_upwind_state", "evpk_host_alloc", "evpk_host_free", "evpk_host_is_mapped", "evpk_ridge_ice",
            "evpk_cleanup_itd", "evpk_aggregate", "evpk_bound_state", "evpk_step_dynamics", "evpk_linear_itd",
            "evpk_new_ice_lateral_melt", "evpk_step_therm2", "evpk_thermo_vertical", "evpk_step_therm1", "evpk_step_radiation",
-           "evpk_prep_radiation", "evpk_step_radiation_dedd", "evpk_dedd_table"]
+           "evpk_prep_radiation", "evpk_step_radiation_dedd", "evpk_dedd_table", "evpk_step_therm1_lvl", "evpk_step_radiation_dedd_lvl"]
 
 REMAP_BAD_DEPARTURE, REMAP_NEGATIVE_MASS = 11, 12        # include/evpk.h
 RIDGE_STOP = 13
@@ -260,6 +260,30 @@ class DeddArgs(ct.Structure):
                 [(n, c_f64p) for n in RAD_OUT2D if n != "coszen"] + [(n, c_f64p) for n in ("albpndn", "apeffn", "snowfracn", "albpnd", "apeff_ai")])
 
 
+POND_LVL_ARRAYS = ["dhsn", "ffracn", "Tair", "fsnow"]                                 # (nb, ncat, ny, nx) x 2, (nb, ny, nx) x 2
+POND_LVL_SCALARS = ["dpscale", "hs1", "dt"]
+POND_LVL_FLAGS = ["frzpnd", "nt_ipnd", "linitonly"]
+FRZPND = {"cesm": 0, "hlid": 1}
+# the values every ice_in the reference ships sets (input_templates/*/ice_in); the defaults of source/ice_init.F90:299-301 are 0.03, 1, 'cesm'
+POND_LVL_DEFAULTS = dict(hs1=0.03, dpscale=1.0e-3, frzpnd="hlid")
+
+
+class PondLvlArgs(ct.Structure):
+    """evpk_pond_lvl_args (include/evpk.h), member for member"""
+    _fields_ = ([(n, c_f64p) for n in POND_LVL_ARRAYS] + [(n, ct.c_double) for n in POND_LVL_SCALARS] + [(n, ct.c_int32) for n in POND_LVL_FLAGS])
+
+
+def pond_lvl_args(ponds, tracers, dt=0.0, linitonly=False):
+    """PondLvlArgs from a dict with any of POND_LVL_ARRAYS, dpscale, hs1 and frzpnd ('cesm' / 'hlid' or 0 / 1); nt_ipnd from tracers"""
+    p = PondLvlArgs()
+    for n in POND_LVL_ARRAYS:
+        setattr(p, n, _p64(ponds.get(n)))
+    p.dpscale, p.hs1, p.dt = float(ponds.get("dpscale", POND_LVL_DEFAULTS["dpscale"])), float(ponds.get("hs1", POND_LVL_DEFAULTS["hs1"])), float(dt)
+    frz = ponds.get("frzpnd", POND_LVL_DEFAULTS["frzpnd"])
+    p.frzpnd, p.nt_ipnd, p.linitonly = int(FRZPND.get(frz, frz)), int(tracers.get("nt_ipnd", 0)), int(bool(linitonly))
+    return p
+
+
 def dedd_table(name: str) -> np.ndarray:
     """evpk_dedd_table: one table of csrc/evpk_dedd_tables.h as the library holds it (the snow tables [band][radius], flattened)"""
     out = np.zeros(DEDD_TABLES[name])
@@ -357,6 +381,8 @@ def lib():
         L.evpk_prep_radiation.argtypes = [ctxp, ct.POINTER(PrepRadArgs)]
         L.evpk_step_radiation_dedd.argtypes = [ctxp, ct.POINTER(DeddArgs)]
         L.evpk_dedd_table.argtypes = [ct.c_char_p, c_f64p, ct.c_int32]
+        L.evpk_step_therm1_lvl.argtypes = [ctxp, ct.POINTER(Therm1Args), ct.POINTER(PondLvlArgs), c_i32p]
+        L.evpk_step_radiation_dedd_lvl.argtypes = [ctxp, ct.POINTER(DeddArgs), ct.POINTER(PondLvlArgs)]
         L.evpk_restart_write.argtypes = [ctxp, ct.c_char_p, ct.c_int32, ct.c_int32]
         L.evpk_restart_read.argtypes = [ctxp, ct.c_char_p, ct.c_int64, ct.c_int32]
         for n in EXPORTS:
@@ -850,7 +876,7 @@ class Context:
     def step_therm1(self, dt: float, state, forcing, inout, out, merged, ntrcr: int, tracers, yday=0.0, conduct=0, min_salin=0.1, constants=None,
                     ktherm=1, calc_Tsfc=True, heat_capacity=True, l_brine=True, chio=0.006, ustar_min=0.0005, natmiter=5, calc_strair=True,
                     hi_min=0.01, pndaspect=0.8, rfracmin=0.15, rfracmax=1.0, formdrag=False, highfreq=False, atmbndy="default",
-                    fbot_xfer_type="constant", tr_aero=False):
+                    fbot_xfer_type="constant", tr_aero=False, ponds=None):
         """evpk_step_therm1: step_therm1 in one call -- frzmlt_bottom_lateral, atmo_boundary_layer, increment_age, update_FYarea,
         thermo_vertical (BL99), compute_ponds_cesm, merge_fluxes -- on arrays staged once.  state, inout as for thermo_vertical; forcing:
         dict of THERMO_FORCING (fbot, Tbot, shcoef, lhcoef may be absent: given, they receive what the call computed) plus THERM1_IN2D
@@ -858,7 +884,8 @@ class Context:
         out: dict of THERMO_OUT plus THERM1_OUT (rside, aice_init (nb, ny, nx); aicen_init, vicen_init (nb, ncat, ny, nx)) and, where
         wanted, THERM1_DIAG (nb, ncat, ny, nx); merged: dict of Cdn_atm and THERM1_MERGED (nb, ny, nx), in / out.  tracers: dict of
         ITD_TRACER_FIELDS plus nt_sice, tr_iage, tr_FY, nt_iage, nt_FY.
-        Returns None, or (reason, block, category, i, j) as thermo_vertical; raises on a refusal, which leaves every array untouched."""
+        Returns None, or (reason, block, category, i, j) as thermo_vertical; raises on a refusal, which leaves every array untouched.
+        (ponds: see step_therm1_lvl, which passes it.)"""
         from . import constants as C
         a = Therm1Args()
         v = a.tv
@@ -886,11 +913,22 @@ class Context:
         a.formdrag, a.highfreq, a.tr_aero = int(bool(formdrag)), int(bool(highfreq)), int(bool(tr_aero))
         a.atmbndy_constant, a.fbot_xfer_Cdn_ocn = int(atmbndy == "constant"), int(fbot_xfer_type == "Cdn_ocn")
         stop = np.zeros(5, dtype=np.int32)
-        rc = self._L.evpk_step_therm1(self._ctx, ct.byref(a), _p32(stop))
+        if ponds is None:
+            rc, who = self._L.evpk_step_therm1(self._ctx, ct.byref(a), _p32(stop)), "evpk_step_therm1"
+        else:
+            p = pond_lvl_args(ponds, tracers)
+            rc, who = self._L.evpk_step_therm1_lvl(self._ctx, ct.byref(a), ct.byref(p), _p32(stop)), "evpk_step_therm1_lvl"
         if rc == THERMO_STOP:
             return tuple(int(v) for v in stop)
-        self._chk(rc, "evpk_step_therm1")
+        self._chk(rc, who)
         return None
+
+    def step_therm1_lvl(self, dt: float, state, forcing, inout, out, merged, ponds, ntrcr: int, tracers, **kw):
+        """evpk_step_therm1_lvl: step_therm1 under tr_pond_lvl -- everything step_therm1 does, with compute_ponds_lvl in the place of
+        compute_ponds_cesm.  Arguments as for step_therm1 (forcing must hold frain; tracers has tr_pond_lvl = 1, nt_alvl, nt_apnd, nt_hpnd
+        and nt_ipnd); ponds: dict of dhsn (nb, ncat, ny, nx; read), ffracn (nb, ncat, ny, nx; written on every cell), Tair (nb, ny, nx) and,
+        where they differ from POND_LVL_DEFAULTS, dpscale and frzpnd ('cesm' / 'hlid').  Returns and raises as step_therm1."""
+        return self.step_therm1(dt, state, forcing, inout, out, merged, ntrcr, tracers, ponds=ponds, **kw)
 
     def step_radiation(self, state, forcing, out, ntrcr: int, tracers, albedo_type="default", shortwave="default", calc_Tsfc=True,
                        heat_capacity=True, puny=1.0e-11, **scalars):
@@ -919,14 +957,15 @@ class Context:
         self._chk(self._L.evpk_step_radiation(self._ctx, ct.byref(a)), "evpk_step_radiation")
 
     def step_radiation_dedd(self, state, forcing, coszen, out, ntrcr: int, tracers, calc_Tsfc=True, heat_capacity=True, tr_aero=False,
-                            puny=1.0e-11, **scalars):
+                            puny=1.0e-11, ponds=None, dt=0.0, linitonly=False, **scalars):
         """evpk_step_radiation_dedd: step_radiation on its Delta-Eddington branch (run_dEdd) and the albedo lines of coupling_prep in one
         launch.  state: dict of DEDD_STATE -- aicen / vicen / vsnon (nb, ncat, ny, nx), trcrn (nb, ncat, ntrcr_dim, ny, nx), read only;
         forcing: dict of DEDD_FORCING (nb, ny, nx); coszen (nb, ny, nx): what compute_coszen made, in / out -- max(puny, coszen) is stored
         on the listed, lit cells; out: dict of DEDD_OUT (nb, ncat, ny, nx), DEDD_OUT_LAYERS (Sswabsn (nb, ncat, nslyr, ny, nx), Iswabsn
         (nb, ncat, nilyr, ny, nx), fswpenln (nb, ncat, nilyr + 1, ny, nx), which may be absent) and DEDD_OUT2D (nb, ny, nx), all written
         on every cell.  tracers: dict with nt_Tsfc, nilyr, nslyr and, with tr_pond_cesm, nt_apnd, nt_hpnd; scalars: any of DEDD_SCALARS
-        (the rest take DEDD_DEFAULTS, the reference's namelist defaults).  Raises on a refusal, which leaves every array untouched."""
+        (the rest take DEDD_DEFAULTS, the reference's namelist defaults).  Raises on a refusal, which leaves every array untouched.
+        (ponds, dt, linitonly: see step_radiation_dedd_lvl, which passes them.)"""
         a = DeddArgs()
         a.calc_Tsfc, a.heat_capacity, a.tr_aero = int(bool(calc_Tsfc)), int(bool(heat_capacity)), int(bool(tr_aero))
         a.tr_pond_cesm, a.tr_pond_lvl, a.tr_pond_topo = (int(bool(tracers.get(k, 0))) for k in ("tr_pond_cesm", "tr_pond_lvl", "tr_pond_topo"))
@@ -944,7 +983,18 @@ class Context:
             for n in names:
                 setattr(a, n, _p64(src.get(n)))
         a.coszen = _p64(coszen)
-        self._chk(self._L.evpk_step_radiation_dedd(self._ctx, ct.byref(a)), "evpk_step_radiation_dedd")
+        if ponds is None:
+            self._chk(self._L.evpk_step_radiation_dedd(self._ctx, ct.byref(a)), "evpk_step_radiation_dedd")
+        else:
+            p = pond_lvl_args(ponds, tracers, dt, linitonly)
+            self._chk(self._L.evpk_step_radiation_dedd_lvl(self._ctx, ct.byref(a), ct.byref(p)), "evpk_step_radiation_dedd_lvl")
+
+    def step_radiation_dedd_lvl(self, dt: float, state, forcing, coszen, out, ponds, ntrcr: int, tracers, linitonly=False, **kw):
+        """evpk_step_radiation_dedd_lvl: step_radiation_dedd under tr_pond_lvl -- the level-ice block of run_dEdd sets the ponds and the
+        snow the radiation sees.  Arguments as for step_radiation_dedd (tracers has tr_pond_lvl = 1, nt_alvl, nt_apnd, nt_hpnd, nt_ipnd);
+        dt: the time step of fsnow dt; ponds: dict of dhsn (nb, ncat, ny, nx; in / out on the listed cells), ffracn (nb, ncat, ny, nx; read),
+        fsnow (nb, ny, nx) and, where it differs from POND_LVL_DEFAULTS, hs1; linitonly: run_dEdd's initonly, which leaves dhsn as it is."""
+        return self.step_radiation_dedd(state, forcing, coszen, out, ntrcr, tracers, ponds=ponds, dt=dt, linitonly=linitonly, **kw)
 
     def prep_radiation(self, arrays, nilyr: int, nslyr: int, puny=1.0e-11):
         """evpk_prep_radiation: prep_radiation in one launch (an AusCOM host does not call it).  arrays: dict of PREP_RAD_IN (aice and the

@@ -256,6 +256,16 @@
          type (c_ptr) :: albpnd = c_null_ptr, apeff_ai = c_null_ptr
       end type evpk_dedd_args
 
+      ! evpk_pond_lvl_args (include/evpk.h): what compute_ponds_lvl and the tr_pond_lvl block of run_dEdd hand each other, and the scheme's
+      ! namelist, member for member.  Tair is read by evpk_step_therm1_lvl only, fsnow, hs1, dt and linitonly by
+      ! evpk_step_radiation_dedd_lvl only; frzpnd: 0 'cesm', 1 'hlid'
+      type, bind(C) :: evpk_pond_lvl_args
+         type (c_ptr) :: dhsn = c_null_ptr, ffracn = c_null_ptr
+         type (c_ptr) :: Tair = c_null_ptr, fsnow = c_null_ptr
+         real (c_double) :: dpscale = 1.0_c_double, hs1 = 0.03_c_double, dt = 0.0_c_double
+         integer (c_int32_t) :: frzpnd = 0, nt_ipnd = 0, linitonly = 0
+      end type evpk_pond_lvl_args
+
       public :: evpk_get_unique_id, evpk_create, evpk_set_params, evpk_run, &
                 evpk_get_stats, evpk_destroy, evpk_last_error, evpk_error_string, &
                 evpk_principal_stress, evpk_pin_host, evpk_unpin_host, evpk_host_alloc, evpk_host_free, evpk_host_is_mapped, &
@@ -272,7 +282,8 @@
                 evpk_thermo_args, evpk_thermo_vertical, EVPK_THERMO_STOP, &
                 evpk_therm1_args, evpk_step_therm1, &
                 evpk_rad_args, evpk_prep_rad_args, evpk_step_radiation, evpk_prep_radiation, &
-                evpk_dedd_args, evpk_step_radiation_dedd
+                evpk_dedd_args, evpk_step_radiation_dedd, &
+                evpk_pond_lvl_args, evpk_step_therm1_lvl, evpk_step_radiation_dedd_lvl
 
       integer (c_int), parameter :: EVPK_REMAP_BAD_DEPARTURE = 11, EVPK_REMAP_NEGATIVE_MASS = 12     ! include/evpk.h
       integer (c_int), parameter :: EVPK_RIDGE_STOP = 13
@@ -525,6 +536,21 @@
             import :: c_int, c_ptr, evpk_dedd_args
             type (c_ptr), value :: ctx
             type (evpk_dedd_args), intent(in) :: a
+         end function
+         ! the two calls above under tr_pond_lvl: compute_ponds_lvl (ice_meltpond_lvl.F90:79-404) in the place of compute_ponds_cesm, and
+         ! the level-ice block of run_dEdd (ice_shortwave.F90:1450-1514); dhsn and ffracn of p pass from one to the other
+         integer (c_int) function evpk_step_therm1_lvl (ctx, a, p, stop) bind(C, name='evpk_step_therm1_lvl')
+            import :: c_int, c_ptr, c_int32_t, evpk_therm1_args, evpk_pond_lvl_args
+            type (c_ptr), value :: ctx
+            type (evpk_therm1_args), intent(in) :: a
+            type (evpk_pond_lvl_args), intent(in) :: p
+            integer (c_int32_t), intent(out) :: stop(5)
+         end function
+         integer (c_int) function evpk_step_radiation_dedd_lvl (ctx, a, p) bind(C, name='evpk_step_radiation_dedd_lvl')
+            import :: c_int, c_ptr, evpk_dedd_args, evpk_pond_lvl_args
+            type (c_ptr), value :: ctx
+            type (evpk_dedd_args), intent(in) :: a
+            type (evpk_pond_lvl_args), intent(in) :: p
          end function
          ! horizontal_remap (ice_transport_remap.F90:309-850) on the resident velocities: dxu, dyu, hm once, then
          ! mm(nx_block,ny_block,0:ncat,max_blocks), tm(nx_block,ny_block,ntrace,ncat,max_blocks) advanced in place

@@ -29,6 +29,11 @@
       implicit none
       private
       public :: evpk_step_dynamics_core, evpk_step_radiation_core, evpk_step_radiation_dedd_core
+      public :: evpk_step_radiation_dedd_lvl_core, evpk_step_therm1_lvl_core
+
+      ! step_therm1 keeps these five per category only as 2-D locals (ice_step_mod.F90:216-223); the library wants planes per category
+      real (kind=dbl_kind), dimension (:,:,:,:), allocatable, save, target :: flwoutn_w, evapn_w, freshn_w, fsaltn_w, fhocnn_w
+      integer (c_int32_t), dimension (:,:,:), allocatable, save, target :: lmask_n_w, lmask_s_w
 
       contains
 
@@ -256,15 +261,72 @@
 
       subroutine evpk_step_radiation_dedd_core
 
+      use ice_dyn_evp, only: evpk_context
+      use ice_exit, only: abort_ice
+      use ice_flux, only: alvdr, alidr, alvdf, alidf, alvdr_ai, alidr_ai, alvdf_ai, alidf_ai
+
+      type (evpk_dedd_args) :: a
+      type (c_ptr) :: ctx
+      integer (c_int) :: rc
+
+      ctx = evpk_context ()
+      if (.not. c_associated(ctx)) call abort_ice('step_radiation: no context on the device: evp has not run yet')
+      call dedd_marshal (a)
+      rc = evpk_step_radiation_dedd (ctx, a)
+      if (rc /= 0) call abort_ice('step_radiation: evpk_step_radiation_dedd: '//trim(evpk_error_string(ctx)))
+      alvdr_ai = alvdr;  alidr_ai = alidr;  alvdf_ai = alvdf;  alidf_ai = alidf      ! CICE_RunMod.F90:564-567
+
+      end subroutine evpk_step_radiation_dedd_core
+
+!=======================================================================
+
+! The same under tr_pond_lvl (the scheme the shipped ice_in select beside shortwave = 'dEdd'): the level-ice block of run_dEdd
+! (ice_shortwave.F90:1450-1514) on dhsn and ffracn of ice_meltpond_lvl, fsnow of ice_flux, nt_alvl, nt_ipnd, hs1.  initonly is run_dEdd's
+! (init_shortwave passes .true.: dhsn then stays as it is).  What the call computes is evpk_step_radiation_dedd_lvl (include/evpk.h).
+
+      subroutine evpk_step_radiation_dedd_lvl_core (initonly)
+
+      use ice_calendar, only: dt
+      use ice_dyn_evp, only: evpk_context
+      use ice_exit, only: abort_ice
+      use ice_flux, only: alvdr, alidr, alvdf, alidf, alvdr_ai, alidr_ai, alvdf_ai, alidf_ai, fsnow
+      use ice_meltpond_lvl, only: dhsn, ffracn, hs1
+      use ice_state, only: nt_alvl, nt_apnd, nt_hpnd, nt_ipnd
+
+      logical (kind=log_kind), intent(in), optional :: initonly
+
+      type (evpk_dedd_args) :: a
+      type (evpk_pond_lvl_args) :: p
+      type (c_ptr) :: ctx
+      integer (c_int) :: rc
+
+      ctx = evpk_context ()
+      if (.not. c_associated(ctx)) call abort_ice('step_radiation: no context on the device: evp has not run yet')
+      call dedd_marshal (a)
+      a%t%nt_alvl = int(nt_alvl, c_int32_t);  a%t%nt_apnd = int(nt_apnd, c_int32_t);  a%t%nt_hpnd = int(nt_hpnd, c_int32_t)
+      p%nt_ipnd = int(nt_ipnd, c_int32_t)
+      p%hs1 = hs1;  p%dt = dt
+      if (present(initonly)) p%linitonly = merge(1_c_int32_t, 0_c_int32_t, initonly)
+      p%dhsn = loc_r8(dhsn);  p%ffracn = loc_r8(ffracn);  p%fsnow = loc_r8(fsnow)
+      rc = evpk_step_radiation_dedd_lvl (ctx, a, p)
+      if (rc /= 0) call abort_ice('step_radiation: evpk_step_radiation_dedd_lvl: '//trim(evpk_error_string(ctx)))
+      alvdr_ai = alvdr;  alidr_ai = alidr;  alvdf_ai = alvdf;  alidf_ai = alidf      ! CICE_RunMod.F90:564-567
+
+      end subroutine evpk_step_radiation_dedd_lvl_core
+
+!=======================================================================
+
+! compute_coszen on the host and the arguments both Delta-Eddington calls share
+
+      subroutine dedd_marshal (a)
+
       use ice_blocks, only: nx_block, ny_block
       use ice_calendar, only: dt
       use ice_constants, only: puny, awtvdr, awtidr, awtvdf, awtidf
       use ice_domain, only: nblocks
       use ice_domain_size, only: ncat, nilyr, nslyr, max_ntrcr
-      use ice_dyn_evp, only: evpk_context
-      use ice_exit, only: abort_ice
       use ice_flux, only: swvdr, swvdf, swidr, swidf, coszen, alvdr, alidr, alvdf, alidf, albice, albsno, albpnd, apeff_ai, &
-          scale_factor, alvdr_ai, alidr_ai, alvdf_ai, alidf_ai
+          scale_factor
       use ice_grid, only: tmask, tlat, tlon
       use ice_meltpond_cesm, only: hs0
       use ice_meltpond_lvl, only: pndaspect
@@ -275,14 +337,9 @@
       use ice_state, only: aicen, vicen, vsnon, trcrn, ntrcr, nt_Tsfc, nt_apnd, nt_hpnd, tr_pond_cesm, tr_pond_lvl, tr_pond_topo, tr_aero
       use ice_therm_shared, only: heat_capacity, calc_Tsfc
 
-      type (evpk_dedd_args) :: a
-      type (c_ptr) :: ctx
-      integer (c_int) :: rc
+      type (evpk_dedd_args), intent(inout) :: a
       integer (kind=int_kind) :: iblk, i, j, icells
       integer (kind=int_kind), dimension (nx_block*ny_block) :: indxi, indxj
-
-      ctx = evpk_context ()
-      if (.not. c_associated(ctx)) call abort_ice('step_radiation: no context on the device: evp has not run yet')
 
       do iblk = 1, nblocks                                   ! ice_shortwave.F90:1385-1402
          icells = 0
@@ -328,11 +385,132 @@
       a%albpndn = loc_r8(albpndn);  a%apeffn = loc_r8(apeffn);  a%snowfracn = loc_r8(snowfracn)
       a%albpnd = loc_r8(albpnd);  a%apeff_ai = loc_r8(apeff_ai)
 
-      rc = evpk_step_radiation_dedd (ctx, a)
-      if (rc /= 0) call abort_ice('step_radiation: evpk_step_radiation_dedd: '//trim(evpk_error_string(ctx)))
-      alvdr_ai = alvdr;  alidr_ai = alidr;  alvdf_ai = alvdf;  alidf_ai = alidf      ! CICE_RunMod.F90:564-567
+      end subroutine dedd_marshal
 
-      end subroutine evpk_step_radiation_dedd_core
+!=======================================================================
+
+! step_therm1 under tr_pond_lvl for every block in one library call.
+!
+! In the reference's ice_step the loop `call step_therm1 (dt, iblk)` becomes
+!     use ice_step_dyn, only: evpk_step_therm1_lvl_core
+!     call evpk_step_therm1_lvl_core (dt)
+! It runs over the reference's own module arrays: the state of ice_state, the forcing and fluxes of ice_flux, the radiation arrays of
+! ice_shortwave, Cdn_atm and Cdn_atm_ratio of ice_atmo, and dhsn, ffracn, dpscale, frzpnd, rfracmin, rfracmax, pndaspect of
+! ice_meltpond_lvl with Tair and nt_ipnd.  flwoutn, evapn, freshn, fsaltn and fhocnn are 2-D locals of step_therm1; the library wants
+! them per category, so this module keeps them.  lmask_n / lmask_s are logical in ice_grid and int32 here.  This routine only marshals
+! arguments; what the call computes is evpk_step_therm1_lvl (include/evpk.h), which refuses formdrag, highfreq, atmbndy = 'constant',
+! fbot_xfer_type = 'Cdn_ocn', ktherm /= 1, aerosols and the other pond schemes with its message.  The call is not collective.
+
+      subroutine evpk_step_therm1_lvl_core (dt)
+
+      use ice_atmo, only: calc_strair, atmbndy, formdrag, highfreq, natmiter, Cdn_atm, Cdn_atm_ratio
+      use ice_blocks, only: nx_block, ny_block
+      use ice_calendar, only: yday
+      use ice_constants, only: rhos, Lfresh, Tocnfrz, ice_ref_salinity, hs_min, cp_ice, puny
+      use ice_domain_size, only: ncat, nilyr, nslyr, max_ntrcr, max_blocks
+      use ice_dyn_evp, only: evpk_context
+      use ice_exit, only: abort_ice
+      use ice_fileunits, only: nu_diag
+      use ice_flux, only: frzmlt, sst, Tf, strocnxT, strocnyT, rside, meltsn, melttn, meltbn, congeln, snoicen, dsnown, uatm, vatm, &
+          wind, rhoa, potT, Qa, zlvl, flatn, fsensn, fsurfn, fcondtopn, flw, fsnow, fpond, sss, mlt_onset, frz_onset, frain, Tair, &
+          strairxT, strairyT, fsurf, fcondtop, fsens, flat, fswabs, flwout, evap, Tref, Qref, Uref, fresh, fsalt, fhocn, fswthru, &
+          meltt, melts, meltb, congel, snoice
+      use ice_grid, only: lmask_n, lmask_s
+      use ice_itd, only: hi_min
+      use ice_meltpond_lvl, only: ffracn, dhsn, rfracmin, rfracmax, dpscale, pndaspect, frzpnd
+      use ice_shortwave, only: fswsfcn, fswintn, fswthrun, Sswabsn, Iswabsn
+      use ice_state, only: aice, aicen, aice_init, aicen_init, vicen_init, vicen, vsnon, ntrcr, trcrn, nt_Tsfc, nt_qice, nt_qsno, &
+          nt_sice, nt_alvl, nt_apnd, nt_hpnd, nt_ipnd, nt_iage, nt_FY, tr_iage, tr_FY, tr_aero, tr_pond_cesm, tr_pond_lvl, tr_pond_topo
+      use ice_therm_shared, only: ktherm, calc_Tsfc, heat_capacity, l_brine, conduct, Tmin
+      use ice_therm_vertical, only: ustar_min, chio, fbot_xfer_type
+      use ice_zbgc_shared, only: min_salin
+
+      real (kind=dbl_kind), intent(in) :: dt                 ! time step
+
+      type (evpk_therm1_args) :: a
+      type (evpk_pond_lvl_args) :: p
+      type (c_ptr) :: ctx
+      integer (c_int) :: rc
+      integer (c_int32_t) :: stop(5)
+
+      ctx = evpk_context ()
+      if (.not. c_associated(ctx)) call abort_ice('step_therm1: no context on the device: evp has not run yet')
+
+      if (.not. allocated(flwoutn_w)) then
+         allocate (flwoutn_w(nx_block,ny_block,ncat,max_blocks), evapn_w(nx_block,ny_block,ncat,max_blocks), &
+                   freshn_w(nx_block,ny_block,ncat,max_blocks), fsaltn_w(nx_block,ny_block,ncat,max_blocks), &
+                   fhocnn_w(nx_block,ny_block,ncat,max_blocks), lmask_n_w(nx_block,ny_block,max_blocks), &
+                   lmask_s_w(nx_block,ny_block,max_blocks))
+         lmask_n_w = merge(1_c_int32_t, 0_c_int32_t, lmask_n)
+         lmask_s_w = merge(1_c_int32_t, 0_c_int32_t, lmask_s)
+      endif
+
+      a%tv%dt = dt;  a%tv%yday = yday
+      a%tv%ktherm = int(ktherm, c_int32_t)
+      a%tv%calc_Tsfc = merge(1_c_int32_t, 0_c_int32_t, calc_Tsfc)
+      a%tv%heat_capacity = merge(1_c_int32_t, 0_c_int32_t, heat_capacity)
+      a%tv%l_brine = merge(1_c_int32_t, 0_c_int32_t, l_brine)
+      a%tv%conduct = merge(1_c_int32_t, 0_c_int32_t, trim(conduct) == 'bubbly')
+      a%tv%min_salin = min_salin
+      a%tv%ncat = int(ncat, c_int32_t);  a%tv%ntrcr = int(ntrcr, c_int32_t);  a%tv%ntrcr_dim = int(max_ntrcr, c_int32_t)
+      a%tv%t%nt_Tsfc = int(nt_Tsfc, c_int32_t);  a%tv%t%nt_qice = int(nt_qice, c_int32_t);  a%tv%t%nilyr = int(nilyr, c_int32_t)
+      a%tv%t%nt_qsno = int(nt_qsno, c_int32_t);  a%tv%t%nslyr = int(nslyr, c_int32_t)
+      a%tv%t%nt_alvl = int(nt_alvl, c_int32_t);  a%tv%t%nt_apnd = int(nt_apnd, c_int32_t);  a%tv%t%nt_hpnd = int(nt_hpnd, c_int32_t)
+      a%tv%t%tr_pond_cesm = merge(1_c_int32_t, 0_c_int32_t, tr_pond_cesm)
+      a%tv%t%tr_pond_lvl = merge(1_c_int32_t, 0_c_int32_t, tr_pond_lvl)
+      a%tv%t%tr_pond_topo = merge(1_c_int32_t, 0_c_int32_t, tr_pond_topo)
+      a%tv%nt_sice = int(nt_sice, c_int32_t)
+      a%tv%k%Tocnfrz = Tocnfrz;  a%tv%k%ice_ref_salinity = ice_ref_salinity;  a%tv%k%hs_min = hs_min;  a%tv%k%cp_ice = cp_ice
+      a%tv%k%Lfresh = Lfresh;  a%tv%k%Tmin = Tmin;  a%tv%k%puny = puny
+      a%tv%aicen = loc_r8(aicen);  a%tv%vicen = loc_r8(vicen);  a%tv%vsnon = loc_r8(vsnon);  a%tv%trcrn = loc_r8(trcrn)
+      a%tv%flw = loc_r8(flw);  a%tv%potT = loc_r8(potT);  a%tv%Qa = loc_r8(Qa);  a%tv%rhoa = loc_r8(rhoa);  a%tv%fsnow = loc_r8(fsnow)
+      a%tv%sss = loc_r8(sss)
+      a%tv%fswsfcn = loc_r8(fswsfcn);  a%tv%fswintn = loc_r8(fswintn);  a%tv%Sswabsn = loc_r8(Sswabsn);  a%tv%Iswabsn = loc_r8(Iswabsn)
+      a%tv%fpond = loc_r8(fpond);  a%tv%mlt_onset = loc_r8(mlt_onset);  a%tv%frz_onset = loc_r8(frz_onset)
+      a%tv%flwoutn = c_loc(flwoutn_w);  a%tv%evapn = c_loc(evapn_w);  a%tv%freshn = c_loc(freshn_w);  a%tv%fsaltn = c_loc(fsaltn_w)
+      a%tv%fhocnn = c_loc(fhocnn_w)
+      a%tv%fsensn = loc_r8(fsensn);  a%tv%flatn = loc_r8(flatn);  a%tv%fsurfn = loc_r8(fsurfn);  a%tv%fcondtopn = loc_r8(fcondtopn)
+      a%tv%melttn = loc_r8(melttn);  a%tv%meltsn = loc_r8(meltsn);  a%tv%meltbn = loc_r8(meltbn);  a%tv%congeln = loc_r8(congeln)
+      a%tv%snoicen = loc_r8(snoicen);  a%tv%dsnown = loc_r8(dsnown)
+
+      a%aice = loc_r8(aice);  a%frzmlt = loc_r8(frzmlt);  a%sst = loc_r8(sst);  a%Tf = loc_r8(Tf)
+      a%strocnxT = loc_r8(strocnxT);  a%strocnyT = loc_r8(strocnyT);  a%uatm = loc_r8(uatm);  a%vatm = loc_r8(vatm)
+      a%wind = loc_r8(wind);  a%zlvl = loc_r8(zlvl);  a%frain = loc_r8(frain)
+      a%fswthrun = loc_r8(fswthrun)
+      a%lmask_n = c_loc(lmask_n_w);  a%lmask_s = c_loc(lmask_s_w)
+      a%Cdn_atm = loc_r8(Cdn_atm)
+      a%rside = loc_r8(rside);  a%aice_init = loc_r8(aice_init);  a%aicen_init = loc_r8(aicen_init);  a%vicen_init = loc_r8(vicen_init)
+      a%strairxT = loc_r8(strairxT);  a%strairyT = loc_r8(strairyT);  a%Cdn_atm_ratio = loc_r8(Cdn_atm_ratio)
+      a%fsurf = loc_r8(fsurf);  a%fcondtop = loc_r8(fcondtop);  a%fsens = loc_r8(fsens);  a%flat = loc_r8(flat)
+      a%fswabs = loc_r8(fswabs);  a%flwout = loc_r8(flwout);  a%evap = loc_r8(evap)
+      a%Tref = loc_r8(Tref);  a%Qref = loc_r8(Qref);  a%Uref = loc_r8(Uref)
+      a%fresh = loc_r8(fresh);  a%fsalt = loc_r8(fsalt);  a%fhocn = loc_r8(fhocn);  a%fswthru = loc_r8(fswthru)
+      a%meltt = loc_r8(meltt);  a%meltb = loc_r8(meltb);  a%melts = loc_r8(melts);  a%congel = loc_r8(congel);  a%snoice = loc_r8(snoice)
+      a%chio = chio;  a%ustar_min = ustar_min;  a%hi_min = hi_min;  a%pndaspect = pndaspect
+      a%rfracmin = rfracmin;  a%rfracmax = rfracmax
+      a%natmiter = int(natmiter, c_int32_t)
+      a%calc_strair = merge(1_c_int32_t, 0_c_int32_t, calc_strair)
+      a%tr_iage = merge(1_c_int32_t, 0_c_int32_t, tr_iage);  a%tr_FY = merge(1_c_int32_t, 0_c_int32_t, tr_FY)
+      a%nt_iage = int(nt_iage, c_int32_t);  a%nt_FY = int(nt_FY, c_int32_t)
+      a%formdrag = merge(1_c_int32_t, 0_c_int32_t, formdrag);  a%highfreq = merge(1_c_int32_t, 0_c_int32_t, highfreq)
+      a%atmbndy_constant = merge(1_c_int32_t, 0_c_int32_t, trim(atmbndy) == 'constant')
+      a%fbot_xfer_Cdn_ocn = merge(1_c_int32_t, 0_c_int32_t, trim(fbot_xfer_type) == 'Cdn_ocn')
+      a%tr_aero = merge(1_c_int32_t, 0_c_int32_t, tr_aero)
+
+      p%dhsn = loc_r8(dhsn);  p%ffracn = loc_r8(ffracn);  p%Tair = loc_r8(Tair)
+      p%dpscale = dpscale
+      p%frzpnd = merge(1_c_int32_t, 0_c_int32_t, trim(frzpnd) == 'hlid')
+      p%nt_ipnd = int(nt_ipnd, c_int32_t)
+
+      rc = evpk_step_therm1_lvl (ctx, a, p, stop)
+      if (rc == EVPK_THERMO_STOP) then
+         write (nu_diag,*) 'evpk_step_therm1_lvl: vertical thermo error, reason', stop(1), ' local block', stop(2), &
+                           ' category', stop(3), ' i, j =', stop(4), stop(5)
+         call abort_ice ('ice: Vertical thermo error')
+      endif
+      if (rc /= 0) call abort_ice('step_therm1: evpk_step_therm1_lvl: '//trim(evpk_error_string(ctx)))
+
+      end subroutine evpk_step_therm1_lvl_core
 
 !=======================================================================
 

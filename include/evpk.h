@@ -925,6 +925,68 @@ typedef struct {
 int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a);
 int evpk_dedd_table(const char *name, double *out, int32_t n);
 
+/* Level-ice melt ponds (tr_pond_lvl): the pond scheme every ice_in of the reference's own grids selects, with shortwave = 'dEdd', tr_lvl
+ * and frzpnd = 'hlid' (reference/input_templates/{gx1,gx3,tp1,col}/ice_in).  evpk_step_therm1 and evpk_step_radiation_dedd keep refusing
+ * tr_pond_lvl; a host on that scheme calls the two entry points below, which do everything their parents do and run
+ *
+ * evpk_step_therm1_lvl: compute_ponds_lvl with brine_permeability (source/ice_meltpond_lvl.F90:79-404) in the place of
+ * compute_ponds_cesm, per category at the reference's call site (source/ice_step_mod.F90:623-642; the LVL instantiations of
+ * k_therm1_merge, csrc/evpk_therm1s.hip), rfrac = rfracmin + (rfracmax - rfracmin) aicen, on the state thermo_vertical left:
+ *   before the list    ffracn = 0 on EVERY cell of the block arrays, ghost cells and land included (:175-181); volpn = hpnd aicen alvl apnd
+ *   cell list          the routine's own (:187-196): physical cells with aicen alvl > puny**2, AND tmask (the departure of every column
+ *                      kernel here).  No aicen > puny test: it can list a cell that the thermodynamics does not
+ *   on listed cells    hi < hi_min removes the pond and the lid (:206-215); the melt-water line dvn (:228-230); frzpnd = 0 'cesm': Tp =
+ *                      Timelt - Td, dvn = dvn - volpn (1 - exp(rexp dTs / Tp)) (:233-236); frzpnd = 1 'hlid' (:238-267): hlid = ipnd; with
+ *                      dvn == 0 and Ts = Tair - Tffresh < 0 the Stefan growth bdt = -2 Ts kice dt / (rhoi Lfresh), dhlid = sqrt(bdt) / 2
+ *                      from open water or bdt / (2 hlid) on an existing lid, clamped by hpnd rhofresh / rhoi; with Ts >= 0 dhlid = 0; with
+ *                      dvn /= 0 the lid melts by max(fsurfn dt / (rhoi Lfresh), 0) and, where hs - dhsn < puny (snow-free pond ice),
+ *                      ffracn = 1 or, under fsurfn > puny, min(-dhlid rhoi Lfresh / (dt fsurfn), 1); dvn = dvn - dhlid alid rhoi / rhofresh;
+ *                      volpn <= 0 (:274-277); existing ponds under apondn aicen > puny, new ponds under alvl aicen > 10 puny, else run-off
+ *                      (:279-294); the freeboard limit hpondn <= ((rhow - rhoi) hi - rhos hs) / rhofresh (:297), which zeroes pond and
+ *                      lid where it is not positive (:303-308); the drainage (:316-331) under hpondn > 0 and dpscale > puny -- ktherm is 1
+ *                      here, evpk_thermo_vertical refuses anything else: calculate_Tin_from_qin under l_brine
+ *                      (source/ice_therm_shared.F90:62-90), Sbr, phi with phi < 0.05 impermeable, perm = 3e-8 minval(phi)**3, drain =
+ *                      perm pressure_head dt / (viscosity_dyn hi) dpscale, and the area and depth update after it; the nilyr enthalpy and
+ *                      nilyr salinity planes are read only behind that test; the reload (:339-341): hpnd, apnd = apondn / (aicen alvl),
+ *                      ipnd only under 'hlid'
+ * evpk_step_radiation_dedd_lvl: the tr_pond_lvl block of run_dEdd (source/ice_shortwave.F90:1450-1514) in the place of the tr_pond_cesm
+ * lines, on the list of k_shortwave_dedd (its LVL instantiations, csrc/evpk_dedd.hip): ipn = alvl apnd ipnd; dhs = dhsn, initialised to
+ * hsn - fsnow dt where ipn > puny, dhs < puny and fsnow dt > hs_min, reset to 0 where ipn spn < puny (spn = hsn - dhs), both steps
+ * skipped under linitonly, stored back into dhsn on the listed cells; fpn = apnd alvl, hpn = hpnd; fpn = (1 - ffracn) fpn; the taper
+ * (1 - min(spn / hs1, 1)) under dhs > puny, spn >= puny, hs1 > puny; the infiltration under hp > puny: rp = rhofresh hp / (rhofresh hp +
+ * rhos hs), rp < p15 hides the pond, otherwise tmp = max(0, sign(1, hp - hmx)), hp, and hsn = hs - hp fpn (1 - tmp) -- the modified hsn is
+ * what shortwave_dEdd then receives; fpn = 0 under hpn < hpmin; fsn = min(fsn, 1 - fpn); apeffn = fpn; snowfracn = fsn.
+ * Operation order: the Fortran's; min / max are a comparison and a select; sign is copysign-exact; x**3 is x*x*x; exp is dev_exp; sqrt is
+ * the IEEE one.  Compiled in: Td = 2, rexp = 0.01 (source/ice_meltpond_lvl.F90:167-169); viscosity_dyn = 1.79e-3, kice = 2.03, gravit =
+ * 9.80616, depressT = 0.054, cp_ocn = 4218, Tffresh = 273.15, rhofresh = 1000, Timelt = 0 (drivers/cice/ice_constants.F90:42, :71, :36,
+ * :31, :29, :50, :45, :54); the permeability's 3e-8, 1e-3 and 0.05 (source/ice_meltpond_lvl.F90:393-402); hs_min = 1e-4
+ * (drivers/auscom/ice_constants.F90:91), hpmin = 0.005 (source/ice_shortwave.F90:143), p15 = 0.15 (drivers/cice/ice_constants.F90:139).
+ * rhoi, rhos, rhow are evpk_set_params'; cp_ice, Lfresh, puny come from tv.k.
+ * **Parity unpinned**: no recipe under oracle/ builds these routines; both calls are held bit for bit to a numpy restatement written
+ * from the Fortran (tests/nppondlvl.py, on top of tests/nptherm1s.py and tests/npdedd.py).
+ * evpk_pond_lvl_args: what the two routines hand each other, and the scheme's own namelist --
+ *   dhsn     per category: the shortwave reads and writes it (listed cells), the thermodynamics reads it
+ *   ffracn   per category: the thermodynamics writes it on every cell, the shortwave reads it
+ *   Tair     2-D, in, read by the thermodynamics only (may be NULL for the shortwave)
+ *   fsnow    2-D, in, read by the shortwave only (may be NULL for the thermodynamics, whose own fsnow is tv.fsnow)
+ *   dpscale, hs1 (source/ice_init.F90:299-300: defaults 1, 0.03; the shipped ice_in set dpscale = 1e-3), dt -- the shortwave's, read by it only; frzpnd 0 'cesm' / 1 'hlid'; nt_ipnd; linitonly (the
+ *   shortwave's initonly).  nt_alvl, nt_apnd, nt_hpnd are those of the evpk_itd_tracers of the parent's struct.
+ * evpk_step_therm1_lvl needs frain.  Host arrays and device pointers both work, staged once with the parent's.
+ * Both return what their parents return; or 1 with evpk_last_error, before any copy, touching nothing: tr_pond_lvl unset; nt_alvl,
+ * nt_apnd, nt_hpnd or nt_ipnd missing or beyond ntrcr; frzpnd outside 0..1; a missing dhsn, ffracn, Tair (thermodynamics) or fsnow
+ * (shortwave); pndaspect <= 0 or frain missing (thermodynamics); dt <= 0 (shortwave); everything the parent refuses (tr_pond_cesm set
+ * beside tr_pond_lvl included).  x-slab ranks: not collective, as the parents are not.
+ * Out of scope: tr_pond_topo, ktherm = 2, the pond restart records. */
+#define EVPK_HAS_POND_LVL 1
+typedef struct {
+    double *dhsn, *ffracn;                                                    /* in / out, per category */
+    const double *Tair, *fsnow;                                               /* in, 2-D */
+    double dpscale, hs1, dt;
+    int32_t frzpnd, nt_ipnd, linitonly;
+} evpk_pond_lvl_args;
+int evpk_step_therm1_lvl(evpk_ctx *c, const evpk_therm1_args *a, const evpk_pond_lvl_args *p, int32_t stop[5]);
+int evpk_step_radiation_dedd_lvl(evpk_ctx *c, const evpk_dedd_args *a, const evpk_pond_lvl_args *p);
+
 /* the elastic-anisotropic-plastic rheology, eap(dt) (source/ice_dyn_eap.F90:66-486; kdyn = 2,
  * ice_step_mod.F90:1118).  eap is evp with another stress: evp_prep1/2, stepu, the velocity halo, evp_finish are shared
  * (:79-80), stress_eap (:1052-1467) with update_stress_rdg (:1474-1658) takes the place of stress, stepa (:1664-1787, with

@@ -1,0 +1,360 @@
+"""evpk_step_therm1_lvl and evpk_step_radiation_dedd_lvl on the device against the numpy restatement tests/nppondlvl.py -- bit for bit, on every
+cell of every array either call may write: ghost cells, land and the ice-free block included (ffracn is written everywhere; dhsn, the
+tracer planes and every other in / out array keep the caller's bits wherever the cell is not listed).  The kernels use + - x /, the IEEE
+sqrt, comparisons, selects, copysign and the fixed-algorithm math of their parents, and the library is built with -ffp-contract=off.
+**Parity with the reference is unpinned** (no reference-built record).  Inputs: tests/golden/pondlvlvec.py (no shape larger than 26 x 18
+cells); tests/test_pondlvl_host.py shows that they take every branch.
+"""
+import os
+import sys
+import traceback
+import uuid
+
+import numpy as np
+import pytest
+
+try:
+    import torch          # before libevpk: the process must end up with ONE HIP runtime (torch bundles its own)
+    torch.cuda.is_available()
+except ImportError:
+    torch = None
+
+from cice5_amd import evpk
+from tests import nppondlvl
+from tests.golden import deddvec as dv
+from tests.golden import itdvec as iv
+from tests.golden import pondlvlvec as pv
+from tests.golden import therm1svec as sv
+from tests.test_pondlvl_host import (CFG, DT_SW, SW_ALL, TH_READ, TH_WRITTEN, inputs, sw_arrays, sw_params, sw_restated, th_arrays, th_input,
+                                     th_restated)
+from tests.test_therm1_gpu import eq, geometry, params
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OTHER = [c for c in pv.CONFIGS if c != CFG][0]
+TH_ALL = TH_WRITTEN + ["dhsn"]
+
+
+@pytest.fixture(scope="module")
+def contexts():
+    made = {}
+
+    def get(cfg):
+        if cfg not in made:
+            x = inputs(cfg, "plain")
+            _, d, f = geometry(cfg)
+            f["tmask"] = x["tmask"]                 # the land of the inputs
+            made[cfg] = evpk.Context(d, f)
+            made[cfg].set_params(params(x))
+        return made[cfg]
+    yield get
+    for c in made.values():
+        c.close()
+
+
+def call_sw(ctx, x, y, linitonly=0, ponds=None, lvl=True, **kw):
+    g = lambda k: y[k] if k in y else x.get(k)
+    a = dict(ntrcr=x["ntrcr"], tracers=x["tracers"])
+    a.update({k: x[k] for k in evpk.DEDD_SCALARS})
+    a.update(kw)
+    args = ({k: g(k) for k in evpk.DEDD_STATE}, {k: g(k) for k in evpk.DEDD_FORCING}, g("coszen"), {k: g(k) for k in dv.WRITTEN})
+    if not lvl:
+        return ctx.step_radiation_dedd(*args, **a)
+    p = dict(dhsn=g("dhsn"), ffracn=g("ffracn"), fsnow=g("fsnow"), hs1=x["hs1"])
+    p.update(ponds or {})
+    return ctx.step_radiation_dedd_lvl(DT_SW, *args, p, linitonly=linitonly, **a)
+
+
+def call_th(ctx, x, y, frzpnd="hlid", dpscale=1.0e-3, ponds=None, lvl=True, **kw):
+    g = lambda k: y[k] if k in y else x.get(k)
+    a = dict(ntrcr=x["ntrcr"], tracers=x["tracers"], yday=x["yday"], min_salin=x["min_salin"], constants=x["k"], hi_min=x["hi_min"])
+    a.update({k: x[k] for k in sv.SCALARS})
+    a.update(kw)
+    forcing = {k: g(k) for k in evpk.THERMO_FORCING + evpk.THERM1_IN2D + ["fswthrun"] + evpk.THERM1_MASKS}
+    args = (x["dt"], {k: g(k) for k in evpk.THERMO_STATE}, forcing, {k: g(k) for k in evpk.THERMO_INOUT},
+            {k: g(k) for k in evpk.THERMO_OUT + evpk.THERM1_OUT + evpk.THERM1_DIAG}, {k: g(k) for k in ["Cdn_atm"] + evpk.THERM1_MERGED})
+    if not lvl:
+        return ctx.step_therm1(*args, **a)
+    p = dict(dhsn=g("dhsn"), ffracn=g("ffracn"), Tair=g("Tair"), frzpnd=frzpnd, dpscale=dpscale)
+    p.update(ponds or {})
+    return ctx.step_therm1_lvl(*args, p, **a)
+
+
+def th_outputs(x):
+    return {k: (x[k].copy() if x[k] is not None else None) for k in TH_ALL}
+
+
+def assert_same(got, want, names):
+    for k in names:
+        if want.get(k) is None:
+            continue
+        assert eq(got[k], want[k]), (k, int((got[k] != want[k]).sum()))
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a).copy()).cuda()
+
+
+@pytest.mark.parametrize("tcase", list(pv.TABLES))
+@pytest.mark.parametrize("frzpnd", pv.FRZPND)
+@pytest.mark.parametrize("dpscale", pv.DPSCALES)
+def test_therm1_lvl_equals_the_restatement_on_every_cell(contexts, tcase, frzpnd, dpscale):
+    """both tables (ncat 5: k_therm1_merge<5, 1>; ncat 3: <0, 1>), both frzpnd, dpscale 0, 1e-3 and 1: every array the call may write and
+    dhsn, on every cell -- ffracn, pre-filled with non-zero draws, is zero wherever the routine leaves it; the pond tracers move"""
+    x, want, _ = th_restated(CFG, tcase, frzpnd, dpscale)
+    y = th_outputs(x)
+    assert call_th(contexts(CFG), x, y, frzpnd, dpscale) is None
+    assert_same(y, want, TH_ALL)
+    tr = x["tracers"]
+    assert (x["ffracn"] != 0.0).mean() > 0.4 and eq(y["dhsn"], x["dhsn"])
+    assert (y["ffracn"] != 0.0).any() == (frzpnd == "hlid") and not y["ffracn"][~x["ocean"][:, None].repeat(x["aicen"].shape[1], 1)].any()
+    for q in ("nt_apnd", "nt_hpnd"):
+        assert not eq(y["trcrn"][:, :, tr[q] - 1], x["trcrn"][:, :, tr[q] - 1]), q
+    assert eq(y["trcrn"][:, :, tr["nt_ipnd"] - 1], x["trcrn"][:, :, tr["nt_ipnd"] - 1]) == (frzpnd == "cesm")
+
+
+@pytest.mark.parametrize("tcase,frzpnd,dpscale", [("plain", "hlid", 1.0e-3), ("deep", "cesm", 1.0)])
+def test_therm1_lvl_on_the_other_grid(contexts, tcase, frzpnd, dpscale):
+    x, want, _ = th_restated(OTHER, tcase, frzpnd, dpscale)
+    y = th_outputs(x)
+    assert call_th(contexts(OTHER), x, y, frzpnd, dpscale) is None
+    assert_same(y, want, TH_ALL)
+
+
+@pytest.mark.parametrize("cfg", list(pv.CONFIGS))
+@pytest.mark.parametrize("tcase", list(pv.TABLES))
+@pytest.mark.parametrize("linitonly", [0, 1])
+def test_radiation_lvl_equals_the_restatement_on_every_cell(contexts, cfg, tcase, linitonly):
+    """both grids, both tables (k_shortwave_dedd<5, 4, 1, 1> and <0, 0, 0, 1>), linitonly 0 and 1: every output, coszen and dhsn on every
+    cell; under linitonly dhsn keeps the caller's bits"""
+    x, want, _, _ = sw_restated(cfg, tcase, linitonly)
+    y = {k: x[k].copy() for k in SW_ALL}
+    assert call_sw(contexts(cfg), x, y, linitonly) is None
+    assert_same(y, want, SW_ALL)
+    assert eq(y["dhsn"], x["dhsn"]) == bool(linitonly)
+    listed = (x["aicen"] > pv.PUNY) & x["ocean"][:, None]
+    assert eq(y["dhsn"][~listed], x["dhsn"][~listed]) and y["apeffn"][listed].any() and not y["apeffn"][~listed].any()
+
+
+@pytest.mark.parametrize("tcase", list(pv.TABLES))
+def test_device_pointers_and_pageable_arrays_agree(contexts, tcase):
+    ctx = contexts(CFG)
+    x, want, _, _ = sw_restated(CFG, tcase)
+    dev = {k: _dev(x[k]) for k in set(dv.STATE + dv.FORCING + SW_ALL + ["ffracn", "fsnow"])}
+    assert call_sw(ctx, x, dev) is None
+    torch.cuda.synchronize()
+    assert_same({k: dev[k].cpu().numpy() for k in SW_ALL}, want, SW_ALL)
+    x, want, _ = th_restated(CFG, tcase, "hlid", 1.0e-3)
+    names = [k for k in TH_ALL + TH_READ if isinstance(x.get(k), np.ndarray)]
+    dev = {k: _dev(x[k]) for k in set(names)}
+    assert call_th(ctx, x, dev) is None
+    torch.cuda.synchronize()
+    assert_same({k: dev[k].cpu().numpy() for k in TH_ALL}, want, TH_ALL)
+    for k in ("dhsn", "Tair", "frain"):
+        assert eq(dev[k].cpu().numpy(), x[k]), k
+
+
+def test_chain_on_device_pointers_hands_ffracn_and_dhsn_over(contexts):
+    """radiation_lvl (linitonly) -> therm1_lvl -> radiation_lvl -> therm1_lvl -> radiation_lvl on device tensors that never visit the host,
+    against the same chain of the restatement: every array on every cell.  ffracn goes from the thermodynamics to the shortwave, dhsn the
+    other way, the radiation arrays and the state both ways"""
+    ctx = contexts(CFG)
+    x = inputs(CFG, "plain")
+    blocks = iv.blocks_of(x["d"])
+    w = dict(th_arrays(x), **sw_arrays(x))
+    w.update({k: x[k].copy() for k in set(TH_ALL + SW_ALL)})
+    w.update({k: sw_restated(CFG, "plain", 1)[1][k].copy() for k in SW_ALL})            # the first call: shared with the tests above
+    pt = nppondlvl.therm_params(x, "hlid", 1.0e-3)
+    for step in range(1, 5):
+        if step % 2 == 0:
+            nppondlvl.step_radiation_dedd_lvl(blocks, x["tmask"], sw_params(x), w)
+        else:
+            assert nppondlvl.step_therm1_lvl(blocks, x["tmask"], pt, w)[1] is None
+    names = [k for k in set(TH_ALL + TH_READ + SW_ALL + dv.STATE + dv.FORCING) if isinstance(x.get(k), np.ndarray)]
+    dev = {k: _dev(x[k]) for k in names}
+    for step in range(5):
+        if step % 2 == 0:
+            assert call_sw(ctx, x, dev, linitonly=int(step == 0)) is None
+        else:
+            assert call_th(ctx, x, dev) is None
+    torch.cuda.synchronize()
+    got = {k: dev[k].cpu().numpy() for k in set(TH_ALL + SW_ALL)}
+    assert_same(got, w, sorted(set(TH_ALL + SW_ALL)))
+    assert not eq(got["ffracn"], x["ffracn"]) and not eq(got["dhsn"], x["dhsn"])
+    one = sw_restated(CFG, "plain", 1)[1]
+    assert not eq(got["apeffn"], one["apeffn"])                        # (the later calls saw what the thermodynamics left)
+
+
+@pytest.mark.parametrize("tcase", list(pv.TABLES))
+def test_without_ponds_the_calls_are_their_parents(contexts, tcase):
+    """apnd = 0: the level-ice shortwave call equals evpk_step_radiation_dedd under tr_pond_cesm on every output; the non-pond outputs of
+    evpk_step_therm1_lvl equal evpk_step_therm1 without a pond scheme"""
+    ctx = contexts(CFG)
+    x = inputs(CFG, tcase)
+    tr = x["tracers"]
+    t = x["trcrn"].copy()
+    t[:, :, tr["nt_apnd"] - 1] = 0.0
+    y = {k: x[k].copy() for k in SW_ALL}
+    y["trcrn"] = t
+    assert call_sw(ctx, x, y) is None
+    z = {k: x[k].copy() for k in SW_ALL}
+    z["trcrn"] = t
+    assert call_sw(ctx, x, z, lvl=False, tracers=dict(tr, tr_pond_cesm=1, tr_pond_lvl=0)) is None
+    assert_same(y, z, dv.WRITTEN + ["coszen"])
+    assert y["fswsfcn"].any() and not y["apeffn"].any()
+    x = th_input(CFG, tcase)
+    y, z = th_outputs(x), th_outputs(x)
+    assert call_th(ctx, x, y) is None
+    assert call_th(ctx, x, z, lvl=False, tracers=dict(tr, tr_pond_lvl=0)) is None
+    ponds = [tr[k] - 1 for k in ("nt_apnd", "nt_hpnd", "nt_ipnd")]
+    rest = [k for k in range(x["trcrn"].shape[2]) if k not in ponds]
+    for k in sv.WRITTEN:
+        if y[k] is None:
+            continue
+        a, b = (y[k][:, :, rest], z[k][:, :, rest]) if k == "trcrn" else (y[k], z[k])
+        assert eq(a, b), k
+    assert not eq(y["trcrn"], z["trcrn"]) and eq(z["ffracn"], x["ffracn"])
+
+
+def _refused(fn, ctx, x, y, match, **kw):
+    with pytest.raises(evpk.EvpkError, match=match):
+        fn(ctx, x, y, **kw)
+    return True
+
+
+def test_refusals_leave_the_arrays_untouched(contexts):
+    ctx = contexts(CFG)
+    x = th_input(CFG, "plain")
+    tr = x["tracers"]
+    n = x["ntrcr"]
+    y = th_outputs(x)
+    R = lambda match, xx=x, yy=y, **kw: _refused(call_th, ctx, xx, yy, "evpk_step_therm1_lvl: .*" + match, **kw)
+    R("tr_pond_lvl is not set", tracers=dict(tr, tr_pond_lvl=0))
+    R("tr_pond_cesm is set beside tr_pond_lvl", tracers=dict(tr, tr_pond_cesm=1))
+    for k in ("nt_alvl", "nt_apnd", "nt_hpnd", "nt_ipnd"):
+        R("tr_pond_lvl without nt_alvl / nt_apnd / nt_hpnd / nt_ipnd", tracers=dict(tr, **{k: 0}))
+        R("tr_pond_lvl without nt_alvl / nt_apnd / nt_hpnd / nt_ipnd", tracers=dict(tr, **{k: n + 1}))
+    R("frzpnd = 2", frzpnd=2)
+    R("frzpnd = -1", frzpnd=-1)
+    R("needs dhsn and ffracn", yy=dict(y, dhsn=None))
+    R("needs dhsn and ffracn", yy=dict(y, ffracn=None))
+    R("needs Tair", xx=dict(x, Tair=None))
+    R("needs frain", xx=dict(x, frain=None))
+    R("pndaspect = 0", pndaspect=0.0)
+    R("only ktherm = 1", ktherm=2)                                  # what the parent refuses
+    R("tr_pond_topo", tracers=dict(tr, tr_pond_topo=1))
+    R("formdrag", formdrag=True)
+    R("aerosol", tr_aero=True)
+    R("a required argument is missing", yy=dict(y, aicen=None))
+    R("a required argument is missing", xx=dict(x, fswthrun=None))
+    for k in TH_ALL:
+        if y[k] is not None:
+            assert eq(y[k], x[k]), k
+    with pytest.raises(evpk.EvpkError, match=r"evpk_step_therm1: tr_pond_lvl \(compute_ponds_lvl\) is not supported"):
+        call_th(ctx, x, y, lvl=False)
+    x = inputs(CFG, "plain")
+    y = {k: x[k].copy() for k in SW_ALL}
+    R = lambda match, xx=x, yy=y, **kw: _refused(call_sw, ctx, xx, yy, "evpk_step_radiation_dedd_lvl: .*" + match, **kw)
+    R("tr_pond_lvl is not set", tracers=dict(tr, tr_pond_lvl=0))
+    R("tr_pond_cesm is set beside tr_pond_lvl", tracers=dict(tr, tr_pond_cesm=1))
+    for k in ("nt_alvl", "nt_apnd", "nt_hpnd", "nt_ipnd"):
+        R("tr_pond_lvl without nt_alvl / nt_apnd / nt_hpnd / nt_ipnd", tracers=dict(tr, **{k: 0}))
+        R("tr_pond_lvl without nt_alvl / nt_apnd / nt_hpnd / nt_ipnd", tracers=dict(tr, **{k: n + 1}))
+    R("frzpnd = 2", ponds=dict(frzpnd=2))
+    R("needs dhsn and ffracn", yy=dict(y, dhsn=None))
+    R("needs dhsn and ffracn", xx=dict(x, ffracn=None))
+    R("needs fsnow", xx=dict(x, fsnow=None))
+    R("calc_Tsfc", calc_Tsfc=False)                                 # what the parent refuses
+    R("tr_aero", tr_aero=True)
+    R("tr_pond_topo", tracers=dict(tr, tr_pond_topo=1))
+    R("dT_mlt = 0", dT_mlt=0.0)
+    R("a required argument is missing", xx=dict(x, swvdr=None))
+    R("a required argument is missing", yy=dict(y, apeffn=None))
+    for k in SW_ALL:
+        assert eq(y[k], x[k]), k
+    with pytest.raises(evpk.EvpkError, match=r"evpk_step_radiation_dedd: tr_pond_lvl \(dhsn, ffracn\) is not supported"):
+        call_sw(ctx, x, y, lvl=False)
+    with pytest.raises(evpk.EvpkError, match=r"evpk_step_radiation_dedd_lvl: dt = 0"):
+        ctx.step_radiation_dedd_lvl(0.0, {k: x[k] for k in evpk.DEDD_STATE}, {k: x[k] for k in evpk.DEDD_FORCING}, y["coszen"],
+                                    {k: y[k] for k in dv.WRITTEN}, dict(dhsn=y["dhsn"], ffracn=x["ffracn"], fsnow=x["fsnow"]),
+                                    ntrcr=n, tracers=tr)
+    for k in SW_ALL:
+        assert eq(y[k], x[k]), k
+
+
+# ---- x-slab ranks: one process per rank on one GPU (the harness of tests/test_therm1s_gpu.py) ----
+def both_calls(ctx, x, y):
+    """the shortwave, then the thermodynamics on what it left: y holds every array either call writes"""
+    assert call_sw(ctx, x, y) is None
+    return call_th(ctx, x, y)
+
+
+def job_pondlvl(rank, world, tag, tcase):
+    d1, d, f = geometry(CFG, world, rank)
+    at = {b.block_id: n for n, b in enumerate(d1.local_blocks)}
+    loc = [at[b.block_id] for b in d.local_blocks]
+    x = pv.pondlvl_input(CFG, tcase)
+    f["tmask"] = np.ascontiguousarray(x["tmask"][loc])
+    cut = lambda a: np.ascontiguousarray(a[loc])
+    ctx = evpk.Context(d, f, device=0, unique_id=(b"EVPKIPC:" + f"{tag}_0".encode()).ljust(128, b"\0"))
+    try:
+        ctx.set_params(params(x))
+        read_only = [k for k in TH_READ + dv.FORCING if isinstance(x.get(k), np.ndarray) and k != "dhsn"]
+        xx = dict(x, **{k: cut(x[k]) for k in read_only})
+        y = {k: cut(x[k]) for k in set(TH_ALL + SW_ALL)}
+        stop = both_calls(ctx, xx, y)
+    finally:
+        ctx.close()
+    return loc, y, stop
+
+
+def _worker(rank, world, tag, job, args, q):
+    try:
+        sys.path.insert(0, ROOT)
+        os.environ["OMP_NUM_THREADS"] = "2"
+        q.put((rank, None, globals()[job](rank, world, tag, *args)))
+    except Exception:
+        q.put((rank, traceback.format_exc(), None))
+
+
+def _spawn(world, job, args=(), timeout=240):
+    import multiprocessing as mp
+    assert world <= 3                              # (+ the parent: at most 4 processes hold the GPU)
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    tag = "evpk_pondlvl_" + uuid.uuid4().hex[:12]
+    procs = [ctx.Process(target=_worker, args=(r, world, tag, job, args, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = {}
+    try:
+        for _ in procs:
+            rank, err, out = q.get(timeout=timeout)
+            assert err is None, f"rank {rank}: {err}"
+            res[rank] = out
+    finally:
+        for p in procs:
+            p.join(timeout=1 if len(res) < world else 30)
+            if p.is_alive():
+                p.kill()
+        try:
+            os.unlink(f"/dev/shm/{tag}_0")
+        except OSError:
+            pass
+    return [res[r] for r in range(world)]
+
+
+def test_two_ranks_equal_one_rank(contexts):
+    """two x-slab rank processes on one GPU run the shortwave and then the thermodynamics on their own blocks: put together, their blocks
+    equal what one rank computes -- neither call is collective"""
+    tcase = "plain"
+    x = inputs(CFG, tcase)
+    one = {k: x[k].copy() for k in set(TH_ALL + SW_ALL)}
+    assert both_calls(contexts(CFG), x, one) is None
+    outs = _spawn(2, "job_pondlvl", (tcase,))
+    assert all(len(loc) > 0 and stop is None for loc, _, stop in outs)
+    assert sorted(n for loc, _, _ in outs for n in loc) == list(range(x["aicen"].shape[0]))
+    for loc, y, _ in outs:
+        assert_same(y, {k: one[k][loc] for k in y}, sorted(y))
+    assert not eq(one["ffracn"], x["ffracn"]) and not eq(one["trcrn"], x["trcrn"])

@@ -1,0 +1,235 @@
+"""The level-ice pond scheme (evpk_step_therm1_lvl, evpk_step_radiation_dedd_lvl) without a GPU: the entry points are declared, exported and
+bound (header, ctypes structure and Fortran type member by member); the inputs of tests/golden/pondlvlvec.py take every branch the numpy
+restatement tests/nppondlvl.py counts, over the union of the committed cases; and the restatement reduces to the existing checkers where
+the scheme has nothing to do.
+
+**Parity with the reference is unpinned**: no reference-built record exists for these routines.
+"""
+import ctypes as ct
+import os
+import re
+
+import numpy as np
+import pytest
+
+from cice5_amd import evpk
+from tests import npdedd, nppondlvl, nptherm1s
+from tests.golden import deddvec as dv
+from tests.golden import itdvec as iv
+from tests.golden import pondlvlvec as pv
+from tests.golden import therm1svec as sv
+from tests.test_dedd_host import params as dedd_params
+from tests.test_rad_host import _fortran_names, _struct_names
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CFG = "g26x18_b8x5"
+DT_SW = 3600.0
+SW_ALL = dv.WRITTEN + ["coszen", "dhsn"]                              # what the shortwave call writes
+TH_WRITTEN = sv.WRITTEN + ["ffracn"]                                 # what the thermodynamics call may write
+TH_READ = sv.IN2D + ["flw", "potT", "Qa", "rhoa", "fsnow", "sss", "fswthrun", "lmask_n", "lmask_s", "yday", "dhsn", "Tair"]
+
+_inputs, _sw, _base, _th = {}, {}, {}, {}
+
+
+def inputs(cfg, tcase):
+    if (cfg, tcase) not in _inputs:
+        _inputs[cfg, tcase] = pv.pondlvl_input(cfg, tcase)
+    return _inputs[cfg, tcase]
+
+
+def sw_params(x, linitonly=0, **kw):
+    p = dedd_params(x, hs1=x["hs1"], dt=DT_SW, linitonly=int(linitonly))
+    p.update(kw)
+    return p
+
+
+def sw_arrays(x, **over):
+    y = {k: x[k].copy() for k in SW_ALL}
+    y.update({k: x[k] for k in dv.STATE + dv.FORCING + ["ffracn", "fsnow"]})
+    y.update(over)
+    return y
+
+
+def sw_restated(cfg, tcase, linitonly=0):
+    """(x, arrays, npdedd's infos, the pond infos) of the shortwave on the ports: computed once per case, shared, not modified"""
+    key = (cfg, tcase, int(linitonly))
+    if key not in _sw:
+        x = inputs(cfg, tcase)
+        y = sw_arrays(x)
+        _sw[key] = (x, y) + nppondlvl.step_radiation_dedd_lvl(iv.blocks_of(x["d"]), x["tmask"], sw_params(x, linitonly), y)
+    return _sw[key]
+
+
+def th_input(cfg, tcase):
+    """the input of the thermodynamics alone: pondlvlvec's under the radiation arrays the restated shortwave leaves (the draws of dhsn
+    stay: they reach more branches than one shortwave call leaves)"""
+    x, w = sw_restated(cfg, tcase)[:2]
+    return dict(x, **{k: w[k] for k in pv.CARRIED})
+
+
+def th_arrays(x):
+    y = {k: (x[k].copy() if x[k] is not None else None) for k in TH_WRITTEN}
+    y.update({k: x[k] for k in TH_READ})
+    return y
+
+
+def th_base(cfg, tcase):
+    """nptherm1s.step with no pond scheme on the input of the thermodynamics: what every (frzpnd, dpscale) variant starts from"""
+    if (cfg, tcase) not in _base:
+        x = th_input(cfg, tcase)
+        y = th_arrays(x)
+        p = nptherm1s.params(x)
+        infos, stop, _ = nptherm1s.step(iv.blocks_of(x["d"]), x["tmask"], dict(p, tr=dict(p["tr"], tr_pond_cesm=0)), y)
+        assert stop is None, stop
+        _base[cfg, tcase] = (x, y, infos)
+    return _base[cfg, tcase]
+
+
+def th_restated(cfg, tcase, frzpnd, dpscale):
+    """(x, arrays, pond infos) of step_therm1 under tr_pond_lvl on the ports: nppondlvl.step_therm1_lvl, with its first half shared"""
+    key = (cfg, tcase, frzpnd, dpscale)
+    if key not in _th:
+        x, y0, _ = th_base(cfg, tcase)
+        y = {k: (v.copy() if isinstance(v, np.ndarray) and k in TH_WRITTEN else v) for k, v in y0.items()}
+        pinfos = nppondlvl.apply_ponds(iv.blocks_of(x["d"]), x["tmask"], nppondlvl.therm_params(x, frzpnd, dpscale), y)
+        _th[key] = (x, y, pinfos)
+    return _th[key]
+
+
+def total(infos, keys):
+    return {k: sum(i[k] for i in infos) for k in keys}
+
+
+def test_header_declares_the_entry_points():
+    hdr = open(os.path.join(ROOT, "include", "evpk.h")).read()
+    assert re.search(r"^#define EVPK_HAS_POND_LVL 1$", hdr, re.M)
+    assert re.search(r"^#define EVPK_VERSION 6$", hdr, re.M)
+    assert re.search(r"^int evpk_step_therm1_lvl\(evpk_ctx \*c, const evpk_therm1_args \*a, const evpk_pond_lvl_args \*p, int32_t stop\[5\]\);$",
+                     hdr, re.M)
+    assert re.search(r"^int evpk_step_radiation_dedd_lvl\(evpk_ctx \*c, const evpk_dedd_args \*a, const evpk_pond_lvl_args \*p\);$", hdr, re.M)
+    block = hdr[hdr.index("Level-ice melt ponds (tr_pond_lvl)"):hdr.index("#define EVPK_HAS_POND_LVL")]
+    assert "**Parity unpinned**" in block
+    for word in ("ice_meltpond_lvl.F90:79-404", "ice_step_mod.F90:623-642", "ice_shortwave.F90:1450-1514", "ice_therm_shared.F90:62-90", "Td = 2",
+                 "rexp = 0.01", "viscosity_dyn = 1.79e-3", "hs_min = 1e-4", "hpmin = 0.005", "p15 = 0.15", "kice = 2.03", "tmask", "puny**2",
+                 "linitonly", "frain", "tr_pond_topo", "ktherm = 2"):
+        assert word in block, word
+
+
+def test_structure_matches_the_header_and_the_fortran_type_member_for_member():
+    hdr = open(os.path.join(ROOT, "include", "evpk.h")).read()
+    names = [n for n, _ in evpk.PondLvlArgs._fields_]
+    assert _struct_names(hdr, "evpk_pond_lvl_args") == names == evpk.POND_LVL_ARRAYS + evpk.POND_LVL_SCALARS + evpk.POND_LVL_FLAGS
+    kinds = dict(evpk.PondLvlArgs._fields_)
+    assert all(kinds[n] is evpk.c_f64p for n in evpk.POND_LVL_ARRAYS) and all(kinds[n] is ct.c_double for n in evpk.POND_LVL_SCALARS)
+    assert all(kinds[n] is ct.c_int32 for n in evpk.POND_LVL_FLAGS)
+    assert ct.sizeof(evpk.PondLvlArgs) == 4 * 8 + 3 * 8 + 3 * 4 + 4                    # (padded to the pointers' alignment)
+    src = open(os.path.join(ROOT, "fortran", "evpk_mod.F90")).read()
+    assert _fortran_names(src, "evpk_pond_lvl_args") == names
+    body = re.sub(r"!.*", "", src[src.index("type, bind(C) :: evpk_pond_lvl_args"):src.index("end type evpk_pond_lvl_args")])
+    for line in body.splitlines()[1:]:
+        if "::" in line:
+            kind, members = line.split("::")
+            want = "type (c_ptr)" if "dhsn" in members or "Tair" in members else "real (c_double)" if "dpscale" in members else "integer (c_int32_t)"
+            assert kind.strip() == want, line
+    assert "bind(C, name='evpk_step_therm1_lvl')" in src and "bind(C, name='evpk_step_radiation_dedd_lvl')" in src
+    core = open(os.path.join(ROOT, "fortran", "ice_step_dyn.F90")).read()
+    assert "subroutine evpk_step_therm1_lvl_core" in core and "subroutine evpk_step_radiation_dedd_lvl_core" in core
+    for word in ("use ice_meltpond_lvl, only: ffracn, dhsn", "Tair", "fsnow", "nt_ipnd", "dpscale", "frzpnd", "hs1"):
+        assert word in core, word
+
+
+def test_symbols_are_exported_and_bound():
+    L = ct.CDLL(evpk.LIB_PATH)
+    for name in ("evpk_step_therm1_lvl", "evpk_step_radiation_dedd_lvl"):
+        assert name in evpk.EXPORTS and hasattr(L, name)
+        assert hasattr(evpk.lib(), name) and getattr(evpk.lib(), name).argtypes is not None
+    assert callable(evpk.Context.step_therm1_lvl) and callable(evpk.Context.step_radiation_dedd_lvl)
+    assert evpk.POND_LVL_ARRAYS == pv.POND_ARRAYS and evpk.FRZPND == nppondlvl.FRZPND
+    assert evpk.POND_LVL_DEFAULTS["hs1"] == pv.NAMELIST["hs1"]
+
+
+def test_inputs_keep_the_shapes_and_the_tables():
+    for cfg in pv.CONFIGS:
+        for tcase, ncat in pv.TABLES.items():
+            x = inputs(cfg, tcase)
+            nb, nc, ny, nx = x["aicen"].shape
+            tr = x["tracers"]
+            assert nc == ncat and ny * nx <= 26 * 18 and nb >= 2 and (x["aicen"][1] == 0.0).all()
+            assert (tr["nilyr"], tr["nslyr"]) == ((4, 1) if tcase == "plain" else (7, 2))
+            assert tr["tr_pond_lvl"] == 1 and not tr["tr_pond_cesm"] and x["trcrn"].shape[2] == x["ntrcr"] == tr["nt_ipnd"]
+            assert [tr["nt_" + q] for q in pv.PLANES] == list(range(x["ntrcr"] - 4, x["ntrcr"] + 1))
+            for q in ("dhsn", "ffracn"):
+                assert x[q].shape == x["aicen"].shape
+            assert x["Tair"].shape == x["fsnow"].shape == (nb, ny, nx)
+
+
+def test_inputs_take_every_branch_of_the_thermodynamics():
+    """every branch of compute_ponds_lvl and brine_permeability the restatement counts, at least once over the union of the committed
+    cases: both grids, both tables, both frzpnd, the three dpscale"""
+    tot = {k: 0 for k in nppondlvl.THERM_KEYS}
+    for cfg in pv.CONFIGS:
+        for tcase in pv.TABLES:
+            for frzpnd in pv.FRZPND:
+                for dpscale in pv.DPSCALES:
+                    x, y, pinfos = th_restated(cfg, tcase, frzpnd, dpscale)
+                    for k, v in total(pinfos, nppondlvl.THERM_KEYS).items():
+                        tot[k] += v
+                    assert pinfos[1]["ponds_listed"] == 0, "an ice-free block"
+    print(tot)
+    for k in nppondlvl.THERM_KEYS:
+        assert tot[k] > 0, k
+
+
+def test_inputs_take_every_branch_of_the_shortwave():
+    tot = {k: 0 for k in nppondlvl.SW_KEYS}
+    for cfg in pv.CONFIGS:
+        for tcase in pv.TABLES:
+            for linitonly in (0, 1):
+                x, y, infos, pinfos = sw_restated(cfg, tcase, linitonly)
+                t = total(pinfos, nppondlvl.SW_KEYS)
+                assert (t["linitonly_suppressed"] > 0) == bool(linitonly) and (t["dhs_initialised"] + t["dhs_reset"] > 0) != bool(linitonly)
+                if linitonly:
+                    assert np.array_equal(y["dhsn"], x["dhsn"])
+                for k, v in t.items():
+                    tot[k] += v
+    print(tot)
+    for k in nppondlvl.SW_KEYS:
+        assert tot[k] > 0, k
+
+
+@pytest.mark.parametrize("tcase", list(pv.TABLES))
+def test_shortwave_without_ponds_is_the_cesm_shortwave(tcase):
+    """with apnd = 0 everywhere the level-ice shortwave equals npdedd.step_radiation_dedd under tr_pond_cesm, bit for bit, on every output"""
+    x = inputs(CFG, tcase)
+    tr = x["tracers"]
+    t = x["trcrn"].copy()
+    t[:, :, tr["nt_apnd"] - 1] = 0.0
+    y = sw_arrays(x, trcrn=t)
+    nppondlvl.step_radiation_dedd_lvl(iv.blocks_of(x["d"]), x["tmask"], sw_params(x), y)
+    z = sw_arrays(x, trcrn=t)
+    cesm = dict(tr, tr_pond_cesm=1, tr_pond_lvl=0)
+    npdedd.step_radiation_dedd(iv.blocks_of(x["d"]), x["tmask"], dedd_params(x, tr=cesm), z)
+    for k in dv.WRITTEN + ["coszen"]:
+        assert y[k].tobytes() == z[k].tobytes(), k
+    assert y["fswsfcn"].any() and not y["apeffn"].any()
+
+
+@pytest.mark.parametrize("tcase", list(pv.TABLES))
+def test_thermodynamics_beside_the_ponds_is_step_therm1_without_ponds(tcase):
+    """every non-pond output of the level-ice thermodynamics equals nptherm1s.step without ponds, bit for bit"""
+    x = th_input(CFG, tcase)
+    y = dict(th_arrays(x))
+    infos, stop, pinfos = nppondlvl.step_therm1_lvl(iv.blocks_of(x["d"]), x["tmask"], nppondlvl.therm_params(x, "hlid", 1.0e-3), y)
+    assert stop is None and sum(i["ponds_listed"] for i in pinfos) > 300
+    _, z, _ = th_base(CFG, tcase)
+    tr = x["tracers"]
+    ponds = [tr[k] - 1 for k in ("nt_apnd", "nt_hpnd", "nt_ipnd")]
+    rest = [k for k in range(x["trcrn"].shape[2]) if k not in ponds]
+    for k in sv.WRITTEN:
+        if k == "trcrn":
+            assert y[k][:, :, rest].tobytes() == z[k][:, :, rest].tobytes()
+            assert not np.array_equal(y[k][:, :, ponds], z[k][:, :, ponds])
+        elif y[k] is not None:
+            assert y[k].tobytes() == z[k].tobytes(), k
+    assert y["trcrn"].tobytes() == th_restated(CFG, tcase, "hlid", 1.0e-3)[1]["trcrn"].tobytes()
+    assert y["ffracn"].tobytes() == th_restated(CFG, tcase, "hlid", 1.0e-3)[1]["ffracn"].tobytes()
