@@ -623,12 +623,19 @@ template <class T> static hipError_t grow(evpk_ctx *c, T *&p, size_t &n, size_t 
 
 // the caller's arrays of one call: in place where the device sees them (mapped_alias, array by array), else through a staging copy -- up
 // into one pool, and down again at the end if the array is an output.  A NULL or empty array gets a null device pointer.  in = false: an
-// array the call writes on every element before it reads it -- it gets its place in the pool and is not copied up.
+// array the call writes on every element before it reads it -- it gets its place in the pool and is not copied up.  An OptArr is a HostArr
+// the caller may leave NULL; any_missing answers for the others, on the list that stage_in gets.
 struct HostArr {
-    void *host; size_t bytes; void **slot; bool out; bool in; bool staged = false;
+    void *host; size_t bytes; void **slot; bool out; bool in; bool staged = false, required = true;
     template <class T, class U> HostArr(T *h, size_t count, U **dev, bool o, bool i = true)
         : host((void *)h), bytes(sizeof(T) * count), slot((void **)dev), out(o), in(i) {}
 };
+struct OptArr : HostArr {
+    template <class... A> OptArr(A... a) : HostArr(a...) { required = false; }
+};
+static bool any_missing(const std::vector<HostArr> &arr) {
+    return std::any_of(arr.begin(), arr.end(), [](const HostArr &a) { return a.required && !a.host; });
+}
 // (the upward copies are asynchronous on c->stream: the caller synchronises once, with whatever else it sends from pageable memory)
 static int stage_in(evpk_ctx *c, std::vector<HostArr> &arr, bool dyn = false) {
     size_t need = 0;
@@ -1261,11 +1268,23 @@ template <class F> static inline void with_bool(bool flag1, bool flag2, F &&f) {
 template <class F> static inline void with_ncat(int ncat, F &&f) {
     if (ncat == 5) f(std::integral_constant<int, 5>{}); else f(std::integral_constant<int, 0>{});
 }
+// the column kernels are built for five categories of four ice layers and one snow layer (<5, 4, 1>) and for any sizes (<0, 0, 0>)
+template <class F> static inline void with_layers(int ncat, int nilyr, int nslyr, F &&f) {
+    using std::integral_constant;
+    if (ncat == 5 && nilyr == 4 && nslyr == 1) f(integral_constant<int, 5>{}, integral_constant<int, 4>{}, integral_constant<int, 1>{});
+    else f(integral_constant<int, 0>{}, integral_constant<int, 0>{}, integral_constant<int, 0>{});
+}
 
 // a knob that is on unless the environment sets it to 0 (read per call)
 static bool env_on(const char *name) { const char *v = getenv(name); return !(v && atoi(v) == 0); }
 // one workgroup row per row of a caller's block array, one grid layer per local block (LAUNCH_BLOCKS)
 static inline dim3 block_grid(const evpk_ctx *c) { return dim3((c->nxb + 63) / 64, c->nyb, c->nblocks); }
+// a launch of that shape on c->stream: kernel(slab, block descriptors, args...)
+template <class K, class... A> static int launch_blocks(evpk_ctx *c, K kernel, const A &...args) {
+    hipLaunchKernelGGL(kernel, block_grid(c), dim3(64), 0, c->stream, c->s, (const BlockDesc *)c->d_bd, args...);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
 
 // workgroups of a launch (or of one part of it: strips, band, mirror slab) rounded up to a multiple of 8: XCD remap in the kernels
 static inline int xcd_round(int nwg) { return (nwg + 7) & ~7; }
@@ -4413,435 +4432,8 @@ extern "C" int evpk_step_therm2(evpk_ctx *c, const evpk_therm2_args *a, int32_t 
     return rc;
 }
 
-// ---- thermo_vertical (source/ice_therm_vertical.F90:79-531), BL99, for every category of every block in one launch (kernel in
-// evpk_therm1.hip) ----
-// what evpk_thermo_vertical refuses (coefs: fbot, Tbot, shcoef, lhcoef are inputs; evpk_step_therm1 makes them itself)
-static int thermo_check(evpk_ctx *c, const char *who, const evpk_thermo_args *a, bool coefs) {
-    const evpk_itd_tracers &t = a->t;
-    if (a->ktherm != 1) FAIL(c, "%s: ktherm = %d: only ktherm = 1 (BL99) is supported", who, a->ktherm);
-    if (a->calc_Tsfc != 1) FAIL(c, "%s: calc_Tsfc = .false. is not supported", who);
-    if (a->heat_capacity != 1) FAIL(c, "%s: heat_capacity = .false. (zero-layer) is not supported", who);
-    if (a->l_brine != 1) FAIL(c, "%s: l_brine = .false. (fresh ice) is not supported", who);
-    if (a->conduct != 0 && a->conduct != 1) FAIL(c, "%s: conduct = %d not 0 (MU71) or 1 (bubbly)", who, a->conduct);
-    if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->flw || !a->potT || !a->Qa || !a->rhoa || !a->fsnow || (coefs && (!a->fbot || !a->Tbot)) ||
-        !a->sss || (coefs && (!a->shcoef || !a->lhcoef)) || !a->fswsfcn || !a->fswintn || !a->Sswabsn || !a->Iswabsn || !a->mlt_onset || !a->frz_onset ||
-        !a->flwoutn || !a->evapn || !a->freshn || !a->fsaltn || !a->fhocnn || !a->fsensn || !a->flatn || !a->fsurfn || !a->fcondtopn ||
-        !a->melttn || !a->meltsn || !a->meltbn || !a->congeln || !a->snoicen || !a->dsnown || a->ntrcr < 1 || a->ntrcr_dim < a->ntrcr)
-        FAIL(c, "%s: a required argument is missing", who);
-    if (!c->connected) FAIL(c, "%s: the context is not connected yet (evpk_connect)", who);
-    if (!c->have_params) FAIL(c, "%s: evpk_set_params has not been called (rhow, rhoi, rhos)", who);
-    if (!(a->dt > 0.0)) FAIL(c, "%s: dt = %g", who, a->dt);
-    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, a->ncat, MAXCAT);
-    if (a->ntrcr > RG_MAXT) FAIL(c, "%s: ntrcr = %d exceeds %d", who, a->ntrcr, RG_MAXT);
-    if (a->k.puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->k.puny);
-    if (t.nt_Tsfc < 1 || t.nt_qice < 1 || t.nt_qsno < 1 || a->nt_sice < 1) FAIL(c, "%s: nt_Tsfc, nt_qice, nt_qsno and nt_sice are required", who);
-    if (t.nilyr < 1 || t.nslyr < 1 || t.nilyr > T1_MAXL || t.nslyr > T1_MAXL)
-        FAIL(c, "%s: nilyr = %d, nslyr = %d not in 1..%d", who, t.nilyr, t.nslyr, T1_MAXL);
-    if (t.nt_Tsfc > a->ntrcr || t.nt_qice + t.nilyr - 1 > a->ntrcr || t.nt_qsno + t.nslyr - 1 > a->ntrcr || a->nt_sice + t.nilyr - 1 > a->ntrcr)
-        FAIL(c, "%s: a tracer index lies beyond ntrcr = %d", who, a->ntrcr);
-    if (t.tr_pond_topo && (!a->fpond || t.nt_apnd < 1 || t.nt_hpnd < 1 || t.nt_apnd > a->ntrcr || t.nt_hpnd > a->ntrcr))
-        FAIL(c, "%s: tr_pond_topo needs fpond, nt_apnd and nt_hpnd", who);
-    if (c->nblocks >= 65536) FAIL(c, "%s: %d blocks exceed the stop key", who, c->nblocks);
-    return 0;
-}
-
-extern "C" int evpk_thermo_vertical(evpk_ctx *c, const evpk_thermo_args *a, int32_t stop[5]) {
-    if (!c) return 1;
-    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
-    RANKS_ENTRY(c, "evpk_thermo_vertical");
-    if (!a || !stop) FAIL(c, "evpk_thermo_vertical: a required argument is missing");
-    if (thermo_check(c, "evpk_thermo_vertical", a, true)) return 1;
-    const evpk_itd_tracers &t = a->t;
-    if (!c->nblocks) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    ThermoArgs T{};
-    T.ncat = a->ncat; T.ntrcr_dim = a->ntrcr_dim; T.nxb = c->nxb; T.nyb = c->nyb; T.nilyr = t.nilyr; T.nslyr = t.nslyr;
-    T.nt_Tsfc = t.nt_Tsfc; T.nt_qice = t.nt_qice; T.nt_qsno = t.nt_qsno; T.nt_sice = a->nt_sice; T.nt_apnd = t.nt_apnd; T.nt_hpnd = t.nt_hpnd;
-    T.tr_pond_topo = t.tr_pond_topo ? 1 : 0; T.conduct = a->conduct;
-    T.dt = a->dt; T.yday = a->yday; T.min_salin = a->min_salin; T.puny = a->k.puny; T.rhoi = c->p.rhoi; T.rhos = c->p.rhos; T.rhow = c->p.rhow;
-    T.cp_ice = a->k.cp_ice; T.Lfresh = a->k.Lfresh; T.hs_min = a->k.hs_min; T.Tmin = a->k.Tmin; T.salinity = a->k.ice_ref_salinity;
-    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
-    std::vector<HostArr> arr = {            // (sss is not staged: ktherm = 1 does not read it; the fifteen outputs are not copied up)
-        {a->aicen, n3, &T.aicen, true}, {a->vicen, n3, &T.vicen, true}, {a->vsnon, n3, &T.vsnon, true}, {a->trcrn, n3 * a->ntrcr_dim, &T.trcrn, true},
-        {a->flw, N, &T.flw, false}, {a->potT, N, &T.potT, false}, {a->Qa, N, &T.Qa, false}, {a->rhoa, N, &T.rhoa, false},
-        {a->fsnow, N, &T.fsnow, false}, {a->fbot, N, &T.fbot, false}, {a->Tbot, N, &T.Tbot, false},
-        {a->shcoef, n3, &T.shcoef, false}, {a->lhcoef, n3, &T.lhcoef, false},
-        {a->fswsfcn, n3, &T.fswsfcn, true}, {a->fswintn, n3, &T.fswintn, true}, {a->Sswabsn, n3 * t.nslyr, &T.Sswabsn, true},
-        {a->Iswabsn, n3 * t.nilyr, &T.Iswabsn, true}, {t.tr_pond_topo ? a->fpond : nullptr, N, &T.fpond, true},
-        {a->mlt_onset, N, &T.mlt_onset, true}, {a->frz_onset, N, &T.frz_onset, true},
-        {a->flwoutn, n3, &T.flwoutn, true, false}, {a->evapn, n3, &T.evapn, true, false}, {a->freshn, n3, &T.freshn, true, false}, {a->fsaltn, n3, &T.fsaltn, true, false},
-        {a->fhocnn, n3, &T.fhocnn, true, false}, {a->fsensn, n3, &T.fsensn, true, false}, {a->flatn, n3, &T.flatn, true, false}, {a->fsurfn, n3, &T.fsurfn, true, false},
-        {a->fcondtopn, n3, &T.fcondtopn, true, false}, {a->melttn, n3, &T.melttn, true, false}, {a->meltsn, n3, &T.meltsn, true, false},
-        {a->meltbn, n3, &T.meltbn, true, false}, {a->congeln, n3, &T.congeln, true, false}, {a->snoicen, n3, &T.snoicen, true, false}, {a->dsnown, n3, &T.dsnown, true, false}};
-    if (stage_in(c, arr, true)) return 1;
-    if (!c->itd_key) HIPCHK(c, hipMalloc(&c->itd_key, sizeof(unsigned long long)));
-    HIPCHK(c, hipMemsetAsync(c->itd_key, 0xff, sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
-    const dim3 b(64), g = block_grid(c);
-    if (a->ncat == 5 && t.nilyr == 4 && t.nslyr == 1)
-        hipLaunchKernelGGL((k_thermo_vertical<5, 4, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, T, c->itd_key);
-    else
-        hipLaunchKernelGGL((k_thermo_vertical<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, T, c->itd_key);
-    HIPCHK(c, hipGetLastError());
-    unsigned long long key = ~0ull;
-    HIPCHK(c, hipMemcpyAsync(&key, c->itd_key, sizeof(key), hipMemcpyDeviceToHost, c->stream));
-    if (stage_out(c, arr)) return 1;
-    if (key == ~0ull) return 0;
-    const int seq = (int)((key >> 32) & 0xff), ns = t.nslyr, nl = t.nilyr;
-    const size_t o = (size_t)(key & 0xffffffffull);
-    stop[0] = seq < ns ? T1_STOP_TSN_HIGH : seq < 2 * ns ? T1_STOP_TSN_LOW : seq < 2 * ns + 3 * nl ? T1_STOP_SALIN + (seq - 2 * ns) % 3
-              : seq == 2 * ns + 3 * nl ? T1_STOP_NITER : T1_STOP_ENERGY;
-    stop[1] = (int32_t)(key >> 48) + 1; stop[2] = (int32_t)((key >> 40) & 0xff) + 1; stop[3] = (int32_t)(o % c->nxb) + 1; stop[4] = (int32_t)(o / c->nxb) + 1;
-    return EVPK_THERMO_STOP;
-}
-
-// what the two level-ice pond entry points refuse beyond their parents
-static int pond_lvl_check(evpk_ctx *c, const char *who, const evpk_itd_tracers &t, int ntrcr, const evpk_pond_lvl_args *p) {
-    const int nts[4] = {t.nt_alvl, t.nt_apnd, t.nt_hpnd, p->nt_ipnd};
-    for (int nt : nts)
-        if (nt < 1 || nt > ntrcr) FAIL(c, "%s: tr_pond_lvl without nt_alvl / nt_apnd / nt_hpnd / nt_ipnd in 1..ntrcr = %d", who, ntrcr);
-    if (p->frzpnd < 0 || p->frzpnd > 1) FAIL(c, "%s: frzpnd = %d not 0 ('cesm') or 1 ('hlid')", who, p->frzpnd);
-    if (!p->dhsn || !p->ffracn) FAIL(c, "%s: tr_pond_lvl needs dhsn and ffracn", who);
-    return 0;
-}
-
-// ---- step_therm1 (source/ice_step_mod.F90:154-733) in one call: k_therm1_open, k_thermo_vertical, k_therm1_merge (evpk_therm1s.hip) on
-// state staged once ----
-// p: the level-ice pond arguments of evpk_step_therm1_lvl, or null for evpk_step_therm1
-static int therm1_run(evpk_ctx *c, const char *who, const evpk_therm1_args *a, const evpk_pond_lvl_args *p, int32_t stop[5]) {
-    const evpk_thermo_args &v = a->tv;
-    const evpk_itd_tracers &t = v.t;
-    if (a->formdrag) FAIL(c, "%s: formdrag (neutral_drag_coeffs) is not supported", who);
-    if (a->highfreq) FAIL(c, "%s: highfreq coupling is not supported", who);
-    if (a->atmbndy_constant) FAIL(c, "%s: atmbndy = 'constant' (atmo_boundary_const) is not supported", who);
-    if (a->fbot_xfer_Cdn_ocn) FAIL(c, "%s: fbot_xfer_type = 'Cdn_ocn' is not supported", who);
-    if (!p && t.tr_pond_lvl) FAIL(c, "%s: tr_pond_lvl (compute_ponds_lvl) is not supported", who);
-    if (p && !t.tr_pond_lvl) FAIL(c, "%s: tr_pond_lvl is not set", who);
-    if (p && t.tr_pond_cesm) FAIL(c, "%s: tr_pond_cesm is set beside tr_pond_lvl", who);
-    if (t.tr_pond_topo) FAIL(c, "%s: tr_pond_topo (compute_ponds_topo) is not supported", who);
-    if (a->tr_aero) FAIL(c, "%s: aerosol tracers (tr_aero, update_aerosol) are not supported", who);
-    if (thermo_check(c, who, &v, false)) return 1;
-    if (a->natmiter < 1) FAIL(c, "%s: natmiter = %d", who, a->natmiter);
-    if (!a->aice || !a->frzmlt || !a->sst || !a->Tf || !a->strocnxT || !a->strocnyT || !a->uatm || !a->vatm || !a->wind || !a->zlvl || !a->fswthrun ||
-        !a->Cdn_atm || !a->rside || !a->aice_init || !a->aicen_init || !a->vicen_init)
-        FAIL(c, "%s: a required argument is missing", who);
-    double *const merged[T1S_NMERGE] = {a->strairxT, a->strairyT, a->Cdn_atm_ratio, a->fsurf, a->fcondtop, a->fsens, a->flat, a->fswabs, a->flwout, a->evap,
-                                        a->Tref, a->Qref, a->Uref, a->fresh, a->fsalt, a->fhocn, a->fswthru, a->meltt, a->meltb, a->melts, a->congel, a->snoice};
-    for (double *q : merged) if (!q) FAIL(c, "%s: a required argument is missing", who);
-    if (a->tr_iage && (a->nt_iage < 1 || a->nt_iage > v.ntrcr)) FAIL(c, "%s: tr_iage without nt_iage in 1..ntrcr = %d", who, v.ntrcr);
-    if (a->tr_FY && (a->nt_FY < 1 || a->nt_FY > v.ntrcr)) FAIL(c, "%s: tr_FY without nt_FY in 1..ntrcr = %d", who, v.ntrcr);
-    if (a->tr_FY && (!a->lmask_n || !a->lmask_s)) FAIL(c, "%s: tr_FY needs lmask_n and lmask_s", who);
-    if (t.tr_pond_cesm && (t.nt_apnd < 1 || t.nt_hpnd < 1 || t.nt_apnd > v.ntrcr || t.nt_hpnd > v.ntrcr))
-        FAIL(c, "%s: tr_pond_cesm without nt_apnd / nt_hpnd in 1..ntrcr = %d", who, v.ntrcr);
-    if (t.tr_pond_cesm && !a->frain) FAIL(c, "%s: tr_pond_cesm needs frain", who);
-    if (t.tr_pond_cesm && !(a->pndaspect > 0.0)) FAIL(c, "%s: pndaspect = %g", who, a->pndaspect);
-    if (p) {
-        if (pond_lvl_check(c, who, t, v.ntrcr, p)) return 1;
-        if (!p->Tair) FAIL(c, "%s: tr_pond_lvl needs Tair", who);
-        if (!a->frain) FAIL(c, "%s: tr_pond_lvl needs frain", who);
-        if (!(a->pndaspect > 0.0)) FAIL(c, "%s: pndaspect = %g", who, a->pndaspect);
-    }
-    if (!c->nblocks) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * v.ncat;
-    evpk_thermo_args x = v;                 // thermo_vertical's arguments on device pointers
-    Therm1sArgs A{};
-    double *d_opt[8] = {};                  // shcoef, lhcoef, strairxn, strairyn, Cdn_atm_ratio_n, Trefn, Qrefn, Urefn where the caller gives them
-    double *d_fbot = nullptr, *d_Tbot = nullptr;
-    double *const h_opt[8] = {const_cast<double *>(v.shcoef), const_cast<double *>(v.lhcoef), a->strairxn, a->strairyn, a->Cdn_atm_ratio_n, a->Trefn,
-                              a->Qrefn, a->Urefn};
-    std::vector<HostArr> arr = {            // (sss is not staged: ktherm = 1 does not read it; arrays a call only writes are not copied up)
-        {v.aicen, n3, &x.aicen, true}, {v.vicen, n3, &x.vicen, true}, {v.vsnon, n3, &x.vsnon, true}, {v.trcrn, n3 * v.ntrcr_dim, &x.trcrn, true},
-        {v.flw, N, &x.flw, false}, {v.potT, N, &x.potT, false}, {v.Qa, N, &x.Qa, false}, {v.rhoa, N, &x.rhoa, false}, {v.fsnow, N, &x.fsnow, false},
-        {v.fswsfcn, n3, &x.fswsfcn, true}, {v.fswintn, n3, &x.fswintn, true}, {v.Sswabsn, n3 * t.nslyr, &x.Sswabsn, true},
-        {v.Iswabsn, n3 * t.nilyr, &x.Iswabsn, true}, {v.mlt_onset, N, &x.mlt_onset, true}, {v.frz_onset, N, &x.frz_onset, true},
-        {v.flwoutn, n3, &x.flwoutn, true, false}, {v.evapn, n3, &x.evapn, true, false}, {v.freshn, n3, &x.freshn, true, false}, {v.fsaltn, n3, &x.fsaltn, true, false},
-        {v.fhocnn, n3, &x.fhocnn, true, false}, {v.fsensn, n3, &x.fsensn, true, false}, {v.flatn, n3, &x.flatn, true, false}, {v.fsurfn, n3, &x.fsurfn, true, false},
-        {v.fcondtopn, n3, &x.fcondtopn, true, false}, {v.melttn, n3, &x.melttn, true, false}, {v.meltsn, n3, &x.meltsn, true, false},
-        {v.meltbn, n3, &x.meltbn, true, false}, {v.congeln, n3, &x.congeln, true, false}, {v.snoicen, n3, &x.snoicen, true, false}, {v.dsnown, n3, &x.dsnown, true, false},
-        {const_cast<double *>(v.fbot), N, &d_fbot, true, false}, {const_cast<double *>(v.Tbot), N, &d_Tbot, true, false},
-        {a->aice, N, &A.aice, false}, {a->frzmlt, N, &A.frzmlt, false}, {a->sst, N, &A.sst, false}, {a->Tf, N, &A.Tf, false},
-        {a->strocnxT, N, &A.strocnxT, false}, {a->strocnyT, N, &A.strocnyT, false}, {a->uatm, N, &A.uatm, false}, {a->vatm, N, &A.vatm, false},
-        {a->wind, N, &A.wind, false}, {a->zlvl, N, &A.zlvl, false}, {t.tr_pond_cesm || p ? a->frain : nullptr, N, &A.frain, false},
-        {a->fswthrun, n3, &A.fswthrun, false}, {a->tr_FY ? a->lmask_n : nullptr, N, &A.lmask_n, false}, {a->tr_FY ? a->lmask_s : nullptr, N, &A.lmask_s, false},
-        {a->Cdn_atm, N, &A.Cdn_atm, true}, {a->rside, N, &A.rside, true, false}, {a->aice_init, N, &A.aice_init, true, false},
-        {a->aicen_init, n3, &A.aicen_init, true, false}, {a->vicen_init, n3, &A.vicen_init, true, false}};
-    for (int q = 0; q < 8; q++) arr.push_back({h_opt[q], n3, &d_opt[q], true, false});
-    for (int q = 0; q < T1S_NMERGE; q++) arr.push_back({merged[q], N, &A.m[q], true});
-    if (p) {                                  // (ffracn is written on every cell: not copied up)
-        arr.push_back({p->dhsn, n3, &A.dhsn, false});
-        arr.push_back({p->ffracn, n3, &A.ffracn, true, false});
-        arr.push_back({p->Tair, N, &A.Tair, false});
-    }
-    if (stage_in(c, arr, true)) return 1;
-    HIPCHK(c, grow(c, c->th1_pool, c->th1_pool_n, 8 * n3 + 2 * N));        // one pool, grown once
-    for (int q = 0; q < 8; q++) if (!d_opt[q]) d_opt[q] = c->th1_pool + (size_t)q * n3;
-    if (!d_fbot) d_fbot = c->th1_pool + 8 * n3;
-    if (!d_Tbot) d_Tbot = c->th1_pool + 8 * n3 + N;
-    x.fbot = d_fbot; x.Tbot = d_Tbot; x.shcoef = d_opt[0]; x.lhcoef = d_opt[1];
-    x.sss = v.sss;                            // (not read: any non-null pointer passes the check)
-    A.potT = x.potT; A.Qa = x.Qa; A.rhoa = x.rhoa; A.flw = x.flw;
-    A.aicen = x.aicen; A.vicen = x.vicen; A.vsnon = x.vsnon; A.trcrn = x.trcrn;
-    A.fbot = d_fbot; A.Tbot = d_Tbot;
-    A.shcoef = d_opt[0]; A.lhcoef = d_opt[1]; A.strairxn = d_opt[2]; A.strairyn = d_opt[3]; A.Cdn_atm_ratio_n = d_opt[4]; A.Trefn = d_opt[5];
-    A.Qrefn = d_opt[6]; A.Urefn = d_opt[7];
-    A.fswsfcn = x.fswsfcn; A.fswintn = x.fswintn; A.flwoutn = x.flwoutn; A.evapn = x.evapn; A.freshn = x.freshn; A.fsaltn = x.fsaltn; A.fhocnn = x.fhocnn;
-    A.fsensn = x.fsensn; A.flatn = x.flatn; A.fsurfn = x.fsurfn; A.fcondtopn = x.fcondtopn; A.melttn = x.melttn; A.meltsn = x.meltsn; A.meltbn = x.meltbn;
-    A.congeln = x.congeln; A.snoicen = x.snoicen;
-    A.ncat = v.ncat; A.ntrcr_dim = v.ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nilyr = t.nilyr; A.nslyr = t.nslyr; A.nt_Tsfc = t.nt_Tsfc;
-    A.nt_qice = t.nt_qice; A.nt_qsno = t.nt_qsno; A.nt_apnd = t.nt_apnd; A.nt_hpnd = t.nt_hpnd; A.nt_iage = a->nt_iage; A.nt_FY = a->nt_FY;
-    A.tr_iage = a->tr_iage ? 1 : 0; A.tr_FY = a->tr_FY ? 1 : 0; A.tr_pond_cesm = t.tr_pond_cesm ? 1 : 0; A.calc_strair = a->calc_strair ? 1 : 0;
-    A.natmiter = a->natmiter;
-    if (p) {
-        A.nt_alvl = t.nt_alvl; A.nt_ipnd = p->nt_ipnd; A.nt_sice = v.nt_sice; A.frzpnd = p->frzpnd; A.dpscale = p->dpscale;
-        A.Lfresh = v.k.Lfresh; A.cp_ice = v.k.cp_ice;
-    }
-    A.dt = v.dt; A.yday = v.yday; A.puny = v.k.puny; A.rhoi = c->p.rhoi; A.rhos = c->p.rhos; A.rhow = c->p.rhow; A.chio = a->chio;
-    A.ustar_min = a->ustar_min; A.hi_min = a->hi_min; A.pndaspect = a->pndaspect; A.rfracmin = a->rfracmin; A.rfracmax = a->rfracmax;
-    const dim3 b(64), g = block_grid(c);
-    if (v.ncat == 5)
-        hipLaunchKernelGGL(k_therm1_open<5>, g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    else
-        hipLaunchKernelGGL(k_therm1_open<0>, g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    HIPCHK(c, hipGetLastError());
-    // thermo_vertical on the staged arrays: its own staging finds device pointers and copies nothing
-    const int rc = evpk_thermo_vertical(c, &x, stop);
-    if (rc == 1) return 1;
-    const std::string keep = c->err;
-    if (rc == 0) {                            // (no merge after a stop)
-        if (v.ncat == 5 && p)
-            hipLaunchKernelGGL((k_therm1_merge<5, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-        else if (p)
-            hipLaunchKernelGGL((k_therm1_merge<0, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-        else if (v.ncat == 5)
-            hipLaunchKernelGGL((k_therm1_merge<5, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-        else
-            hipLaunchKernelGGL((k_therm1_merge<0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-        HIPCHK(c, hipGetLastError());
-    }
-    if (stage_out(c, arr)) return 1;
-    if (rc) c->err = keep;
-    return rc;
-}
-
-extern "C" int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t stop[5]) {
-    if (!c) return 1;
-    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
-    RANKS_ENTRY(c, "evpk_step_therm1");
-    if (!a || !stop) FAIL(c, "evpk_step_therm1: a required argument is missing");
-    return therm1_run(c, "evpk_step_therm1", a, nullptr, stop);
-}
-
-// step_therm1 under tr_pond_lvl: compute_ponds_lvl (source/ice_meltpond_lvl.F90:79-404) in the place of compute_ponds_cesm
-extern "C" int evpk_step_therm1_lvl(evpk_ctx *c, const evpk_therm1_args *a, const evpk_pond_lvl_args *p, int32_t stop[5]) {
-    if (!c) return 1;
-    if (stop) stop[0] = stop[1] = stop[2] = stop[3] = stop[4] = 0;
-    RANKS_ENTRY(c, "evpk_step_therm1_lvl");
-    if (!a || !p || !stop) FAIL(c, "evpk_step_therm1_lvl: a required argument is missing");
-    return therm1_run(c, "evpk_step_therm1_lvl", a, p, stop);
-}
-
-// ---- step_radiation (source/ice_step_mod.F90:1364-1524, ccsm3) with the albedo lines of coupling_prep, and prep_radiation (:33-145):
-// one launch each (kernels in evpk_rad.hip) ----
-extern "C" int evpk_step_radiation(evpk_ctx *c, const evpk_rad_args *a) {
-    if (!c) return 1;
-    RANKS_ENTRY(c, "evpk_step_radiation");
-    const char *who = "evpk_step_radiation";
-    if (!a) FAIL(c, "%s: a required argument is missing", who);
-    const evpk_itd_tracers &t = a->t;
-    if (a->shortwave_dEdd) FAIL(c, "%s: shortwave = 'dEdd' (run_dEdd) is not supported", who);
-    if (a->calc_Tsfc != 1) FAIL(c, "%s: calc_Tsfc = .false. is not supported", who);
-    if (a->heat_capacity != 1) FAIL(c, "%s: heat_capacity = .false. (zero-layer) is not supported", who);
-    if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->swvdr || !a->swvdf || !a->swidr || !a->swidf || !a->alvdrn || !a->alidrn ||
-        !a->alvdfn || !a->alidfn || !a->albicen || !a->albsnon || !a->fswsfcn || !a->fswintn || !a->fswthrun || !a->Sswabsn || !a->Iswabsn ||
-        !a->coszen || !a->alvdr || !a->alidr || !a->alvdf || !a->alidf || !a->albice || !a->albsno || !a->scale_factor)
-        FAIL(c, "%s: a required argument is missing", who);
-    if (t.nilyr < 1 || t.nslyr < 1 || t.nilyr > T1_MAXL || t.nslyr > T1_MAXL)
-        FAIL(c, "%s: nilyr = %d, nslyr = %d not in 1..%d", who, t.nilyr, t.nslyr, T1_MAXL);
-    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, a->ncat, MAXCAT);
-    if (a->ntrcr < 1 || a->ntrcr_dim < a->ntrcr || t.nt_Tsfc < 1 || t.nt_Tsfc > a->ntrcr)
-        FAIL(c, "%s: nt_Tsfc = %d lies beyond ntrcr = %d (ntrcr_dim = %d)", who, t.nt_Tsfc, a->ntrcr, a->ntrcr_dim);
-    if (a->puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->puny);
-    if (!c->nblocks) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    RadArgs A{};
-    A.ncat = a->ncat; A.ntrcr_dim = a->ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nilyr = t.nilyr; A.nslyr = t.nslyr; A.nt_Tsfc = t.nt_Tsfc;
-    A.constant_albedos = a->albedo_constant ? 1 : 0;
-    A.puny = a->puny; A.albicev = a->albicev; A.albicei = a->albicei; A.albsnowv = a->albsnowv; A.albsnowi = a->albsnowi; A.ahmax = a->ahmax;
-    A.snowpatch = a->snowpatch; A.albocn = a->albocn; A.awtvdr = a->awtvdr; A.awtidr = a->awtidr; A.awtvdf = a->awtvdf; A.awtidf = a->awtidf;
-    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
-    std::vector<HostArr> arr = {            // (every output is written on every cell: none is copied up)
-        {a->aicen, n3, &A.aicen, false}, {a->vicen, n3, &A.vicen, false}, {a->vsnon, n3, &A.vsnon, false}, {a->trcrn, n3 * a->ntrcr_dim, &A.trcrn, false},
-        {a->swvdr, N, &A.swvdr, false}, {a->swvdf, N, &A.swvdf, false}, {a->swidr, N, &A.swidr, false}, {a->swidf, N, &A.swidf, false},
-        {a->ocn_albedo2D, N, &A.ocn_albedo2D, false},
-        {a->alvdrn, n3, &A.alvdrn, true, false}, {a->alidrn, n3, &A.alidrn, true, false}, {a->alvdfn, n3, &A.alvdfn, true, false},
-        {a->alidfn, n3, &A.alidfn, true, false}, {a->albicen, n3, &A.albicen, true, false}, {a->albsnon, n3, &A.albsnon, true, false},
-        {a->fswsfcn, n3, &A.fswsfcn, true, false}, {a->fswintn, n3, &A.fswintn, true, false}, {a->fswthrun, n3, &A.fswthrun, true, false},
-        {a->Sswabsn, n3 * t.nslyr, &A.Sswabsn, true, false}, {a->Iswabsn, n3 * t.nilyr, &A.Iswabsn, true, false},
-        {a->fswpenln, n3 * (t.nilyr + 1), &A.fswpenln, true, false},
-        {a->coszen, N, &A.coszen, true, false}, {a->alvdr, N, &A.alvdr, true, false}, {a->alidr, N, &A.alidr, true, false},
-        {a->alvdf, N, &A.alvdf, true, false}, {a->alidf, N, &A.alidf, true, false}, {a->albice, N, &A.albice, true, false},
-        {a->albsno, N, &A.albsno, true, false}, {a->scale_factor, N, &A.scale_factor, true, false}};
-    if (stage_in(c, arr, true)) return 1;
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
-    const dim3 b(64), g = block_grid(c);
-    if (a->ncat == 5 && t.nilyr == 4 && t.nslyr == 1)
-        hipLaunchKernelGGL((k_shortwave_ccsm3<5, 4, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    else
-        hipLaunchKernelGGL((k_shortwave_ccsm3<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    HIPCHK(c, hipGetLastError());
-    return stage_out(c, arr);
-}
-
-extern "C" int evpk_prep_radiation(evpk_ctx *c, const evpk_prep_rad_args *a) {
-    if (!c) return 1;
-    RANKS_ENTRY(c, "evpk_prep_radiation");
-    const char *who = "evpk_prep_radiation";
-    if (!a) FAIL(c, "%s: a required argument is missing", who);
-    if (!a->aice || !a->aicen || !a->swvdr || !a->swvdf || !a->swidr || !a->swidf || !a->alvdr_ai || !a->alvdf_ai || !a->alidr_ai || !a->alidf_ai ||
-        !a->scale_factor || !a->fswsfcn || !a->fswintn || !a->fswthrun || !a->Sswabsn || !a->Iswabsn || !a->fswfac)
-        FAIL(c, "%s: a required argument is missing", who);
-    if (a->nilyr < 1 || a->nslyr < 1 || a->nilyr > T1_MAXL || a->nslyr > T1_MAXL)
-        FAIL(c, "%s: nilyr = %d, nslyr = %d not in 1..%d", who, a->nilyr, a->nslyr, T1_MAXL);
-    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, a->ncat, MAXCAT);
-    if (a->puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->puny);
-    if (!c->nblocks) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    PrepRadArgs A{};
-    A.ncat = a->ncat; A.nxb = c->nxb; A.nyb = c->nyb; A.nilyr = a->nilyr; A.nslyr = a->nslyr; A.puny = a->puny;
-    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
-    std::vector<HostArr> arr = {            // (fswfac is copied up too: its ghost cells keep the caller's values)
-        {a->aice, N, &A.aice, false}, {a->aicen, n3, &A.aicen, false}, {a->swvdr, N, &A.swvdr, false}, {a->swvdf, N, &A.swvdf, false},
-        {a->swidr, N, &A.swidr, false}, {a->swidf, N, &A.swidf, false}, {a->alvdr_ai, N, &A.alvdr_ai, false}, {a->alvdf_ai, N, &A.alvdf_ai, false},
-        {a->alidr_ai, N, &A.alidr_ai, false}, {a->alidf_ai, N, &A.alidf_ai, false},
-        {a->scale_factor, N, &A.scale_factor, true}, {a->fswfac, N, &A.fswfac, true},
-        {a->fswsfcn, n3, &A.fswsfcn, true}, {a->fswintn, n3, &A.fswintn, true}, {a->fswthrun, n3, &A.fswthrun, true},
-        {a->fswpenln, n3 * (a->nilyr + 1), &A.fswpenln, true}, {a->Sswabsn, n3 * a->nslyr, &A.Sswabsn, true},
-        {a->Iswabsn, n3 * a->nilyr, &A.Iswabsn, true}};
-    if (stage_in(c, arr, true)) return 1;
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
-    const dim3 b(64), g = block_grid(c);
-    if (a->ncat == 5 && a->nilyr == 4 && a->nslyr == 1)
-        hipLaunchKernelGGL((k_prep_radiation<5, 4, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    else
-        hipLaunchKernelGGL((k_prep_radiation<0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    HIPCHK(c, hipGetLastError());
-    return stage_out(c, arr);
-}
-
-// ---- step_radiation on its Delta-Eddington branch (source/ice_step_mod.F90:1408-1451: run_dEdd, source/ice_shortwave.F90:1251-1577) with
-// the albedo lines of coupling_prep: one launch (kernel in evpk_dedd.hip) ----
-// p: the level-ice pond arguments of evpk_step_radiation_dedd_lvl, or null for evpk_step_radiation_dedd
-static int dedd_run(evpk_ctx *c, const char *who, const evpk_dedd_args *a, const evpk_pond_lvl_args *p) {
-    const evpk_itd_tracers &t = a->t;
-    const bool cesm = a->tr_pond_cesm || t.tr_pond_cesm;
-    if (a->calc_Tsfc != 1) FAIL(c, "%s: calc_Tsfc = .false. is not supported", who);
-    if (a->heat_capacity != 1) FAIL(c, "%s: heat_capacity = .false. (zero-layer) is not supported", who);
-    if (a->tr_aero) FAIL(c, "%s: aerosol tracers (tr_aero) are not supported", who);
-    if (!p && (a->tr_pond_lvl || t.tr_pond_lvl)) FAIL(c, "%s: tr_pond_lvl (dhsn, ffracn) is not supported", who);
-    if (p && !(a->tr_pond_lvl || t.tr_pond_lvl)) FAIL(c, "%s: tr_pond_lvl is not set", who);
-    if (p && cesm) FAIL(c, "%s: tr_pond_cesm is set beside tr_pond_lvl", who);
-    if (a->tr_pond_topo || t.tr_pond_topo) FAIL(c, "%s: tr_pond_topo is not supported", who);
-    if (!a->aicen || !a->vicen || !a->vsnon || !a->trcrn || !a->swvdr || !a->swvdf || !a->swidr || !a->swidf || !a->coszen || !a->alvdrn ||
-        !a->alidrn || !a->alvdfn || !a->alidfn || !a->albicen || !a->albsnon || !a->fswsfcn || !a->fswintn || !a->fswthrun || !a->Sswabsn ||
-        !a->Iswabsn || !a->alvdr || !a->alidr || !a->alvdf || !a->alidf || !a->albice || !a->albsno || !a->scale_factor || !a->albpndn ||
-        !a->apeffn || !a->snowfracn || !a->albpnd || !a->apeff_ai)
-        FAIL(c, "%s: a required argument is missing", who);
-    if (t.nilyr < 1 || t.nslyr < 1 || t.nilyr > DEDD_MAXL || t.nslyr > DEDD_MAXL)
-        FAIL(c, "%s: nilyr = %d, nslyr = %d not in 1..%d", who, t.nilyr, t.nslyr, DEDD_MAXL);
-    if (a->ncat < 1 || a->ncat > MAXCAT) FAIL(c, "%s: ncat = %d not in 1..%d", who, a->ncat, MAXCAT);
-    if (a->ntrcr < 1 || a->ntrcr_dim < a->ntrcr || t.nt_Tsfc < 1 || t.nt_Tsfc > a->ntrcr)
-        FAIL(c, "%s: nt_Tsfc = %d lies beyond ntrcr = %d (ntrcr_dim = %d)", who, t.nt_Tsfc, a->ntrcr, a->ntrcr_dim);
-    if (cesm && (t.nt_apnd < 1 || t.nt_hpnd < 1 || t.nt_apnd > a->ntrcr || t.nt_hpnd > a->ntrcr))
-        FAIL(c, "%s: tr_pond_cesm without nt_apnd / nt_hpnd in 1..ntrcr = %d", who, a->ntrcr);
-    if (a->puny != 1.0e-11) FAIL(c, "%s: puny = %g: the device code is built with 1e-11", who, a->puny);
-    if (!(a->dT_mlt > 0.0)) FAIL(c, "%s: dT_mlt = %g", who, a->dT_mlt);
-    if (p) {
-        if (pond_lvl_check(c, who, t, a->ntrcr, p)) return 1;
-        if (!p->fsnow) FAIL(c, "%s: tr_pond_lvl needs fsnow", who);
-        if (!(p->dt > 0.0)) FAIL(c, "%s: dt = %g", who, p->dt);
-    }
-    if (!c->nblocks) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    DeddArgs A{};
-    A.ncat = a->ncat; A.ntrcr_dim = a->ntrcr_dim; A.nxb = c->nxb; A.nyb = c->nyb; A.nilyr = t.nilyr; A.nslyr = t.nslyr; A.nt_Tsfc = t.nt_Tsfc;
-    A.nt_apnd = t.nt_apnd; A.nt_hpnd = t.nt_hpnd; A.tr_pond_cesm = cesm ? 1 : 0;
-    A.puny = a->puny; A.rhos = c->p.rhos; A.R_snw = a->R_snw; A.dT_mlt = a->dT_mlt; A.rsnw_mlt = a->rsnw_mlt; A.kalg = a->kalg; A.hs0 = a->hs0;
-    A.pndaspect = a->pndaspect; A.awtvdr = a->awtvdr; A.awtidr = a->awtidr; A.awtvdf = a->awtvdf; A.awtidf = a->awtidf;
-    dedd_iops(a->R_ice, a->R_pnd, A.iop);
-    if (p) { A.nt_alvl = t.nt_alvl; A.nt_ipnd = p->nt_ipnd; A.linitonly = p->linitonly ? 1 : 0; A.hs1 = p->hs1; A.dt = p->dt; }
-    const size_t N = (size_t)c->nblocks * c->nyb * c->nxb, n3 = N * a->ncat;
-    std::vector<HostArr> arr = {            // (every output is written on every cell: none is copied up; coszen is in / out)
-        {a->aicen, n3, &A.aicen, false}, {a->vicen, n3, &A.vicen, false}, {a->vsnon, n3, &A.vsnon, false}, {a->trcrn, n3 * a->ntrcr_dim, &A.trcrn, false},
-        {a->swvdr, N, &A.swvdr, false}, {a->swvdf, N, &A.swvdf, false}, {a->swidr, N, &A.swidr, false}, {a->swidf, N, &A.swidf, false},
-        {a->coszen, N, &A.coszen, true},
-        {a->alvdrn, n3, &A.alvdrn, true, false}, {a->alidrn, n3, &A.alidrn, true, false}, {a->alvdfn, n3, &A.alvdfn, true, false},
-        {a->alidfn, n3, &A.alidfn, true, false}, {a->albicen, n3, &A.albicen, true, false}, {a->albsnon, n3, &A.albsnon, true, false},
-        {a->albpndn, n3, &A.albpndn, true, false}, {a->apeffn, n3, &A.apeffn, true, false}, {a->snowfracn, n3, &A.snowfracn, true, false},
-        {a->fswsfcn, n3, &A.fswsfcn, true, false}, {a->fswintn, n3, &A.fswintn, true, false}, {a->fswthrun, n3, &A.fswthrun, true, false},
-        {a->Sswabsn, n3 * t.nslyr, &A.Sswabsn, true, false}, {a->Iswabsn, n3 * t.nilyr, &A.Iswabsn, true, false},
-        {a->fswpenln, n3 * (t.nilyr + 1), &A.fswpenln, true, false},
-        {a->alvdr, N, &A.alvdr, true, false}, {a->alidr, N, &A.alidr, true, false}, {a->alvdf, N, &A.alvdf, true, false},
-        {a->alidf, N, &A.alidf, true, false}, {a->albice, N, &A.albice, true, false}, {a->albsno, N, &A.albsno, true, false},
-        {a->albpnd, N, &A.albpnd, true, false}, {a->apeff_ai, N, &A.apeff_ai, true, false}, {a->scale_factor, N, &A.scale_factor, true, false}};
-    if (p) {                                  // (dhsn is in / out on the listed cells)
-        arr.push_back({p->dhsn, n3, &A.dhsn, true});
-        arr.push_back({p->ffracn, n3, &A.ffracn, false});
-        arr.push_back({p->fsnow, N, &A.fsnow, false});
-    }
-    if (stage_in(c, arr, true)) return 1;
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // (staged caller arrays are pageable)
-    const dim3 b(64), g = block_grid(c);
-    const bool fixed = a->ncat == 5 && t.nilyr == 4 && t.nslyr == 1;
-    if (fixed && p)
-        hipLaunchKernelGGL((k_shortwave_dedd<5, 4, 1, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    else if (p)
-        hipLaunchKernelGGL((k_shortwave_dedd<0, 0, 0, 1>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    else if (fixed)
-        hipLaunchKernelGGL((k_shortwave_dedd<5, 4, 1, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    else
-        hipLaunchKernelGGL((k_shortwave_dedd<0, 0, 0, 0>), g, b, 0, c->stream, c->s, (const BlockDesc *)c->d_bd, A);
-    HIPCHK(c, hipGetLastError());
-    return stage_out(c, arr);
-}
-
-extern "C" int evpk_step_radiation_dedd(evpk_ctx *c, const evpk_dedd_args *a) {
-    if (!c) return 1;
-    RANKS_ENTRY(c, "evpk_step_radiation_dedd");
-    if (!a) FAIL(c, "evpk_step_radiation_dedd: a required argument is missing");
-    return dedd_run(c, "evpk_step_radiation_dedd", a, nullptr);
-}
-
-// step_radiation (dEdd) under tr_pond_lvl: the level-ice block of run_dEdd (source/ice_shortwave.F90:1450-1514) sets the ponds
-extern "C" int evpk_step_radiation_dedd_lvl(evpk_ctx *c, const evpk_dedd_args *a, const evpk_pond_lvl_args *p) {
-    if (!c) return 1;
-    RANKS_ENTRY(c, "evpk_step_radiation_dedd_lvl");
-    if (!a || !p) FAIL(c, "evpk_step_radiation_dedd_lvl: a required argument is missing");
-    return dedd_run(c, "evpk_step_radiation_dedd_lvl", a, p);
-}
-
-// the tables of evpk_dedd_tables.h by name (no context, no device): out[0 .. n), n the table's length; 1 for an unknown name or another n
-extern "C" int evpk_dedd_table(const char *name, double *out, int32_t n) {
-    using namespace dedd;
-    if (!name || !out) return 1;
-    struct Tab { const char *name; const double *p; int n; };
-    const Tab tabs[] = {{"rsnw_tab", rsnw_tab, NMBRAD}, {"Qs_tab", &Qs_tab[0][0], NSPINT * NMBRAD}, {"ws_tab", &ws_tab[0][0], NSPINT * NMBRAD},
-                        {"gs_tab", &gs_tab[0][0], NSPINT * NMBRAD},
-                        {"ki_ssl_mn", ki_ssl_mn, NSPINT}, {"wi_ssl_mn", wi_ssl_mn, NSPINT}, {"gi_ssl_mn", gi_ssl_mn, NSPINT},
-                        {"ki_dl_mn", ki_dl_mn, NSPINT}, {"wi_dl_mn", wi_dl_mn, NSPINT}, {"gi_dl_mn", gi_dl_mn, NSPINT},
-                        {"ki_int_mn", ki_int_mn, NSPINT}, {"wi_int_mn", wi_int_mn, NSPINT}, {"gi_int_mn", gi_int_mn, NSPINT},
-                        {"ki_p_ssl_mn", ki_p_ssl_mn, NSPINT}, {"wi_p_ssl_mn", wi_p_ssl_mn, NSPINT}, {"gi_p_ssl_mn", gi_p_ssl_mn, NSPINT},
-                        {"ki_p_int_mn", ki_p_int_mn, NSPINT}, {"wi_p_int_mn", wi_p_int_mn, NSPINT}, {"gi_p_int_mn", gi_p_int_mn, NSPINT},
-                        {"kw", kw, NSPINT}, {"ww", ww, NSPINT}, {"gw", gw, NSPINT}, {"gauspt", gauspt, NGMAX}, {"gauswt", gauswt, NGMAX},
-                        {"scalars", scalars, NSCALARS}};
-    for (const Tab &t : tabs)
-        if (!strcmp(name, t.name)) {
-            if (n != t.n) return 1;
-            for (int q = 0; q < n; q++) out[q] = t.p[q];
-            return 0;
-        }
-    return 1;
-}
+// ---- the column physics behind step_therm2: thermo_vertical, step_therm1, step_radiation (ccsm3, dEdd), prep_radiation ----
+#include "evpk_api_column.hip"
 
 extern "C" int evpk_calibrate(evpk_ctx *c, int32_t nrep) {
     if (c && c->idle) return 0;       // a rank without a block column: in no exchange, nothing to compute

@@ -816,6 +816,42 @@ class Context:
         self._chk(rc, "evpk_step_dynamics")
         return None
 
+    @staticmethod
+    def _itd_header(a, state, ntrcr, tracers):
+        """a.ncat and a.ntrcr_dim from the shapes of state's aicen and trcrn, a.ntrcr, and a.t from the tracers dict"""
+        aicen, trcrn = state.get("aicen"), state.get("trcrn")
+        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
+        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
+        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+
+    @staticmethod
+    def _pointers(a, *tables):
+        """a.<name> = the float64 array src[name], or NULL where src has none, for every (names, src) of tables"""
+        for names, src in tables:
+            for n in names:
+                setattr(a, n, _p64(src.get(n)))
+
+    @staticmethod
+    def _scalars(a, who, scalars, names, defaults):
+        """a.<name> for every name of names, from the keyword arguments scalars or else from defaults"""
+        unknown = set(scalars) - set(names)
+        if unknown:
+            raise TypeError(f"{who}: unknown arguments {sorted(unknown)}")
+        for n in names:
+            setattr(a, n, float(scalars.get(n, defaults[n])))
+
+    def _thermo_args(self, a, dt, state, forcing, inout, out, ntrcr, tracers, yday, conduct, min_salin, constants, ktherm, calc_Tsfc,
+                     heat_capacity, l_brine):
+        """fills the ThermoArgs a in place: thermo_vertical's own, or the tv of step_therm1's Therm1Args"""
+        from . import constants as C
+        a.dt, a.yday, a.min_salin = float(dt), float(yday), float(min_salin)
+        a.ktherm, a.calc_Tsfc, a.heat_capacity, a.l_brine = int(ktherm), int(bool(calc_Tsfc)), int(bool(heat_capacity)), int(bool(l_brine))
+        a.conduct = int({"MU71": 0, "bubbly": 1}.get(conduct, conduct))
+        self._itd_header(a, state, ntrcr, tracers)
+        a.nt_sice = int(tracers.get("nt_sice", 0))
+        a.k = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
+        self._pointers(a, (THERMO_STATE, state), (THERMO_FORCING, forcing), (THERMO_INOUT, inout), (THERMO_OUT, out))
+
     def _therm2_args(self, dt, state, forcing, fluxes, ntrcr, trcr_depend, tracers, hin_max, kitd, ktherm, update_ocn_f, yday, hi_min, hfrazilmin,
                      phi_init, dSin0_frazil, cp_ocn, constants, first_ice, tr_aero, nbtrcr, heat_capacity, skl_bgc):
         from . import constants as C
@@ -823,21 +859,16 @@ class Context:
         a.kitd, a.ktherm, a.update_ocn_f = int(kitd), int(ktherm), int(bool(update_ocn_f))
         a.dt, a.yday, a.hi_min, a.hfrazilmin = float(dt), float(yday), float(hi_min), float(hfrazilmin)
         a.phi_init, a.dSin0_frazil, a.cp_ocn = float(phi_init), float(dSin0_frazil), float(C.cp_ocn if cp_ocn is None else cp_ocn)
-        aicen, trcrn = state.get("aicen"), state.get("trcrn")
-        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
-        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
+        self._itd_header(a, state, ntrcr, tracers)
         dep = np.ascontiguousarray(trcr_depend, dtype=np.int32)
         a.trcr_depend = _p32(dep) if ntrcr else None
-        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
         a.nt_sice, a.nt_iage, a.nt_FY, a.nt_vlvl = (int(tracers.get(k, 0)) for k in ("nt_sice", "nt_iage", "nt_FY", "nt_vlvl"))
         hin = np.ascontiguousarray(hin_max, dtype=np.float64)
-        assert hin.shape == (a.ncat + 1,) or aicen is None
+        assert hin.shape == (a.ncat + 1,) or state.get("aicen") is None
         a.hin_max = _p64(hin)
         a.k = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
         a.tr_aero, a.nbtrcr, a.heat_capacity, a.skl_bgc = int(bool(tr_aero)), int(nbtrcr), int(bool(heat_capacity)), int(bool(skl_bgc))
-        for names, src in ((THERM2_STATE, state), (THERM2_FORCING, forcing), (THERM2_FLUXES, fluxes)):
-            for n in names:
-                setattr(a, n, _p64(src.get(n)))
+        self._pointers(a, (THERM2_STATE, state), (THERM2_FORCING, forcing), (THERM2_FLUXES, fluxes))
         a.first_ice = _p32(first_ice)
         return a, [dep, hin]
 
@@ -886,24 +917,10 @@ class Context:
         ITD_TRACER_FIELDS plus nt_sice, tr_iage, tr_FY, nt_iage, nt_FY.
         Returns None, or (reason, block, category, i, j) as thermo_vertical; raises on a refusal, which leaves every array untouched.
         (ponds: see step_therm1_lvl, which passes it.)"""
-        from . import constants as C
         a = Therm1Args()
-        v = a.tv
-        v.dt, v.yday, v.min_salin = float(dt), float(yday), float(min_salin)
-        v.ktherm, v.calc_Tsfc, v.heat_capacity, v.l_brine = int(ktherm), int(bool(calc_Tsfc)), int(bool(heat_capacity)), int(bool(l_brine))
-        v.conduct = int({"MU71": 0, "bubbly": 1}.get(conduct, conduct))
-        aicen, trcrn = state.get("aicen"), state.get("trcrn")
-        v.ncat = int(aicen.shape[1]) if aicen is not None else 0
-        v.ntrcr, v.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
-        v.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
-        v.nt_sice = int(tracers.get("nt_sice", 0))
-        v.k = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
-        for names, src in ((THERMO_STATE, state), (THERMO_FORCING, forcing), (THERMO_INOUT, inout), (THERMO_OUT, out)):
-            for n in names:
-                setattr(v, n, _p64(src.get(n)))
-        for names, src in ((THERM1_IN2D + ["fswthrun"], forcing), (THERM1_OUT + THERM1_DIAG, out), (["Cdn_atm"] + THERM1_MERGED, merged)):
-            for n in names:
-                setattr(a, n, _p64(src.get(n)))
+        self._thermo_args(a.tv, dt, state, forcing, inout, out, ntrcr, tracers, yday, conduct, min_salin, constants, ktherm, calc_Tsfc,
+                          heat_capacity, l_brine)
+        self._pointers(a, (THERM1_IN2D + ["fswthrun"], forcing), (THERM1_OUT + THERM1_DIAG, out), (["Cdn_atm"] + THERM1_MERGED, merged))
         for n in THERM1_MASKS:
             setattr(a, n, _p32(forcing.get(n)))
         a.chio, a.ustar_min, a.hi_min, a.pndaspect = float(chio), float(ustar_min), float(hi_min), float(pndaspect)
@@ -941,19 +958,10 @@ class Context:
         a = RadArgs()
         a.shortwave_dEdd, a.calc_Tsfc, a.heat_capacity = int(shortwave == "dEdd"), int(bool(calc_Tsfc)), int(bool(heat_capacity))
         a.albedo_constant = int(albedo_type == "constant")
-        aicen, trcrn = state.get("aicen"), state.get("trcrn")
-        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
-        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
-        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        self._itd_header(a, state, ntrcr, tracers)
         a.puny = float(puny)
-        unknown = set(scalars) - set(RAD_SCALARS)
-        if unknown:
-            raise TypeError(f"step_radiation: unknown arguments {sorted(unknown)}")
-        for n in RAD_SCALARS:
-            setattr(a, n, float(scalars.get(n, RAD_DEFAULTS[n])))
-        for names, src in ((RAD_STATE, state), (RAD_FORCING, forcing), (RAD_OUT + RAD_OUT_LAYERS + RAD_OUT2D, out)):
-            for n in names:
-                setattr(a, n, _p64(src.get(n)))
+        self._scalars(a, "step_radiation", scalars, RAD_SCALARS, RAD_DEFAULTS)
+        self._pointers(a, (RAD_STATE, state), (RAD_FORCING, forcing), (RAD_OUT + RAD_OUT_LAYERS + RAD_OUT2D, out))
         self._chk(self._L.evpk_step_radiation(self._ctx, ct.byref(a)), "evpk_step_radiation")
 
     def step_radiation_dedd(self, state, forcing, coszen, out, ntrcr: int, tracers, calc_Tsfc=True, heat_capacity=True, tr_aero=False,
@@ -969,19 +977,10 @@ class Context:
         a = DeddArgs()
         a.calc_Tsfc, a.heat_capacity, a.tr_aero = int(bool(calc_Tsfc)), int(bool(heat_capacity)), int(bool(tr_aero))
         a.tr_pond_cesm, a.tr_pond_lvl, a.tr_pond_topo = (int(bool(tracers.get(k, 0))) for k in ("tr_pond_cesm", "tr_pond_lvl", "tr_pond_topo"))
-        aicen, trcrn = state.get("aicen"), state.get("trcrn")
-        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
-        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
-        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
+        self._itd_header(a, state, ntrcr, tracers)
         a.puny = float(puny)
-        unknown = set(scalars) - set(DEDD_SCALARS)
-        if unknown:
-            raise TypeError(f"step_radiation_dedd: unknown arguments {sorted(unknown)}")
-        for n in DEDD_SCALARS:
-            setattr(a, n, float(scalars.get(n, DEDD_DEFAULTS[n])))
-        for names, src in ((DEDD_STATE, state), (DEDD_FORCING, forcing), (DEDD_OUT + DEDD_OUT_LAYERS + DEDD_OUT2D, out)):
-            for n in names:
-                setattr(a, n, _p64(src.get(n)))
+        self._scalars(a, "step_radiation_dedd", scalars, DEDD_SCALARS, DEDD_DEFAULTS)
+        self._pointers(a, (DEDD_STATE, state), (DEDD_FORCING, forcing), (DEDD_OUT + DEDD_OUT_LAYERS + DEDD_OUT2D, out))
         a.coszen = _p64(coszen)
         if ponds is None:
             self._chk(self._L.evpk_step_radiation_dedd(self._ctx, ct.byref(a)), "evpk_step_radiation_dedd")
@@ -1004,8 +1003,7 @@ class Context:
         aicen = arrays.get("aicen")
         a.ncat = int(aicen.shape[1]) if aicen is not None else 0
         a.nilyr, a.nslyr, a.puny = int(nilyr), int(nslyr), float(puny)
-        for n in PREP_RAD_IN + PREP_RAD_INOUT + ["fswfac"]:
-            setattr(a, n, _p64(arrays.get(n)))
+        self._pointers(a, (PREP_RAD_IN + PREP_RAD_INOUT + ["fswfac"], arrays))
         self._chk(self._L.evpk_prep_radiation(self._ctx, ct.byref(a)), "evpk_prep_radiation")
 
     def thermo_vertical(self, dt: float, state, forcing, inout, out, ntrcr: int, tracers, yday=0.0, conduct=0, min_salin=0.1, constants=None,
@@ -1018,20 +1016,9 @@ class Context:
         nt_sice; conduct: 0 / 'MU71' or 1 / 'bubbly'.
         Returns None, or (reason, block, category, i, j) for the reference's l_stop cases (THERMO_STOP_REASONS); raises on a refusal,
         which leaves every array untouched."""
-        from . import constants as C
         a = ThermoArgs()
-        a.dt, a.yday, a.min_salin = float(dt), float(yday), float(min_salin)
-        a.ktherm, a.calc_Tsfc, a.heat_capacity, a.l_brine = int(ktherm), int(bool(calc_Tsfc)), int(bool(heat_capacity)), int(bool(l_brine))
-        a.conduct = int({"MU71": 0, "bubbly": 1}.get(conduct, conduct))
-        aicen, trcrn = state.get("aicen"), state.get("trcrn")
-        a.ncat = int(aicen.shape[1]) if aicen is not None else 0
-        a.ntrcr, a.ntrcr_dim = int(ntrcr), (int(trcrn.shape[2]) if trcrn is not None else 0)
-        a.t = ItdTracers(**{k: int(tracers.get(k, 0)) for k in ITD_TRACER_FIELDS})
-        a.nt_sice = int(tracers.get("nt_sice", 0))
-        a.k = ItdConstants(**{k: float((constants or {}).get(k, getattr(C, k))) for k in ITD_CONSTANT_FIELDS})
-        for names, src in ((THERMO_STATE, state), (THERMO_FORCING, forcing), (THERMO_INOUT, inout), (THERMO_OUT, out)):
-            for n in names:
-                setattr(a, n, _p64(src.get(n)))
+        self._thermo_args(a, dt, state, forcing, inout, out, ntrcr, tracers, yday, conduct, min_salin, constants, ktherm, calc_Tsfc, heat_capacity,
+                          l_brine)
         stop = np.zeros(5, dtype=np.int32)
         rc = self._L.evpk_thermo_vertical(self._ctx, ct.byref(a), _p32(stop))
         if rc == THERMO_STOP:

@@ -746,7 +746,8 @@ typedef struct {
 } evpk_therm1_args;
 int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t stop[5] /* out: reason, block, category, i, j */);
 
-/* the shortwave of ice_step (kernels in csrc/evpk_rad.hip).  With it the per-category radiation arrays that
+/* the shortwave of ice_step (kernels in csrc/evpk_rad.hip, host layer in csrc/evpk_api_column.hip).
+ * With it the per-category radiation arrays that
  * evpk_step_therm1 reads (fswsfcn, fswintn, fswthrun, Sswabsn, Iswabsn) are made on the device from the state the project leaves there.
  *
  * evpk_step_radiation: step_radiation (source/ice_step_mod.F90:1364-1524) on its calc_Tsfc / not-dEdd branch -- shortwave_ccsm3
@@ -832,7 +833,8 @@ typedef struct {
 int evpk_step_radiation(evpk_ctx *c, const evpk_rad_args *a);
 int evpk_prep_radiation(evpk_ctx *c, const evpk_prep_rad_args *a);
 
-/* The Delta-Eddington shortwave (kernel in csrc/evpk_dedd.hip, tables in csrc/evpk_dedd_tables.h): the scheme every ice_in of the
+/* The Delta-Eddington shortwave (kernel in csrc/evpk_dedd.hip, tables in csrc/evpk_dedd_tables.h, host layer in
+ * csrc/evpk_api_column.hip): the scheme every ice_in of the
  * reference's own grids selects (shortwave = 'dEdd', reference/input_templates/{gx1,gx3,tp1,col}/ice_in).  evpk_step_radiation keeps
  * refusing shortwave_dEdd = 1; a Delta-Eddington host calls this instead.
  *
