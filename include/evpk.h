@@ -778,8 +778,12 @@ int evpk_step_therm1(evpk_ctx *c, const evpk_therm1_args *a, int32_t stop[5] /* 
  * Compiled in: kappav = 1.4, Timelt = 0 (drivers/auscom/ice_constants.F90:82, :65); dT_melt = 1, dalb_mlt = -0.075, dalb_mltv = -0.1,
  * dalb_mlti = -0.15 (source/ice_shortwave.F90:709-716: local parameters that shadow the namelist variable); i0vis = 0.70 (:1079);
  * warmice = 0.68, coldice = 0.70, warmsnow = 0.77, coldsnow = 0.81 (:923-927).
- * **Parity unpinned**: no recipe under oracle/ builds these routines; both calls are held bit for bit to a numpy restatement written
- * from the Fortran (tests/nprad.py).
+ * Both calls are held bit for bit to a numpy restatement written from the Fortran (tests/nprad.py).  shortwave_ccsm3 with
+ * compute_albedos, constant_albedos and absorbed_solar is PINNED to the reference's own compiled routines (oracle/ref/Makefile target
+ * shortwave, tests/golden/ref_sw_c_*.npz): the restatement equals those records bit for bit on libm, and the device is compared with them
+ * directly within four times the measured distance of its fixed-algorithm exp / atan from libm (at most 4.7e-16 of an array's largest
+ * magnitude; tests/test_shortwave_ref.py, test_shortwave_ref_gpu.py).  **Parity unpinned** stay step_radiation's call order and zeroing,
+ * the aggregation and scale_factor lines (the reference driver restates them), the stock scalar albocn path and evpk_prep_radiation.
  * Members (one struct of borrowed pointers; arrays (nx_block, ny_block[, ncat], nblocks) unless given):
  *   shortwave_dEdd, calc_Tsfc, heat_capacity (only 0, 1, 1 are accepted), albedo_constant (0 default / 1 'constant')
  *   ncat, ntrcr, ntrcr_dim, t (nt_Tsfc, nilyr, nslyr are read) as in evpk_thermo_args; puny (must be 1e-11)
@@ -890,8 +894,12 @@ int evpk_prep_radiation(evpk_ctx *c, const evpk_prep_rad_args *a);
  * Compiled in (csrc/evpk_dedd_tables.h names the lines): rsnw_tab, Qs_tab, ws_tab, gs_tab; the mean ice and pond optical properties; kw,
  * ww, gw; gauspt, gauswt; hi_ssl = 0.05, hs_ssl = 0.04, hpmin = 0.005, hp0 = 0.2, hs_min = 1e-4, rhoi = 917 (compute_dEdd's own), trmin =
  * 0.001, refindx = 1.31.  rhos is that of evpk_set_params.  evpk_dedd_table(name, out, n) reads any of them back.
- * **Parity unpinned**: nothing under oracle/ builds these routines; the call is held bit for bit to a numpy restatement written from the
- * Fortran (tests/npdedd.py) with its own copy of the tables.
+ * Parity: run_dEdd and everything below it are PINNED to the reference's own compiled routines (oracle/ref/Makefile target shortwave,
+ * tests/golden/ref_sw_d_*.npz): the restatement tests/npdedd.py, to which the call is held bit for bit, equals those records bit for bit
+ * on libm, and the device is compared with them directly within four times the measured distance of its fixed-algorithm exp from libm
+ * (at most 6.4e-14 of an array's largest magnitude; tests/test_shortwave_ref.py, test_shortwave_ref_gpu.py).
+ * **Parity unpinned** stay step_radiation's call order and zeroing, the albedo aggregation / scale_factor lines of coupling_prep (the
+ * reference driver restates them), aerosols and topographic ponds.
  * Members (one struct of borrowed pointers; arrays (nx_block, ny_block[, ncat], nblocks) unless given):
  *   calc_Tsfc, heat_capacity (only 1, 1 are accepted), tr_pond_cesm, tr_pond_lvl, tr_pond_topo, tr_aero (a pond flag set here or in t counts)
  *   ncat, ntrcr, ntrcr_dim, t (nt_Tsfc, nt_apnd, nt_hpnd, nilyr, nslyr are read) as in evpk_thermo_args; puny (must be 1e-11)
@@ -964,8 +972,11 @@ int evpk_dedd_table(const char *name, double *out, int32_t n);
  * :31, :29, :50, :45, :54); the permeability's 3e-8, 1e-3 and 0.05 (source/ice_meltpond_lvl.F90:393-402); hs_min = 1e-4
  * (drivers/auscom/ice_constants.F90:91), hpmin = 0.005 (source/ice_shortwave.F90:143), p15 = 0.15 (drivers/cice/ice_constants.F90:139).
  * rhoi, rhos, rhow are evpk_set_params'; cp_ice, Lfresh, puny come from tv.k.
- * **Parity unpinned**: no recipe under oracle/ builds these routines; both calls are held bit for bit to a numpy restatement written
- * from the Fortran (tests/nppondlvl.py, on top of tests/nptherm1s.py and tests/npdedd.py).
+ * Both calls are held bit for bit to a numpy restatement written from the Fortran (tests/nppondlvl.py, on top of tests/nptherm1s.py and
+ * tests/npdedd.py).  The tr_pond_lvl block of run_dEdd is PINNED with run_dEdd (tests/golden/ref_sw_v_*.npz, initonly absent and .true.),
+ * and compute_ponds_lvl with brine_permeability is pinned on the CPU (ref_sw_p_*.npz; the restatement alone -- the device has no entry
+ * point for it alone, and the AusCOM build's cp_ocn = 3989.24495292815 is handed to the restatement where the device carries 4218).
+ * **Parity unpinned** stays evpk_step_therm1_lvl as a whole, with step_therm1 and thermo_vertical.
  * evpk_pond_lvl_args: what the two routines hand each other, and the scheme's own namelist --
  *   dhsn     per category: the shortwave reads and writes it (listed cells), the thermodynamics reads it
  *   ffracn   per category: the thermodynamics writes it on every cell, the shortwave reads it

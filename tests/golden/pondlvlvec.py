@@ -16,6 +16,9 @@ and draws of their own:
   fsnow        therm1vec's, the one field both calls read: zero on half of the cells, else up to 4e-5 kg m-2 s-1 (fsnow dt > hs_min)
   dhsn         0; hs exactly (the pond ice is snow-free though the sea ice is not); 0.2 .. 0.8 hs; 0.05 m over bare ice (reset)
   ffracn       0, 1, or a draw strictly between
+  hpnd         on up to EDGE_COLUMNS snow-covered ponded columns per input with ffracn = 0 and dhsn = 0: the depth at which rp = rhofresh hp /
+               (rhofresh hp + rhos hs) comes out EXACTLY p15 in double precision, so that the strict comparison rp < p15 of run_dEdd's
+               level-ice block (source/ice_shortwave.F90:1493) decides them ("p15_edge")
 The shortwave's outputs are deddvec's non-zero pre-fills: a test that calls the thermodynamics alone takes fswsfcn, fswintn, fswthrun,
 Sswabsn and Iswabsn (CARRIED) from a shortwave call on the same input, as a time step does.
 """
@@ -38,6 +41,19 @@ CARRIED = ["fswsfcn", "fswintn", "fswthrun", "Sswabsn", "Iswabsn"]
 LID = [("none", 0.4), ("thin", 0.25), ("thick", 0.35)]
 DHS = [("zero", 0.45), ("all", 0.2), ("part", 0.2), ("stale", 0.15)]
 FFRAC = [("zero", 0.5), ("one", 0.2), ("mid", 0.3)]
+EDGE_COLUMNS = 12
+RHOFRESH, P15 = 1000.0, 0.15                                      # drivers/auscom/ice_constants.F90:56, :139 of drivers/cice's
+
+
+def _hp_at_p15(hs, rhos):
+    """the pond depth hp for which rhofresh hp / (rhofresh hp + rhos hs) rounds to exactly p15, or None if no double does"""
+    hp = np.float64(P15 * rhos * hs / ((1.0 - P15) * RHOFRESH))
+    for _ in range(64):
+        rp = (RHOFRESH * hp) / (RHOFRESH * hp + rhos * hs)
+        if rp == P15:
+            return float(hp)
+        hp = np.nextafter(hp, np.inf if rp < P15 else -np.inf)
+    return None
 
 
 def pondlvl_input(cfg, tcase):
@@ -98,5 +114,17 @@ def pondlvl_input(cfg, tcase):
     fk = kind(h("ffrackind", s3), FFRAC)
     x["ffracn"] = np.ascontiguousarray(np.where(fk == "one", 1.0, np.where(fk == "mid", 0.02 + 0.96 * h("ffracn", s3), 0.0)))
     x["dhs_kinds"], x["ffrac_kinds"] = dk, fk
+    # the columns on the edge of rp < p15: ponded (not a speck), under at least 1 mm of snow, nothing else hiding the pond
+    edge = np.zeros(s3, dtype=bool)
+    t = x["trcrn"]
+    cand = x["ocean"][:, None] & (a > PUNY) & ~tiny & (hs >= 1.0e-3) & np.isin(pk, ("shallow", "trans", "deep")) & (fk == "zero") & (dk == "zero")
+    for b, n, j, i in zip(*np.nonzero(cand)):
+        if edge.sum() == EDGE_COLUMNS:
+            break
+        hp = _hp_at_p15(float(x["vsnon"][b, n, j, i]) / float(a[b, n, j, i]), x["k"]["rhos"])
+        if hp is not None:
+            t[b, n, n0 + 1, j, i] = hp
+            edge[b, n, j, i] = True
+    x["p15_edge"] = edge
     x.update(NAMELIST)
     return x

@@ -1,4 +1,4 @@
-"""What the six generators tests/golden/make_ref_*.py share: building a program of oracle/_ref (oracle/ref/Makefile), packing its
+"""What the seven generators tests/golden/make_ref_*.py share: building a program of oracle/_ref (oracle/ref/Makefile), packing its
 in.bin, running it in a scratch directory and reading its out.bin, and the helpers that put block arrays into the records' form.
 The builds and runs work in the build container only (the reference does not travel); the helpers are used by the tests as well."""
 from __future__ import annotations
@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REFDIR = os.path.join(ROOT, "oracle", "ref")
 # the make target that builds each program (`kernels` builds ref_kernels and ref_remap together)
-TARGET = {"ref_harness": "all", "ref_kernels": "kernels", "ref_remap": "kernels", "ref_ridge": "ridge", "ref_itd": "itd", "ref_therm2": "therm2"}
+TARGET = {"ref_harness": "all", "ref_kernels": "kernels", "ref_remap": "kernels", "ref_ridge": "ridge", "ref_itd": "itd", "ref_therm2": "therm2",
+          "ref_shortwave": "shortwave"}
 # the tracer indices and switches ref_therm2.F90 reads, in its order; ref_itd.F90 reads the same without nt_sice and nt_FY
 IDX = ("nt_Tsfc", "nt_qice", "nt_qsno", "nt_sice", "nt_alvl", "nt_vlvl", "nt_apnd", "nt_hpnd", "nt_fbri", "nt_iage", "nt_FY", "tr_pond_cesm",
        "tr_pond_lvl", "tr_pond_topo", "tr_brine")
@@ -23,11 +24,11 @@ def exe(program, cfg):
     return os.path.join(ROOT, "oracle", "_ref", cfg, program)
 
 
-def build(program, cfg, dims, ncat):
-    """makes oracle/_ref/<cfg>/<program> for dims = (nx, ny, bx, by, mxb) and ncat categories; returns its path"""
+def build(program, cfg, dims, ncat, layers=(4, 1)):
+    """makes oracle/_ref/<cfg>/<program> for dims = (nx, ny, bx, by, mxb), ncat categories and layers = (nilyr, nslyr); returns its path"""
     nx, ny, bx, by, mxb = dims
     subprocess.check_call(["make", "-C", REFDIR, TARGET[program], f"CFG={cfg}", f"NX={nx}", f"NY={ny}", f"BX={bx}", f"BY={by}", f"MXB={mxb}",
-                           f"NCAT={ncat}"], stdout=subprocess.DEVNULL)
+                           f"NCAT={ncat}", f"NILYR={layers[0]}", f"NSLYR={layers[1]}"], stdout=subprocess.DEVNULL)
     return exe(program, cfg)
 
 

@@ -4,7 +4,8 @@
                     shortwave_dEdd_set_pond (:3893-3958), shortwave_dEdd (:1607-2024), compute_dEdd (:2034-3261), solution_dEdd (:3270-3772)
   coupling_prep     the albedo lines, drivers/auscom/CICE_RunMod.F90:503-548, :564-567, :582-586
 
-**PARITY IS UNPINNED**: no reference-built record of these routines exists; this file is held to the Fortran by reading.
+Parity: run_dEdd and below are held to reference-built records (tests/golden/ref_sw_d_*.npz, tests/test_shortwave_ref.py: bit for bit on
+LIBM); the call order and the coupling_prep lines are held to the Fortran by reading.
 
 Vectorised over the listed cells of one category of one block (the Fortran's ij loops); the loops over surface types, bands, layers and
 Gaussian angles are the Fortran's.  Every numpy operation is one IEEE operation per element, in the Fortran's order; a branch is a mask

@@ -13,7 +13,8 @@ reads inside it; the routine writes only apnd, hpnd, ipnd of its own category an
 Shortwave (step_radiation_dedd_lvl): its own category loop -- shortwave_dEdd_set_snow as tests/npdedd.step_radiation_dedd has it, the
 level-ice block, npdedd.shortwave_dEdd with the modified fs, hs, fp, hp, then the coupling_prep lines.
 
-**PARITY IS UNPINNED**: no reference-built record of these routines exists; this file is held to the Fortran by reading.
+Parity: the tr_pond_lvl block of run_dEdd and compute_ponds_lvl / brine_permeability are held to reference-built records
+(tests/golden/ref_sw_v_*.npz, ref_sw_p_*.npz, tests/test_shortwave_ref.py: bit for bit on LIBM); step_therm1_lvl as a whole is not.
 
 min / max are a comparison and a select; sign(a, b) is copysign; x**3 is (x*x)*x; sqrt is IEEE; exp is a parameter (PORTS: the device's
 bits).  Stated departure, shared with the device: compute_ponds_lvl's cell list requires tmask.  ktherm is 1, so the drainage runs
@@ -41,8 +42,8 @@ THERM_KEYS = ["ponds_listed", "listed_tiny_area", "thin_ice", "cesm_freeze", "ce
               "growth_clamped", "warm_air", "lid_melts_ffrac1", "lid_melts_ffrac_lt1", "lid_melts_snow", "volpn_le0", "existing_kept",
               "existing_lost", "new_ponds", "runoff", "freeboard_binds", "freeboard_negative", "drain_perm0", "drain_partial",
               "drain_complete", "dpscale_off"]
-SW_KEYS = ["dhs_initialised", "dhs_reset", "linitonly_suppressed", "tapered", "rp_lt_p15", "tmp_one", "tmp_zero_hsn_reduced", "hpn_lt_hpmin",
-           "fsn_cut", "ffracn_mid"]
+SW_KEYS = ["dhs_initialised", "dhs_reset", "linitonly_suppressed", "tapered", "rp_lt_p15", "rp_eq_p15", "tmp_one", "tmp_zero_hsn_reduced",
+           "hpn_lt_hpmin", "fsn_cut", "ffracn_mid"]
 
 _min, _max = nptherm1._min, nptherm1._max
 
@@ -50,11 +51,12 @@ _min, _max = nptherm1._min, nptherm1._max
 def brine_permeability(nilyr, qicen, salin, p):
     """:351-404 with calculate_Tin_from_qin (l_brine); qicen, salin: lists of nilyr floats"""
     rhoi, cp_ice, Lfresh = p["rhoi"], p["cp_ice"], p["Lfresh"]
+    cp_ocn = p.get("cp_ocn_build", CP_OCN)                 # (the AusCOM build fixes another value: tests/golden/make_ref_shortwave.py)
     phimin = C0
     for k in range(nilyr):
         Tmlt = (-salin[k]) * DEPRESST
         aa1 = cp_ice
-        bb1 = (((CP_OCN - cp_ice) * Tmlt) - qicen[k] / rhoi) - Lfresh
+        bb1 = (((cp_ocn - cp_ice) * Tmlt) - qicen[k] / rhoi) - Lfresh
         cc1 = Lfresh * Tmlt
         Tin = _min((-bb1 - math.sqrt(bb1 * bb1 - (C4 * aa1) * cc1)) / (C2 * aa1), Tmlt)
         Sbr = C1 / (1.0e-3 - np.float64(DEPRESST) / np.float64(Tin))
@@ -295,6 +297,7 @@ def step_radiation_dedd_lvl(blocks, tmask, p, y, M=npdedd.PORTS):
                 hpi = (RHOFRESH * hp + (rhos * hs) * tmp) / (RHOFRESH - rhos * (C1 - tmp))
                 hs_new = hs - (hpi * fp) * (C1 - tmp)
                 pinfo["rp_lt_p15"] += int(hide.sum())
+                pinfo["rp_eq_p15"] += int((soak & (rp == P15) & (fp > C0)).sum())
                 pinfo["tmp_one"] += int((soak & (tmp == C1)).sum())
                 pinfo["tmp_zero_hsn_reduced"] += int((soak & (tmp == C0) & (hs_new < hs)).sum())
                 hs = np.where(soak, hs_new, hs)

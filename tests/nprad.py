@@ -6,7 +6,8 @@ evpk_step_radiation and evpk_prep_radiation (tests/test_rad_gpu.py), independent
                    and behind it the albedo lines of coupling_prep (drivers/auscom/CICE_RunMod.F90:503-548, :564-567, :582-586)
   prep_radiation   source/ice_step_mod.F90:33-145
 
-**PARITY IS UNPINNED**: no reference-built record of these routines exists; this file is held to the Fortran by reading.
+Parity: shortwave_ccsm3 and below are held to reference-built records (tests/golden/ref_sw_c_*.npz, tests/test_shortwave_ref.py: bit for bit
+on LIBM); prep_radiation, the call order and the coupling_prep lines are held to the Fortran by reading.
 
 The math functions are parameters: PORTS (npridge.dev_exp and tests/npfmath2.py: the device's bits) or LIBM (math.exp / math.atan).
 min / max are a comparison and a select.  Stated departure, shared with the device (include/evpk.h): the cell lists require tmask.

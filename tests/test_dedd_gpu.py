@@ -1,8 +1,9 @@
 """evpk_step_radiation_dedd on the device against the numpy restatement tests/npdedd.py -- bit for bit, on every cell of every output: the
 call writes every cell (zeros where the cell is not listed), so ghost cells, land and the ice-free block are compared too; coszen is in /
 out and keeps the caller's bits outside the listed, lit cells.  The kernel uses + - x /, sqrt, comparisons, selects and the fixed-algorithm
-exp (dev_exp, whose array port the restatement runs on), and the library is built with -ffp-contract=off.  **Parity with the reference is
-unpinned** (no reference-built record).  Inputs: tests/golden/deddvec.py (no shape larger than 26 x 18 cells); tests/test_dedd_host.py
+exp (dev_exp, whose array port the restatement runs on), and the library is built with -ffp-contract=off.  Parity with the reference:
+tests/test_shortwave_ref.py holds the restatement, and tests/test_shortwave_ref_gpu.py the device, to reference-built records of run_dEdd and
+below; step_radiation's call order, the aggregation lines of coupling_prep, aerosols and topographic ponds stay unpinned.  Inputs: tests/golden/deddvec.py (no shape larger than 26 x 18 cells); tests/test_dedd_host.py
 shows that they take every branch.
 """
 import os

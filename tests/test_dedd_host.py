@@ -3,7 +3,8 @@ by member); the tables the library holds (evpk_dedd_table) equal, bit for bit, t
 where the reference is present -- the literals of the cited lines; exp_min is the double nearest to e^-10; the array version of dev_exp
 equals npridge.dev_exp element for element; and the inputs of tests/golden/deddvec.py take every branch the restatement counts.
 
-**Parity with the reference is unpinned**: no reference-built record exists for these routines.
+Parity with the reference: tests/test_shortwave_ref.py holds the restatement to reference-built records of run_dEdd and below; the call
+order and the aggregation lines of coupling_prep stay unpinned.
 
 The spread between the restatement on the port of the device's exp and on libm is printed per array: a record, not
 a bound.

@@ -2,8 +2,9 @@
 cell of every array either call may write: ghost cells, land and the ice-free block included (ffracn is written everywhere; dhsn, the
 tracer planes and every other in / out array keep the caller's bits wherever the cell is not listed).  The kernels use + - x /, the IEEE
 sqrt, comparisons, selects, copysign and the fixed-algorithm math of their parents, and the library is built with -ffp-contract=off.
-**Parity with the reference is unpinned** (no reference-built record).  Inputs: tests/golden/pondlvlvec.py (no shape larger than 26 x 18
-cells); tests/test_pondlvl_host.py shows that they take every branch.
+Parity with the reference: the level-ice block of run_dEdd is pinned with run_dEdd (tests/test_shortwave_ref.py the restatement,
+tests/test_shortwave_ref_gpu.py the device) and compute_ponds_lvl on the CPU; evpk_step_therm1_lvl as a whole stays unpinned with
+step_therm1.  Inputs: tests/golden/pondlvlvec.py (no shape larger than 26 x 18 cells); tests/test_pondlvl_host.py shows that they take every branch.
 """
 import os
 import sys

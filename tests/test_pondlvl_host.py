@@ -3,7 +3,8 @@ bound (header, ctypes structure and Fortran type member by member); the inputs o
 restatement tests/nppondlvl.py counts, over the union of the committed cases; and the restatement reduces to the existing checkers where
 the scheme has nothing to do.
 
-**Parity with the reference is unpinned**: no reference-built record exists for these routines.
+Parity with the reference: tests/test_shortwave_ref.py holds the level-ice block of run_dEdd and compute_ponds_lvl to reference-built
+records; step_therm1_lvl as a whole stays unpinned with step_therm1.
 """
 import ctypes as ct
 import os

@@ -2,7 +2,9 @@
 writes every cell of every output, so its arrays are compared on every cell; prep_radiation's in / out arrays carry sentinels in their
 ghost cells (and the category arrays on land too), which must survive.  The kernels use + - x /, comparisons, selects and the
 fixed-algorithm exp and atan (csrc/evpk_fmath2.h, whose Python ports the restatement runs on), and the library is built with
--ffp-contract=off.  **Parity with the reference is unpinned** (no reference-built record).  Inputs: tests/golden/radvec.py (no shape
+-ffp-contract=off.  Parity with the reference: tests/test_shortwave_ref.py holds the restatement, and tests/test_shortwave_ref_gpu.py the
+device, to reference-built records of shortwave_ccsm3 and below; prep_radiation, step_radiation's call order, the aggregation lines and the
+scalar albocn path stay unpinned.  Inputs: tests/golden/radvec.py (no shape
 larger than 26 x 18 cells); tests/test_rad_host.py shows that they take every branch.
 """
 import os

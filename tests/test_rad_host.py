@@ -4,7 +4,8 @@ branch the inputs of tests/golden/radvec.py are drawn for and satisfies, recompu
 absorbed_solar, the bounds of the albedos and the sums of coupling_prep; step_radiation followed by prep_radiation under the same
 shortwave is the identity, which pins the order in which both build the net shortwave.
 
-**Parity with the reference is unpinned**: no reference-built record exists for these routines.
+Parity with the reference: tests/test_shortwave_ref.py holds the restatement to reference-built records of shortwave_ccsm3 and below;
+prep_radiation, the call order, the aggregation lines and the scalar albocn path stay unpinned.
 
 The spread between the restatement on the ports of the device's math (tests/npfmath2.py, npridge.dev_exp) and on libm is printed per
 array and bounded by four times the spread measured here with libm, as

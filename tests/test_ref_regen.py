@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests import refcompile as R
-from tests.golden import itdvec, make_ref_therm2, refrun, refvec, ridgevec
+from tests.golden import itdvec, make_ref_shortwave, make_ref_therm2, refrun, refvec, ridgevec
 
 # generator -> (the names of its fixtures, the program it runs, the builds of that program)
 FAMILIES = {
@@ -20,6 +20,7 @@ FAMILIES = {
     "make_ref_ridge": (["ref_ridge_*.npz"], "ref_ridge", ridgevec.CONFIGS),
     "make_ref_itd": (["ref_itd_*.npz"], "ref_itd", itdvec.CONFIGS),
     "make_ref_therm2": (["ref_litd_*.npz", "ref_therm2_*.npz"], "ref_therm2", make_ref_therm2.BUILDS),
+    "make_ref_shortwave": (["ref_sw_*.npz"], "ref_shortwave", make_ref_shortwave.BUILDS),
 }
 EXES = [refrun.exe(program, cfg) for _, program, cfgs in FAMILIES.values() for cfg in cfgs]
 pytestmark = pytest.mark.skipif(not (os.path.isdir(R.REF) and os.path.exists(R.FC) and all(os.path.exists(e) for e in EXES)),
